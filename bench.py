@@ -2,7 +2,7 @@
 """Headline benchmark: HR pixels / second of the RRDB-23 x4 generator + CEM (eval mode) forward on synthetic
 32 x 3 x 128 x 128 fp32 batches per GPU (BASELINE.json configs[1]), weak scaling over N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 launches its own ranks (python -m torch.distributed.run, one process per GPU, RCCL) unless it already runs
 under a launcher (WORLD_SIZE set).  A step = one pass of the hot path over one batch already resident in HBM.  Rank 0 prints ONE
@@ -17,6 +17,9 @@ roofline fractions: against the fp32-equivalent algorithmic bytes and against th
 
 `--workload c3` times the generator + discriminator training step of configs[2] at its per-GPU shape (32 crops of 52x52, latent 3)
 with the gradient all-reduce over RCCL when N > 1.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step (rank 0's arrays) as DIR/<name>.npy,
+so that two builds run with the same arguments (same seeded inputs and weights) can be compared output for output: see dump_outputs.
 """
 import argparse
 import json
@@ -41,6 +44,9 @@ FLOP_PER_FWD = LR_PX_THROUGH_G * FLOP_PER_LR_PX                    # 25.13 TFLOP
 HBM_PEAK = 8.0e12
 N_CONV_LAUNCHES = 3 + NB * 15 + 2 + 1                              # 351
 MFMA_TERMS = {'split': 3, 'f16x2': 2, 'mixed': 1.16}              # bf16/f16 MFMA instructions issued per product, network average
+
+DUMP_BYTES = 64 * 10 ** 6                                          # --dump-outputs: all .npy files of one run together, headers included
+NPY_HEADER_RESERVE = 4096                                          # per file, on top of the data (a .npy header is 128 bytes for these arrays)
 
 # what the `traffic: null` of the c3 / c4 / c5 roofline blocks means: HBM counters need rocprofv3 passes, which this process cannot take of itself
 TRAFFIC_NOT_COLLECTED = ('not collected by this run (PMC counters need separate rocprofv3 --pmc passes: tools/pmc_workload.sh %s); committed '
@@ -222,6 +228,38 @@ def newest_pmc_mfma(precision):
     return _static_pmc(fs[-1], 'all_conv_launches')
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: tensor} as out_dir/<name>.npy, float64 where the tensor is float64 and float32 otherwise, DUMP_BYTES at
+    most together.  Arrays are written smallest first, each whole if it fits its even share of the bytes still free; a larger one becomes a
+    1-D sample of its flattened elements at sorted indices drawn (with replacement) from a generator seeded by its name and shape, so that
+    every run with the same arguments writes the same elements.  Returns {name: {'shape', 'sampled_elements'}} for the result line."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    free = DUMP_BYTES
+    record = {}
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        share = free // (len(items) - i) - NPY_HEADER_RESERVE
+        flat = t.reshape(-1)
+        k = None
+        if flat.numel() * dtype.itemsize > share:
+            k = share // dtype.itemsize
+            g = torch.Generator().manual_seed(zlib.crc32(('%s %s' % (name, tuple(t.shape))).encode()))
+            idx = torch.randint(flat.numel(), (k,), generator=g).sort().values
+            a = flat[idx.to(flat.device)].to(dtype).cpu().numpy()
+        else:
+            a = t.to(dtype).cpu().numpy()
+        path = os.path.join(out_dir, name + '.npy')
+        np.save(path, a)
+        free -= os.path.getsize(path)
+        record[name] = {'shape': list(t.shape), 'sampled_elements': k}
+    return record
+
+
 # ---------------------------------------------------------------------------------------------------------------- main
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -243,7 +281,13 @@ def parse_args(argv=None):
                          "(one weight-gradient launch per bucket, each followed by its all-reduce: esr_hip.dist.EarlyBucketReducer) instead of after it")
     ap.add_argument('--no-extra-workloads', action='store_true',
                     help="skip the short configs[2] / configs[4] runs appended (after the headline's timed region) as `extra_workloads`")
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, float32 or "
+                         "float64, 64 MB at most in all (a larger array as a fixed seeded sample of its elements)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def main(argv=None):
@@ -383,6 +427,7 @@ def run_c2(args, dev, rank, world, dist, sync, max_over_ranks):
     ms_per_step = dt / args.steps * 1e3
     hr_px = BATCH * (SF * LR_SIZE) ** 2
     value = world * hr_px * args.steps / dt
+    dumped = dump_outputs(args.dump_outputs, {'output': y}) if args.dump_outputs and rank == 0 else None
     if rank != 0:
         if precision == 'split' and not args.no_alt_precision:      # every rank takes part in the alt timing's barriers
             net.set_precision('mixed')
@@ -421,6 +466,8 @@ def run_c2(args, dev, rank, world, dist, sync, max_over_ranks):
                      'mfma_bf16_issue_frac_of_measured_1.79PF': terms * FLOP_PER_FWD / (conv_ms * 1e-3) / 1.79e15},
         'cem_consistency_rmse_interior': cons,
     }
+    if dumped:
+        out['dumped_outputs'] = dumped
     if BATCH == 32:
         # The wrapping CEM projection alone (A6-A8: out = g + U(K(x - D(g))), cropped), timed live with events over 20 back-to-back projections of the
         # generator's output, against SURVEY section 8(a) A8's algorithmic minimum (read g 134.6 MB + x 8.4 MB, write out 100.7 MB)
@@ -508,7 +555,7 @@ def extra_workloads(args, dev, rank, world, dist, sync, max_over_ranks):
     blocks = (('c3', run_c3, 5, 3), ('c5', run_c5, 5, 3), ('c4', run_c4, 2, 1)) if world == 1 else (('c3', run_c3, 5, 3),)
     for name, fn, steps, warmup in blocks:
         a = copy.copy(args)
-        a.workload, a.steps, a.warmup, a.precision, a.comm_diag = name, steps, warmup, None, world > 1
+        a.workload, a.steps, a.warmup, a.precision, a.comm_diag, a.dump_outputs = name, steps, warmup, None, world > 1, None
         gc.collect()
         torch.cuda.empty_cache()
         t0 = time.perf_counter()
@@ -560,6 +607,14 @@ def run_c3(args, dev, rank, world, dist, sync, max_over_ranks):
         model.feed_data(data); model.optimize_parameters()
     sync()
     dt, per_rank = max_over_ranks(time.perf_counter() - t0)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's generator output, both networks' parameters after its Adam steps and its losses
+        flat = lambda net: torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        arrays = {'fake_H': model.fake_H, 'G_parameters': flat(model.netG), 'D_parameters': flat(model.netD)}
+        arrays.update({'loss_' + k: torch.tensor(float(v), dtype=torch.float64) for k, v in model.get_current_log().items()
+                       if isinstance(v, (int, float))})
+        dumped = dump_outputs(args.dump_outputs, arrays)
     # per-phase GPU times from a few extra steps OUTSIDE the timed region: the phase timers synchronise at the end of every step, which
     # costs the overlap of the host's launch work with the GPU (49-50 instead of 45-46 ms per step)
     nphase = min(args.steps, 5)
@@ -624,7 +679,7 @@ def run_c3(args, dev, rank, world, dist, sync, max_over_ranks):
     # per element the precision stores (one 16-bit plane, or hi + lo)
     eng_g = getattr(model.netG.generated_image_model, 'engine', None)
     bytes_g = 3 * B * 52 * 52 * (49268 + 15728) * (4 if precision in ('split', 'mixed') else 2)
-    return {'metric': 'LR crops/sec (RRDB-23 x4 lat 3 G + Discriminator_VGG_128 WGAN-GP step, 32 x 52x52 per GPU)', 'value': world * B * args.steps / dt, 'unit': 'LR crops/s',
+    out = {'metric': 'LR crops/sec (RRDB-23 x4 lat 3 G + Discriminator_VGG_128 WGAN-GP step, 32 x 52x52 per GPU)', 'value': world * B * args.steps / dt, 'unit': 'LR crops/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None, 'dtype': DTYPE.get(precision, precision) + ' (generator); discriminator ' + (('%s on the HIP kernels (esr_hip/critic.py)' % ('bf16' if d_bf16 else 'bf16x3'))
                                                                               if model.D_engine is not None else ('%s on MIOpen' % ('bf16 autocast' if d_bf16 else 'fp32'))), 'data': 'synthetic',
@@ -642,6 +697,9 @@ def run_c3(args, dev, rank, world, dist, sync, max_over_ranks):
                          'generator_algorithmic_bytes_per_step': bytes_g, 'generator_hbm_frac_of_step': bytes_g / (dt / args.steps) / 8.0e12,
                          'note': 'MFMA issue rate (and, beside it, the layer-granular HBM bytes) of the generator over the WHOLE step time: D, optimizers '
                                  'and all-reduce are in the denominator; per-owner GPU time of a step: profiles/*_c3_*_step_kernels.csv'}}
+    if dumped:
+        out['dumped_outputs'] = dumped
+    return out
 
 
 def run_c4(args, dev, rank, world, dist, sync, max_over_ranks):
@@ -676,18 +734,20 @@ def run_c4(args, dev, rank, world, dist, sync, max_over_ranks):
         torch.cuda.reset_peak_memory_stats()
         sync()
         t0 = time.perf_counter()
-        zo.optimize()
+        Z = zo.optimize()
         sync()
     dt, per_rank = max_over_ranks(time.perf_counter() - t0)
     peak = torch.cuda.max_memory_allocated() / 2 ** 30
     if rank != 0:
         return None
+    # the Z samples the timed optimize() returned and its loss history
+    dumped = dump_outputs(args.dump_outputs, {'Z': Z, 'loss_values': torch.tensor(zo.loss_values, dtype=torch.float64)}) if args.dump_outputs else None
     t_it = dt / args.steps
     lr_px = B * 148 * 148                                    # LR pixels through G per iteration (1,401,856 at B = 64)
     flop = 2 * 2 * 18316944 * lr_px                          # forward + data gradient, RRDB-23 x4 lat 3
     algo_bytes = 2 * 259984 * lr_px                          # layer-granular fp32-equivalent bytes of the two passes
     terms = MFMA_TERMS.get(precision, 1)
-    return {'metric': 'HR pixels/sec of Z-search iterations (RRDB-23 x4 lat 3 + CEM, 64 Z samples of 512x512, forward + data gradient + Adam on Z)',
+    out = {'metric': 'HR pixels/sec of Z-search iterations (RRDB-23 x4 lat 3 + CEM, 64 Z samples of 512x512, forward + data gradient + Adam on Z)',
             'value': B * 512 * 512 * args.steps / dt, 'unit': 'HR pixels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': t_it * 1e3,
             'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': DTYPE.get(precision, precision), 'data': 'synthetic',
             'config': {'workload': 'configs[3]: Z_optimizer.optimize(), STD_increase, %d Z samples of 512x512 on one 128x128 LR image (G on 148x148), Adam lr 0.1; '
@@ -702,6 +762,9 @@ def run_c4(args, dev, rank, world, dist, sync, max_over_ranks):
                          'fp32_equiv_tflops': flop / t_it / 1e12 / world, 'algorithmic_bytes_per_iteration': algo_bytes,
                          'hbm_frac': algo_bytes / t_it / HBM_PEAK / world,
                          'note': 'MFMA issue rate over the WHOLE iteration (CEM, objective, Adam and the host in the denominator); per GPU'}}
+    if dumped:
+        out['dumped_outputs'] = dumped
+    return out
 
 
 def run_c5(args, dev, rank, world, dist, sync, max_over_ranks):
@@ -743,6 +806,7 @@ def run_c5(args, dev, rank, world, dist, sync, max_over_ranks):
         d = G.DownscaleOP(y)
     if rank != 0:
         return None
+    dumped = dump_outputs(args.dump_outputs, {'output': y}) if args.dump_outputs else None
     m = int(cem.invalidity_margins_LR)
     cons = float(((d - x)[..., m:-m, m:-m] ** 2).mean().sqrt())
     t = dt / args.steps
@@ -754,7 +818,7 @@ def run_c5(args, dev, rank, world, dist, sync, max_over_ranks):
     flop = 2 * 22138560 * lr_px
     terms = MFMA_TERMS.get(precision, 1)
     n_launch = 3 + NB * 15 + 3 + 1
-    return {'metric': 'HR pixels/sec (RRDB-23 x8, 256->2048, 16 images, fwd + CEM with the blurry_cubic_2.0 kernel)', 'value': B * 2048 * 2048 * args.steps / dt,
+    out = {'metric': 'HR pixels/sec (RRDB-23 x8, 256->2048, 16 images, fwd + CEM with the blurry_cubic_2.0 kernel)', 'value': B * 2048 * 2048 * args.steps / dt,
             'unit': 'HR pixels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': t * 1e3, 'higher_is_better': True, 'scaling': 'strong',
             'vs_baseline': None, 'dtype': DTYPE.get(precision, precision), 'data': 'synthetic',
             'config': {'workload': "configs[4]: RRDB-23 x8 SR forward, %d images of 256x256 -> 2048x2048, CEM with upscale_kernel='blurry_cubic_2.0' (eval: G on %dx%d)" % (B, side, side),
@@ -767,6 +831,9 @@ def run_c5(args, dev, rank, world, dist, sync, max_over_ranks):
                          'generator_ms_per_step': conv_ms, 'avg_launch_ms': conv_ms / n_launch,
                          'mfma_issue_frac': terms * flop / (conv_ms * 1e-3) / 2.5e15,
                          'note': 'layer-granular bytes at the element size the precision stores (SURVEY 8(d): 313,356 B per LR pixel in fp32, half in fp16); rank 0'}}
+    if dumped:
+        out['dumped_outputs'] = dumped
+    return out
 
 
 if __name__ == '__main__':

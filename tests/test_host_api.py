@@ -1,9 +1,12 @@
 """CPU-only tests of the host side: the C-ABI library exports what include/esr_hip.h declares, the product refuses to run without a
 GPU (no CPU fallback), the reference-compatible module tree / state_dict / CEM construction / options / checkpoint loader behave
 like the reference (golden data from tests/golden), and the Z-optimisation loop logic."""
+import atexit
 import json
 import os
 import re
+import shutil
+import tempfile
 
 import numpy as np
 import pytest
@@ -14,6 +17,9 @@ from oracle.weights import seeded_uniform
 from oracle.gen_golden import aniso_gaussian_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the options' directories: private to this run (the model constructor loads the newest checkpoint it finds under path.models)
+RUN_DIR = tempfile.mkdtemp(prefix='esr_host_')
+atexit.register(shutil.rmtree, RUN_DIR, True)
 
 
 def test_cabi_library_exports_every_declared_symbol():
@@ -103,7 +109,7 @@ def _opt(nb=1, lat=0, cem=True, is_train=False):
     from options.options import dict_to_nonedict
     return dict_to_nonedict({
         'model': 'srragan', 'scale': 4, 'gpu_ids': None, 'range': [0, 1], 'is_train': is_train,
-        'path': {'models': '/tmp/esr_models', 'log': '/tmp/esr_log', 'pretrain_model_G': None},
+        'path': {'models': os.path.join(RUN_DIR, 'models'), 'log': os.path.join(RUN_DIR, 'log'), 'pretrain_model_G': None},
         'network_G': {'which_model_G': 'RRDB_net', 'CEM_arch': 1 if cem else 0, 'sigmoid_range_limit': 0, 'latent_input': 'all_layers' if lat else 'None',
                       'latent_input_domain': 'HR_downscaled', 'latent_channels': lat, 'norm_type': None, 'mode': 'CNA', 'nf': 64, 'nb': nb,
                       'in_nc': 3, 'out_nc': 3, 'gc': 32, 'scale': 4},

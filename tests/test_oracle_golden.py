@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import cem_oracle as co
+from oracle import pattern as PT
 from oracle import rrdb_oracle as ro
 from oracle.check_golden import load, rel_l2, rel_max
 from oracle.weights import formula_tensor, seeded_uniform
@@ -128,6 +129,15 @@ def f4_input(nb, sf, lat):
     return x
 
 
+def f4_reference_pattern(name):
+    """F14: whether each LeakyReLU output of F4's reference run was > 0, one 0/1 tensor per activation in call order."""
+    g = load('rrdb_fwd_bwd_pattern.npz')
+    shapes = [tuple(int(d) for d in s) for s in g[name + '/shapes']]
+    sizes = [int(np.prod(s)) for s in shapes]
+    bits = np.unpackbits(g[name + '/positive'], count=sum(sizes)).astype(np.float32)
+    return [torch.from_numpy(b.reshape(s)) for b, s in zip(np.split(bits, np.cumsum(sizes)[:-1]), shapes)]
+
+
 @pytest.mark.parametrize('name,nb,sf,lat', F4_CASES, ids=[c[0] for c in F4_CASES])
 def test_rrdb_fwd_bwd_matches_reference(name, nb, sf, lat):
     g = load('rrdb_fwd_bwd.npz')
@@ -137,7 +147,15 @@ def test_rrdb_fwd_bwd_matches_reference(name, nb, sf, lat):
     for v in sd.values():
         v.requires_grad_(True)
     x = f4_input(nb, sf, lat).requires_grad_(True)
-    y = ro.rrdb_forward(sd, x, nb, sf, lat)
+    # The gradient of this LeakyReLU network is a function of its activation pattern, and nb1_x8 / nb1_x4_lat3 hold pre-activations within
+    # rounding distance of zero: a CPU whose convolutions round differently from the one that ran the reference may put them on the other
+    # side, which moves dx by O(1e-3).  The reference's pattern is forced; where this run's pre-activations disagree with it they must lie
+    # at zero within rounding, and everything below is held to the plain bars.
+    stored = f4_reference_pattern(name)
+    with PT.forced_pattern(stored), PT.capture_preactivations() as pre:
+        y = ro.rrdb_forward(sd, x, nb, sf, lat)
+    flips, worst_pre = PT.pattern_flips(pre, stored)
+    assert worst_pre < 1e-5, (flips, worst_pre)
     assert rel_l2(y.detach().numpy(), g[name + '/out']) < 2e-6
     cot = seeded_uniform(tuple(y.shape), 41 + nb + sf + lat, -1.0, 1.0)
     (y * cot).sum().backward()

@@ -8,8 +8,11 @@ per-GPU shape and Z-search iterations at the C4 shape, both through the product'
 Under torchrun (one process per GPU) c3 all-reduces the gradients over RCCL and c4 shards the Z batch.
 """
 import argparse
+import atexit
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,12 +20,17 @@ sys.path.insert(0, os.path.join(ROOT, 'explorable-super-resolution_amd'))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
+# make_opt's directories: private to this process (the model constructor loads the newest checkpoint it finds under path.models, so a
+# fixed shared path would let files left by another run change what is measured)
+RUN_DIR = tempfile.mkdtemp(prefix='esr_bench_')
+atexit.register(shutil.rmtree, RUN_DIR, True)
+
 
 def make_opt(is_train, lat=3, nb=23, with_D=False):
     from options.options import dict_to_nonedict
     return dict_to_nonedict({
         'model': 'srragan', 'scale': 4, 'gpu_ids': [0], 'range': [0, 1], 'is_train': is_train,
-        'path': {'models': '/tmp/esr_models', 'log': '/tmp/esr_log', 'pretrain_model_G': None},
+        'path': {'models': os.path.join(RUN_DIR, 'models'), 'log': os.path.join(RUN_DIR, 'log'), 'pretrain_model_G': None},
         'network_G': {'which_model_G': 'RRDB_net', 'CEM_arch': 1, 'sigmoid_range_limit': 0, 'latent_input': 'all_layers',
                       'latent_input_domain': 'HR_downscaled', 'latent_channels': lat, 'norm_type': None, 'mode': 'CNA', 'nf': 64, 'nb': nb,
                       'in_nc': 3, 'out_nc': 3, 'gc': 32, 'scale': 4},

@@ -4,6 +4,7 @@
     weights frozen)  ->  clamp(0,1)  ->  objective  ->  loss.mean().backward()  (data-gradient kernels only)  ->  Adam step,
 keeping the iterate with the smallest loss.  The forward/backward are the HIP kernels; the objectives below are element-wise /
 reduction torch ops on the SR output.  Implemented objectives: 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1',
+'VGG' / 'max_VGG' (L1 between the VGG features of the output and of the desired image, the extractor on the library's kernels),
 whole-image or restricted to a user-marked region (image_mask: where the objective looks; Z_mask: which latent entries may move — the
 GUI's region tools, GUI.py:1925-2057).  The GUI's scribble / histogram / periodicity / dictionary / adversarial / 'local_*' patch objectives are
 not part of this build and raise NotImplementedError.
@@ -121,12 +122,12 @@ class Optimizable_Z(torch.nn.Module):
 
 class Z_optimizer():
     MIN_LR = 1e-5
-    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist']
+    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG']
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, **unsupported):
-        if objective not in self.SUPPORTED or ((image_mask is not None or Z_mask is not None) and 'l1' in objective):
-            raise NotImplementedError("Z objective '%s': implemented are %s (optionally with image_mask / Z_mask, except 'l1'); the GUI's other "
+        if objective not in self.SUPPORTED or ((image_mask is not None or Z_mask is not None) and ('l1' in objective or 'VGG' in objective)):
+            raise NotImplementedError("Z objective '%s': implemented are %s (optionally with image_mask / Z_mask, except 'l1' and the VGG ones); the GUI's other "
                                       "editing objectives are not part of this build" % (objective, self.SUPPORTED))
         assert (image_mask is None) == (Z_mask is None), 'Should either supply both masks or niether'        # (reference :384)
         self.objective, self.model, self.data, self.loggers = objective, model, data, loggers
@@ -166,6 +167,10 @@ class Z_optimizer():
                 self.desired_STD = self.desired_STD + (inc if 'increase' in objective else -inc)
         if 'l1' in objective and data is not None and 'desired' in data:
             self.desired_im = data['desired'].to(self.device)
+        if 'VGG' in objective:           # reference :505-507: L1 between the VGG features of the output and of the desired image
+            self.loss = torch.nn.L1Loss().to(self.device)
+            if data is not None and 'desired' in data:
+                self._set_desired_VGG(data['desired'])
         if objective == 'hist':          # reference :536-541: 256 bins on [0, 1], temperature 5e-4
             self.loss = SoftHistogramLoss(bins=256, min=0, max=1, desired_hist_image=[d.to(self.device) for d in data['desired']] if data is not None else None,
                                           desired_hist_image_mask=data.get('Desired_Im_Mask') if data is not None else None, input_im_HR_mask=self.image_mask,
@@ -186,11 +191,18 @@ class Z_optimizer():
         out = self.model.Output_Batch(within_0_1=True)
         return torch.std(out if self.image_mask is None else out * self.image_mask, dim=(1, 2, 3)).view(1, -1)
 
+    def _set_desired_VGG(self, desired):
+        self.desired_im = desired.to(self.device)
+        with torch.no_grad():
+            self.GT_HR_VGG = self.model.netF(self.desired_im).detach()
+
     def feed_data(self, data):
         self.data = data
         self.cur_iter = 0
         if 'l1' in self.objective:
             self.desired_im = data['desired'].to(self.device)
+        if 'VGG' in self.objective:
+            self._set_desired_VGG(data['desired'])
 
     def Manage_Model_Grad_Requirements(self, verify_disabled):
         if verify_disabled:
@@ -245,6 +257,8 @@ class Z_optimizer():
                 Z_loss = self.loss(self.output_image).reshape(1)
             elif 'l1' in self.objective:
                 Z_loss = (self.output_image - self.desired_im).abs().mean(dim=(1, 2, 3))
+            elif 'VGG' in self.objective:
+                Z_loss = self.loss(self.model.netF(self.output_image), self.GT_HR_VGG).reshape(1)
             elif 'TV' in self.objective:
                 Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean(0) + \
                     (TV_Loss(self.model.fake_H, self.image_mask, clamp01=True) if not self.model_training else

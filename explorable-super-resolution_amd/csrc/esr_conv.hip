@@ -517,7 +517,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
                 for (int k = 0; k < 2; ++k)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        // alpha * LeakyReLU(y) = max(alpha * y, alpha * slope * y) for alpha >= 0, 0 < slope <= 1 (checked by the host); the bias is
+                        // alpha * LeakyReLU(y) = max(alpha * y, alpha * slope * y) for alpha >= 0, 0 <= slope <= 1 (checked by the host); the bias is
                         // the accumulators' seed.  (Scaling first makes both operands of the max products: no canonicalising v_max x, x.)
                         v[k][j] = f32x2{acc[m][r][(gp * 2 + k) * 4 + 2 * j], acc[m][r][(gp * 2 + k) * 4 + 2 * j + 1]} * alpha2;
                         v[k][j] = __builtin_elementwise_max(v[k][j], v[k][j] * slope2);
@@ -542,7 +542,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
                 }
                 if constexpr (HAS_MK) {
                     // LeakyReLU' from the stored post-activation value: its sign is the pre-activation's (slope > 0);
-                    // x <= 0 -> slope (torch: leaky_relu'(0) = slope).  16-bit elements, two per dword: the low one is positive iff
+                    // x <= 0 -> slope (torch: leaky_relu'(0) = slope; slope 0: ReLU', which passes the gradient where the stored output is > 0).  16-bit elements, two per dword: the low one is positive iff
                     // (int)(d << 16) > 0, the high one iff (int)d > 0xFFFF (sign clear, magnitude bits not all zero) — bf16 and f16 alike
                     uint32_t d[2][2];
                     swap_halves(qm[rq][m * 2 + gp], d);
@@ -1169,7 +1169,8 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     // a missing lo OUTPUT plane with hi+lo inputs is the single-plane-intermediate case (fp16 formats only, checked below)
     if (d->out.hi && d->out.lo && !split) return ESR_E_ARG;
     if (d->out2.hi && (!d->out.hi || (d->out2.lo && !d->out.lo))) return ESR_E_ARG;      // out2 may drop the lo plane, not add one
-    if (d->act_slope <= 0.f || d->act_slope > 1.f || !(d->alpha >= 0.f)) return ESR_E_ARG;      // (the epilogue evaluates alpha * LeakyReLU as a max of two products)
+    // (the epilogue evaluates alpha * LeakyReLU as a max of two products; act_slope 0 is ReLU: max(alpha*y, 0))
+    if (d->act_slope < 0.f || d->act_slope > 1.f || !(d->alpha >= 0.f)) return ESR_E_ARG;
 
     ConvArgs a{};
     a.in0 = to_dview(d->in0);

@@ -213,6 +213,10 @@ _SIGS = {
     'esr_cem_filter_upscale_sep': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'esr_cem_sep_form': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'esr_pack_nchw_norm': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ActView), C.c_void_p]),
+    'esr_unpack_grad_nchw_norm': (C.c_int, [C.POINTER(ActView), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'esr_maxpool2x2': (C.c_int, [C.POINTER(ActView), C.POINTER(ActView), C.c_int, C.c_void_p]),
+    'esr_maxpool2x2_grad': (C.c_int, [C.POINTER(ActView), C.POINTER(ActView), C.c_int, C.POINTER(ActView), C.c_int, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

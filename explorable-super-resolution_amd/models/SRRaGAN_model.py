@@ -10,8 +10,10 @@ packing.  What is reproduced:
     run (one process per GPU) instead of nn.DataParallel
   * perform_validation / save_log / save / load (G, D, optimizers, logs.npz) through BaseModel (positional checkpoint loading)
   * FilterLoss for train.latent_weight (structure-tensor statistics on the library's kernels, esr_hip/zobj.py)
-Not reproduced, and refused loudly: the VGG-feature loss (define_F needs torchvision), the LR-rollback heuristics (:592-632), D_update_ratio
-given as a controller range.
+  * the VGG-feature loss (train.feature_weight, :125-139, :442-451) with define_F's extractor on the library's kernels (esr_hip/vgg.py), and
+    init_Fnet for the Z search's VGG objectives (:200-203)
+Not reproduced, and refused loudly: the feature loss in the LR domain (train.feature_domain = 'LR'), the LR-rollback heuristics (:592-632),
+D_update_ratio given as a controller range.
 """
 import os
 from collections import OrderedDict
@@ -72,8 +74,6 @@ class SRRaGANModel(BaseModel):
         self.D_engine, self.D_engine_mode, self.D_engine_fallback = None, None, None
         self.timing = None               # set to {} to accumulate per-phase GPU milliseconds of optimize_parameters (bench.py --workload c3)
         if self.is_train:
-            if train_opt['feature_weight'] is not None:
-                raise NotImplementedError('The VGG-feature loss needs define_F (torchvision), which is outside this build; set train.feature_weight to null')
             if self.latent_input is not None and train_opt['latent_weight'] is not None:
                 # L_struct: the structure tensor of G's output against the value the latent code asks for (reference :35-40)
                 self.l_latent_w = train_opt['latent_weight']
@@ -154,6 +154,19 @@ class SRRaGANModel(BaseModel):
                                                batch_size=opt['datasets']['train']['batch_size'], HR_unpadder=self.CEM_net.HR_unpadder)
                 self.cri_optimalZ = (nn.MSELoss() if self.optimalZ_loss_type == 'l2' else nn.L1Loss()).to(self.device)
             self.cri_fea = None
+            if train_opt['feature_weight'] is not None:
+                # the VGG-feature loss (reference :125-139): the criterion between the extractor's features of the output and of the HR image
+                l_fea_type = train_opt['feature_criterion']
+                if l_fea_type == 'l1':
+                    self.cri_fea = nn.L1Loss().to(self.device)
+                elif l_fea_type == 'l2':
+                    self.cri_fea = nn.MSELoss().to(self.device)
+                else:
+                    raise NotImplementedError('Loss type [{:s}] not recognized.'.format(l_fea_type))
+                if train_opt.get('feature_domain') == 'LR':
+                    raise NotImplementedError("train.feature_domain = 'LR'")
+                self.l_fea_w = train_opt['feature_weight']
+                self.netF = self._define_F(opt)
             self.cri_range = None
             if train_opt['range_weight'] is not None:
                 self.cri_range = CreateRangeLoss(opt['range'])
@@ -201,8 +214,8 @@ class SRRaGANModel(BaseModel):
         elif init_Dnet:
             self.netD = networks.define_D(opt, CEM=self.CEM_net).to(self.device)
             self.netD.eval()
-        if init_Fnet:
-            raise NotImplementedError('init_Fnet: the VGG feature extractor needs torchvision')
+        if init_Fnet and not self.is_train:
+            self.netF = self._define_F(opt)          # the Z search's 'VGG' / 'max_VGG' objectives (reference :200-203)
         self.load()
         if self.is_train:
             # what the reference does after loading (:209-218): once the critic counts as verified, G trains at D's learning rate and the
@@ -227,6 +240,13 @@ class SRRaGANModel(BaseModel):
             gc.freeze()
             self._gc_frozen = True          # close() undoes it
         print('---------- Model initialized ------------------')
+
+    def _define_F(self, opt):
+        """The frozen VGG feature extractor, in eval mode; its kernels run 'bf16' operands when the critic's do (network_D.precision = 'bf16',
+        the reduced-precision switch of configs[2]), otherwise 'split' (fp32-class)."""
+        netF = networks.define_F(opt, use_bn=False).to(self.device).eval()
+        netF.set_precision('bf16' if (opt['network_D'] or {}).get('precision') == 'bf16' else 'split')
+        return netF
 
     # ------------------------------------------------------------------ input packing (reference :224-278)
     def Output_Batch(self, within_0_1):
@@ -525,7 +545,7 @@ class SRRaGANModel(BaseModel):
                 self.Set_Require_Grad_Status(self.netG, True)
                 if first_acc_G and first_dual:
                     self.optimizer_G.zero_grad()
-                    self._g_acc = {k: [] for k in ['l_g_pix', 'l_g_range', 'l_g_gan', 'l_g_optimalZ'] + ['l_g_latent_%d' % i for i in range(self.num_latent_channels)]}
+                    self._g_acc = {k: [] for k in ['l_g_pix', 'l_g_fea', 'l_g_range', 'l_g_gan', 'l_g_optimalZ'] + ['l_g_latent_%d' % i for i in range(self.num_latent_channels)]}
                 scale = acc_G * dual_steps
                 l_g_total = 0
                 if self.cri_pix is not None:
@@ -534,6 +554,14 @@ class SRRaGANModel(BaseModel):
                     l_g_pix = self.cri_pix(self.fake_H, self.var_H)
                     l_g_total = l_g_total + self.l_pix_w * l_g_pix / scale
                     self._g_acc['l_g_pix'].append(l_g_pix.detach())
+                if self.cri_fea is not None:
+                    # feature loss (reference :442-451): the HR image's features carry no graph (no activations kept for them)
+                    with torch.no_grad():
+                        real_fea = self.netF(self.var_H)
+                    fake_fea = self.netF((self.fake_H[0] + self.fake_H[1]) if self.decomposed_output else self.fake_H)
+                    l_g_fea = self.cri_fea(fake_fea, real_fea)
+                    l_g_total = l_g_total + self.l_fea_w * l_g_fea / scale
+                    self._g_acc['l_g_fea'].append(l_g_fea.detach())
                 if self.cri_range is not None:
                     l_g_range = self.cri_range(self.fake_H)
                     l_g_total = l_g_total + self.l_range_w * l_g_range / scale

@@ -2,10 +2,14 @@
 same constructor, attributes, module tree and state_dict keys, executed by the gfx950 engine (esr_hip/engine.py).
 
 Discriminator_VGG_128 (architecture.py:446-508), the other half of the configs[2] training step, is a stock-PyTorch module (MIOpen
-convolutions, BatchNorm, Linear): the WGAN-GP penalty differentiates it twice, which autograd does for stock ops.  The other
-discriminators / feature extractors of the reference's architecture.py are outside this build.
+convolutions, BatchNorm, Linear): the WGAN-GP penalty differentiates it twice, which autograd does for stock ops.
+
+VGGFeatureExtractor (architecture.py:658-705), the perceptual loss's network, is a stock module tree (torchvision's `features` layout and
+state_dict keys) whose GPU forward and input gradient run on the library's kernels (esr_hip/vgg.py).  The other discriminators / feature
+extractors of the reference's architecture.py are outside this build.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -13,6 +17,7 @@ import torch.nn as nn
 
 from . import block as B
 from esr_hip.engine import RRDBEngine
+from esr_hip import vgg as esr_vgg
 
 
 class RRDBNet(nn.Module):
@@ -164,3 +169,102 @@ class Discriminator_VGG_128(nn.Module):
         if self.last_FC_layers:
             x = x.reshape(x.size(0), -1)          # (NCHW order also when the features ran channels_last)
         return self.classifier(x)
+
+
+# torchvision's file names of the ImageNet weights (torch.hub cache, <hub dir>/checkpoints/)
+VGG_HUB_FILES = {'vgg11': 'vgg11-8a719046.pth', 'vgg13': 'vgg13-19584684.pth', 'vgg16': 'vgg16-397923af.pth', 'vgg19': 'vgg19-dcbb9e9d.pth'}
+
+
+def vgg_weight_sources(arch, pretrained_path=None):
+    """The places VGGFeatureExtractor takes its weights from, in order, when no state_dict is passed: the options' pretrained_model_F, then
+    torchvision's file in the torch hub cache.  Nothing is ever downloaded."""
+    import torch.hub
+    return [p for p in (pretrained_path, os.path.join(torch.hub.get_dir(), 'checkpoints', VGG_HUB_FILES.get(arch, arch + '.pth'))) if p]
+
+
+class VGGFeatureExtractor(nn.Module):
+    """Perceptual-loss network (reference architecture.py:658-705): torchvision's VGG `features` cut after index `feature_layer` (34: conv5_4
+    of VGG19, before its ReLU), frozen, behind the ImageNet input normalisation.  `features` is a stock Sequential of Conv2d / ReLU /
+    MaxPool2d and `mean` / `std` are buffers, so state_dict keys are the reference's (features.<i>.weight / bias, mean, std).
+
+    Weights (torchvision is not part of this build, and nothing is downloaded), first found wins: the `state_dict` keyword (the reference's own;
+    a torchvision VGG state_dict or this module's, 'module.' prefixes dropped), `pretrained_path` (define_F passes the options'
+    path.pretrained_model_F: a torchvision-format .pth), torchvision's vgg*.pth in the torch hub cache.
+
+    On the GPU the forward and its input gradient run on the library's kernels (esr_hip/vgg.py; set_precision picks 'split' — fp32-class, the
+    default — or 'bf16'); CPU tensors run the stock modules, as Discriminator_VGG_128 does."""
+
+    def __init__(self, feature_layer=34, use_bn=False, use_input_norm=True, device=torch.device('cpu'), state_dict=None, arch='vgg19',
+                 arch_config='', pretrained_path=None, **kwargs):
+        super(VGGFeatureExtractor, self).__init__()
+        if arch == 'SegNetAE':
+            raise NotImplementedError('VGGFeatureExtractor(arch=SegNetAE): the SegNet auto-encoder is not part of this build')
+        if use_bn:
+            raise NotImplementedError('VGGFeatureExtractor(use_bn=True): the batch-norm VGG variants are not part of this build')
+        if arch_config != '':
+            raise NotImplementedError('VGGFeatureExtractor(arch_config=%r): the RandomPooling model modifications are not part of this build' % (arch_config,))
+        table = esr_vgg.layer_table(arch, feature_layer)
+        layers = []
+        for entry in table:
+            if entry[0] == 'conv':
+                layers.append(nn.Conv2d(entry[1], entry[2], kernel_size=3, padding=1))
+            elif entry[0] == 'relu':
+                layers.append(nn.ReLU(inplace=True))
+            else:
+                layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
+        self.features = nn.Sequential(*layers)
+        self.arch = arch
+        self._load_weights(state_dict, pretrained_path)
+        self.use_input_norm = use_input_norm
+        if self.use_input_norm:
+            self.register_buffer('mean', torch.Tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
+            self.register_buffer('std', torch.Tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
+        for v in self.features.parameters():
+            v.requires_grad = False
+        self.to(device)
+        self._engine = None
+        self._precision = 'split'
+
+    def _load_weights(self, state_dict, pretrained_path):
+        if state_dict is None:
+            sources = vgg_weight_sources(self.arch, pretrained_path)
+            found = [p for p in sources if os.path.isfile(p)]
+            if not found:
+                raise FileNotFoundError('VGGFeatureExtractor(%s): no weights. Looked for (1) the state_dict= keyword, (2) the options\' '
+                                        'path.pretrained_model_F (%s), (3) the torch hub cache file %s. Nothing is downloaded: put torchvision\'s '
+                                        '%s there or pass one of the others.' % (self.arch, pretrained_path or 'not set', sources[-1],
+                                                                                 VGG_HUB_FILES.get(self.arch, self.arch + '.pth')))
+            state_dict = torch.load(found[0], map_location='cpu')
+        state_dict = {k.replace('module.', ''): v for k, v in state_dict.items()}
+        own = self.features.state_dict()
+        missing = ['features.' + k for k in own if 'features.' + k not in state_dict]
+        if missing:
+            raise KeyError('VGGFeatureExtractor(%s): the weights lack %s' % (self.arch, ', '.join(missing)))
+        with torch.no_grad():
+            for k, v in own.items():
+                src = state_dict['features.' + k]
+                if tuple(src.shape) != tuple(v.shape):
+                    raise ValueError('VGGFeatureExtractor: features.%s has shape %s, expected %s' % (k, tuple(src.shape), tuple(v.shape)))
+                v.copy_(src)
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = esr_vgg.VGGEngine(self.features, precision=self._precision)
+        return self._engine
+
+    def set_precision(self, precision):
+        """'split' (default): bf16 hi+lo operands, fp32-class features and gradients; 'bf16': one plane, one MFMA per product."""
+        assert precision in ('split', 'bf16')
+        self._precision = precision
+        if self._engine is not None:
+            self._engine.set_precision(precision)
+
+    def forward(self, x):
+        if x.is_cuda:
+            eng = self.engine
+            eng.mean, eng.std = (self.mean, self.std) if self.use_input_norm else (None, None)
+            return esr_vgg.vgg_forward(eng, x)
+        if self.use_input_norm:
+            x = (x - self.mean) / self.std
+        return self.features(x)

@@ -4,8 +4,9 @@ Differences that follow from the MI355X design (one process per GPU, RCCL data p
   * define_G never wraps the generator in nn.DataParallel; callers that reach through `.module` (GUI.py:1687) still work
     because the CEM wrapper and RRDBNet expose `.module` as themselves.
   * define_D builds the reference's default critic (Discriminator_VGG_128) from stock PyTorch modules (MIOpen kernels): it is the other
-    half of the configs[2] training step, not part of the RRDB+CEM kernel path.  The VGG feature extractor (define_F) needs
-    torchvision and stays out.
+    half of the configs[2] training step, not part of the RRDB+CEM kernel path.
+  * define_F builds the VGG feature extractor without torchvision: the module tree is built here and the weights come from a file
+    (architecture.VGGFeatureExtractor), never from the network.
 """
 import functools
 
@@ -116,4 +117,15 @@ def define_D(opt, CEM=None, **kwargs):
 
 
 def define_F(opt, use_bn=False, **kwargs):
-    raise NotImplementedError('define_F: the VGG feature extractor needs torchvision and is outside the RRDB+CEM hot path')
+    """VGG feature extractor (reference networks.py:185-197): VGG19 features up to conv5_4 before its ReLU (feature_layer 34), or
+    arch='vgg<N>_<layer>' for another cut; weights from the options' path.pretrained_model_F or the torch hub cache (see
+    VGGFeatureExtractor).  Returned in eval() mode; no nn.DataParallel (one process per GPU; the weights are frozen, so nothing is exchanged)."""
+    from esr_hip.vgg import parse_arch
+    gpu_ids = opt['gpu_ids']
+    device = torch.device('cuda' if gpu_ids else 'cpu')
+    feature_layer = 49 if use_bn else 34
+    if 'arch' in kwargs:
+        kwargs['arch'], feature_layer = parse_arch(kwargs['arch'], use_bn)
+    path = (opt.get('path') or {}).get('pretrained_model_F') if hasattr(opt, 'get') else None
+    netF = arch.VGGFeatureExtractor(feature_layer=feature_layer, use_bn=use_bn, use_input_norm=True, device=device, pretrained_path=path, **kwargs)
+    return netF.eval()

@@ -72,8 +72,8 @@ typedef struct {
  *
  *   out = alpha * act(conv(in0 ++ in1) + bias) + beta1*res1 + beta2*res2
  *
- * Limits checked by the entry point (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise): 0 < act_slope <= 1 and alpha >= 0 (the epilogue evaluates
- * alpha * LeakyReLU(y) as max(alpha*y, alpha*act_slope*y)); H + 2 and W + 2 below 32768, upsample <= 8; every view's image (ncg * cg_stride * 16
+ * Limits checked by the entry point (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise): 0 <= act_slope <= 1 and alpha >= 0 (the epilogue evaluates
+ * alpha * LeakyReLU(y) as max(alpha*y, alpha*act_slope*y); act_slope = 0 is ReLU, torchvision VGG's nn.ReLU(inplace=True)); H + 2 and W + 2 below 32768, upsample <= 8; every view's image (ncg * cg_stride * 16
  * bytes) and the fp32 destination's image below 4 GiB (per-lane addresses are a uniform per-image base + a 32-bit offset); res1 / res2 cover
  * every output group (ncg * 8 >= cout); mask_src covers the masked groups.
  *
@@ -91,7 +91,7 @@ typedef struct {
                               * holds one 64-row pack per slice, slice s at byte offset s * esr_conv_wpack_bytes(in0.ncg + in1.ncg, 64, fmt)
                               * (no out_nchw / pixel_shuffle with slices) */
     int32_t B, H, W;         /* output interior size (= input size * upsample) */
-    float act_slope;         /* 1.0f: identity; 0.2f: LeakyReLU(0.2) */
+    float act_slope;         /* 1.0f: identity; 0.2f: LeakyReLU(0.2); 0.0f: ReLU */
     float alpha;
     esr_act_view res1; float beta1;   /* optional (hi == NULL: absent); same H, W as the output */
     esr_act_view res2; float beta2;
@@ -100,7 +100,8 @@ typedef struct {
     float* out_nchw;         /* optional fp32 [B][cout][H][W] destination */
     /* data-gradient helper: multiply the result for output groups [mask_cg0, mask_cg1) by
      * act'(mask_src) = (mask_src > 0 ? 1 : mask_slope) AFTER the residual add (LeakyReLU backward of
-     * the layer that produced those channels; block.py:18). mask_src.hi == NULL: disabled. */
+     * the layer that produced those channels; block.py:18; mask_slope = 0: ReLU backward, the gradient passes where the stored output
+     * is > 0, as torch's in-place ReLU). mask_src.hi == NULL: disabled. */
     esr_act_view mask_src; int32_t mask_cg0, mask_cg1; float mask_slope;
     /* scheduling hint, no effect on the result: walk the tiles (and so the images) last to first.  Consecutive layers of a network
      * re-read what the previous launch just touched; alternating the direction lets the tail of one launch, still in the 256 MB
@@ -202,6 +203,24 @@ int esr_pack_nchw(const float* src, int64_t src_batch_stride, int B, int C, int 
 int esr_unpack_nchw(const esr_act_view* src, int B, int nc, float* dst, esr_stream_t stream);
 /* zero `n16` 16-byte vectors (border initialisation of freshly allocated activation buffers) */
 int esr_zero(void* p, int64_t n16, esr_stream_t stream);
+
+/* ---- VGG feature extractor glue (the perceptual loss's network: codes/models/modules/architecture.py:658-705, VGGFeatureExtractor on
+ * torchvision's VGG `features` = Conv2d(3x3, pad 1) / ReLU(inplace) / MaxPool2d(2, 2) layers; the convs and their ReLU are esr_conv3x3
+ * launches with act_slope = 0, their data gradients esr_conv3x3 on transposed packs with mask_slope = 0).
+ * esr_pack_nchw_norm: fp32 NCHW [B][C][h][w] -> act view (h x w, zero border) of (x - mean[c]) / std[c] — VGGFeatureExtractor.forward's
+ *   input normalisation (architecture.py:705-709) applied BEFORE conv1_1's zero padding, so the border stays 0.  mean / std: device fp32 [C],
+ *   both NULL = no normalisation (use_input_norm = False).
+ * esr_unpack_grad_nchw_norm: its adjoint — act-layout gradient (hi + lo) -> fp32 NCHW [B][C][G->H][G->W], divided by std[c] (NULL: copied).
+ * esr_maxpool2x2: nn.MaxPool2d(kernel_size=2, stride=2) — y->H = floor(x->H / 2), y->W = floor(x->W / 2) (F.max_pool2d floors); the window
+ *   value is hi + lo; the output is the element at torch's argmax (the first maximum in row-major window order; a NaN propagates), copied
+ *   bit for bit, and y's one-pixel zero border is written (y is the next conv's input).  Same format and planes in x and y.
+ * esr_maxpool2x2_grad: its backward — dx (x's size, zero border written, as are the uncovered last row / column of odd sizes) receives dy
+ *   at the argmax of every window, recomputed from the saved pre-pool x, and zero elsewhere; relu_mask != 0 also zeroes it where x <= 0
+ *   (x is a ReLU's output: the ReLU's backward, fused).  dy and dx share format and planes; x may have either. */
+int esr_pack_nchw_norm(const float* src, int B, int C, int h, int w, const float* mean, const float* std, const esr_act_view* dst, esr_stream_t stream);
+int esr_unpack_grad_nchw_norm(const esr_act_view* G, int B, int C, const float* std, float* dst, esr_stream_t stream);
+int esr_maxpool2x2(const esr_act_view* x, const esr_act_view* y, int B, esr_stream_t stream);
+int esr_maxpool2x2_grad(const esr_act_view* x, const esr_act_view* dy, int relu_mask, const esr_act_view* dx, int B, esr_stream_t stream);
 
 /* ---- Consistency Enforcing Module filters (fixed depth-wise taps, fp32, NCHW) ----
  * codes/CEM/CEMnet.py:243-252 (Filter_Layer) x3 as built in CEM_PyTorch.__init__ (:254-281).

@@ -5,14 +5,18 @@
 keeping the iterate with the smallest loss.  The forward/backward are the HIP kernels; the objectives below are element-wise /
 reduction torch ops on the SR output.  Implemented objectives: 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1',
 'VGG' / 'max_VGG' (L1 between the VGG features of the output and of the desired image, the extractor on the library's kernels),
+'hist' (gray-level histogram), and the patch-histogram / dictionary objectives of the GUI's "Imitate histogram" and "Imitate patch histogram"
+tools: 'patchhist', 'patchhist_noDC', 'dict', 'dict_noDC', 'patchdict', 'patchdict_noDC' (SoftHistogramLoss on the pairwise KDE kernels),
 whole-image or restricted to a user-marked region (image_mask: where the objective looks; Z_mask: which latent entries may move — the
-GUI's region tools, GUI.py:1925-2057).  The GUI's scribble / histogram / periodicity / dictionary / adversarial / 'local_*' patch objectives are
-not part of this build and raise NotImplementedError.
+GUI's region tools, GUI.py:1925-2057).  The GUI's scribble / periodicity / adversarial / 'local_*' patch objectives, the '*_localSTD' histogram
+variants and the automatic histogram temperature are not part of this build and raise NotImplementedError.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective).  Like the reference, the loss is the
 mean over the WHOLE batch, so each shard scales its local sum by 1/B_global; the loss history that picks the best iterate is
 all-reduced (one scalar per iteration).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -38,26 +42,62 @@ def TV_Loss(image, mask=None, clamp01=False):
 
 
 class SoftHistogramLoss(torch.nn.Module):
-    """KL divergence between the soft gray-level histogram of the produced image(s) and that of a desired image — the 'hist' Z objective
-    (reference Z_optimization.py:24-230), in the form the whole-image tool uses: gray scale, patch size 1, fixed temperature.
+    """The histogram / dictionary Z objectives (reference Z_optimization.py:24-230), gray scale, fixed temperature.
+    patch_size 1, histogram ('hist'): the soft gray-level histogram
         h[k] = mean_i exp(-(d(v_i, c_k) + 1e-7)^2 / T) over the (masked) pixels, c = linspace(min, max, bins), d wrapped with period max;
         p = h / sum(h);   loss = KLDivLoss()(log(p_current + eps) stacked over the batch, p_desired)      (:170-209, :211-229)
-    The O(pixels x bins) histogram and its gradient are the HIP kernels of csrc/esr_zobj.hip (the reference materialises that matrix in
-    float64).  Patch (KDE) histograms, dictionaries and the automatic temperature search are not part of this build."""
+    on the soft-histogram kernels of csrc/esr_zobj.hip.
+    patch_size > 1 and/or dictionary_not_histogram: the pairwise KDE of csrc/esr_kde.hip (esr_hip.kde) between the image's points x_i — its
+    patch_size x patch_size gray patches (ReturnPatchExtractionMat of the image mask, overlap 0.5; DC removed with no_patch_DC) or, for patch
+    size 1, its (masked) gray pixels — and the bins b_j, k_ij = exp(-s_ij / T), s_ij = mean_d (w(x_id - b_jd) + 1e-7)^2:
+      * bins: the desired images' patches (overlap (D - patch_size) / D, masks desired_hist_image_mask, DC removed as above), de-duplicated
+        (Desired_Im_2_Bins; its retry in sub-images on memory failure is not reproduced); for patch size 1 (dictionary) the bin centres, and
+        the desired image is not used (:146-150, the reference's KDE flag is off there).
+      * dictionary: per image the mean over its points of -log mean_j k_ij  -> [B]   (the canonical-KDE branch, :196-201).
+      * KDE histogram: h_j = sum_i k_ij / N / normaliser / N in float64, cast to float, with an extra bin 1 - min(1, sum h) for the missing mass;
+        the normaliser is the DESIRED histogram's (sum_j h_desired_j / N_desired), as the reference keeps it; loss = KLDivLoss() (mean) of
+        log(h + eps_f32) against the desired histogram.
+    Sums of k run in the log domain on the GPU: where the reference's float64 exp underflows for every bin of a patch (s/T > ~745) it returns
+    inf and this class a finite value — the one intended divergence.  Not part of this build (NotImplementedError): automatic_temperature,
+    no_patch_STD, colour (gray_scale=False)."""
 
     def __init__(self, bins, min, max, desired_hist_image_mask=None, desired_hist_image=None, gray_scale=True, input_im_HR_mask=None, patch_size=1,
                  automatic_temperature=False, image_Z=None, temperature=0.05, dictionary_not_histogram=False, no_patch_DC=False, no_patch_STD=False):
         super(SoftHistogramLoss, self).__init__()
-        if not gray_scale or patch_size != 1 or automatic_temperature or dictionary_not_histogram:
-            raise NotImplementedError('SoftHistogramLoss: gray-scale, patch_size 1, fixed temperature histograms only')
+        if automatic_temperature:
+            raise NotImplementedError('SoftHistogramLoss: automatic_temperature (a temperature search through a double backward of the generator) '
+                                      'is not part of this build')
+        if no_patch_STD:
+            raise NotImplementedError('SoftHistogramLoss: no_patch_STD (per-patch STD normalisation) is not part of this build')
+        if not gray_scale:
+            raise NotImplementedError('SoftHistogramLoss: colour histograms (gray_scale=False) are not part of this build')
         self.bins_n, self.min, self.max, self.temperature = int(bins), float(min), float(max), float(temperature)
         self.SQRT_EPSILON = 1e-7
-        self.image_mask = None if input_im_HR_mask is None else input_im_HR_mask.reshape(-1).bool()
+        self.patch_size = int(patch_size)
+        self.num_dims = self.patch_size ** 2
+        self.dictionary_not_histogram = bool(dictionary_not_histogram)
+        self.no_patch_DC = bool(no_patch_DC) and self.patch_size > 1
+        self.KDE = self.patch_size > 1
+        self.bin_width = (self.max - self.min) / (self.bins_n - 1)
         self.loss = torch.nn.KLDivLoss()
         self.desired_hists_list = []
-        if desired_hist_image is not None:
-            # (the reference ignores desired_hist_image_mask for non-patch gray histograms: it is applied in its KDE branch only, :74-76)
-            self.Feed_Desired_Hist_Im([im[0] if im.dim() == 4 else im for im in desired_hist_image][:1])
+        if not self.KDE and not self.dictionary_not_histogram:
+            self.image_mask = None if input_im_HR_mask is None else input_im_HR_mask.reshape(-1).bool()
+            if desired_hist_image is not None:
+                # (the reference ignores desired_hist_image_mask for non-patch gray histograms: it is applied in its KDE branch only, :74-76)
+                self.Feed_Desired_Hist_Im([im[0] if im.dim() == 4 else im for im in desired_hist_image][:1])
+            return
+        # the KDE / dictionary forms
+        self.image_mask = None if input_im_HR_mask is None else (input_im_HR_mask.detach().cpu().numpy() if torch.is_tensor(input_im_HR_mask)
+                                                                 else np.asarray(input_im_HR_mask))
+        self._patch_index = {}
+        self.bins = None
+        if not self.KDE:           # dictionary of gray levels: the bin centres, float32 values as the reference's linspace
+            self.bins = torch.linspace(self.min, self.max, self.bins_n).view(-1, 1)
+        elif desired_hist_image is None:
+            raise ValueError('SoftHistogramLoss: patch histograms and dictionaries need desired_hist_image')
+        else:
+            self.Feed_Desired_Hist_Im(desired_hist_image, desired_hist_image_mask)
 
     def _hist(self, gray_values, log):
         from esr_hip import zobj
@@ -65,20 +105,82 @@ class SoftHistogramLoss(torch.nn.Module):
         h = (h / h.sum()).float()
         return torch.log(h + torch.finfo(h.dtype).eps).view(1, -1) if log else h.view(1, -1)
 
-    def Feed_Desired_Hist_Im(self, desired_hist_image):
-        self.desired_hists_list = []
+    def _patch_indexes(self, mask, overlap, device):
+        """[P, D] flat pixel indexes of the selected patches (esr_hip.kde.patch_extraction_indexes), cached per mask"""
+        key = (mask.shape, mask.tobytes(), overlap, str(device))
+        if key not in self._patch_index:
+            from esr_hip import kde
+            self._patch_index[key] = torch.from_numpy(kde.patch_extraction_indexes(mask, self.patch_size, overlap)).to(device)
+        return self._patch_index[key]
+
+    def _points(self, gray, mask, overlap):
+        """gray [B, H, W] -> [B, N, D] float32 points: patches (DC removed as asked) or masked pixels"""
+        B, H, W = gray.shape
+        flat = gray.reshape(B, H * W)
+        if self.KDE:
+            m = np.ones((H, W), dtype=np.float32) if mask is None else mask
+            idx = self._patch_indexes(m, overlap, gray.device)
+            if idx.size(0) == 0:
+                raise ValueError('SoftHistogramLoss: the mask holds no %d x %d patch' % (self.patch_size, self.patch_size))
+            pts = flat[:, idx]
+            if self.no_patch_DC:
+                pts = pts - pts.mean(2, keepdim=True)
+            return pts
+        if mask is not None:
+            flat = flat[:, torch.from_numpy(np.asarray(mask).reshape(-1) != 0).to(gray.device)]
+        return flat.unsqueeze(-1)
+
+    def Feed_Desired_Hist_Im(self, desired_hist_image, desired_hist_image_mask=None):
+        """patch size 1 histogram: the desired histogram of the first image.  KDE histograms and patch dictionaries: the bins and (histogram)
+        the desired histogram and its normaliser, rebuilt from the desired images and their masks (the reference's method of this name is
+        broken for the KDE forms: it skips the patch extraction; Z_optimizer.feed_data calls it with a new 'desired')."""
+        if not self.KDE and not self.dictionary_not_histogram:
+            self.desired_hists_list = []
+            with torch.no_grad():
+                for im in desired_hist_image:
+                    self.desired_hists_list.append(self._hist(im.mean(0).reshape(-1), log=False).detach())
+            return
+        if not self.KDE:
+            return                 # gray-level dictionary: the bins are the centres
+        from esr_hip import kde
+        masks = list(desired_hist_image_mask) if desired_hist_image_mask is not None else [None] * len(desired_hist_image)
+        overlap = (self.num_dims - self.patch_size) / self.num_dims
         with torch.no_grad():
-            for im in desired_hist_image:
-                self.desired_hists_list.append(self._hist(im.mean(0).reshape(-1), log=False).detach())
+            pts = []
+            for im, m in zip(desired_hist_image, masks):
+                im = im[0] if im.dim() == 4 else im
+                m = None if m is None else (m.detach().cpu().numpy() if torch.is_tensor(m) else np.asarray(m))
+                pts.append(self._points(im.float().mean(0, keepdim=True), m, overlap)[0])
+            pts = torch.cat(pts, 0).contiguous()                                       # [N_desired, D]
+            self.bins = pts[kde.dedup_keep(pts, self.bin_width / 2)].contiguous()
+            if not self.dictionary_not_histogram:
+                n = pts.size(0)
+                hist = torch.exp(kde.column_lse(pts, (n,), self.bins, self.temperature, self.max)[0]) / n
+                self.normalizer = hist.sum() / n
+                hist = (hist / self.normalizer / n).float()
+                hist = torch.cat([hist, (1 - torch.minimum(torch.ones((), dtype=hist.dtype, device=hist.device), hist.sum())).view(1)])
+                self.desired_hists_list = [hist.view(1, -1)]
 
     def forward(self, cur_images):
-        logs = []
-        for im in cur_images:
-            gray = im.mean(0).reshape(-1)
-            if self.image_mask is not None:
-                gray = gray[self.image_mask.to(gray.device)]
-            logs.append(self._hist(gray, log=True))
-        return self.loss(torch.cat(logs, 0), torch.cat(self.desired_hists_list, 0).to(logs[0].device)).float()
+        if not self.KDE and not self.dictionary_not_histogram:
+            logs = []
+            for im in cur_images:
+                gray = im.mean(0).reshape(-1)
+                if self.image_mask is not None:
+                    gray = gray[self.image_mask.to(gray.device)]
+                logs.append(self._hist(gray, log=True))
+            return self.loss(torch.cat(logs, 0), torch.cat(self.desired_hists_list, 0).to(logs[0].device)).float()
+        from esr_hip import kde
+        pts = self._points(cur_images.mean(1), self.image_mask, 0.5)                  # [B, N, D]
+        B, N, D = pts.shape
+        bins = self.bins.to(pts.device)
+        if self.dictionary_not_histogram:
+            lse = kde.row_lse(pts.reshape(B * N, D), bins, self.temperature, self.max).view(B, N)
+            return (math.log(bins.size(0)) - lse).mean(1).float()                      # -log mean_j k_ij, mean over the image's points
+        hist = torch.exp(kde.column_lse(pts.reshape(B * N, D), (N,) * B, bins, self.temperature, self.max)) / N
+        hist = (hist / self.normalizer / N).float()
+        hist = torch.cat([hist, 1 - torch.minimum(torch.ones((), dtype=hist.dtype, device=hist.device), hist.sum(1, keepdim=True))], 1)
+        return self.loss(torch.log(hist + torch.finfo(hist.dtype).eps), torch.cat(self.desired_hists_list, 0).to(hist.device)).float()
 
 
 class Optimizable_Z(torch.nn.Module):
@@ -120,12 +222,34 @@ class Optimizable_Z(torch.nn.Module):
         self.Z.data = 1 * Z
 
 
+# the patch-histogram and dictionary objectives (reference :510-543; what the GUI's histogram tools send, GUI.py:1460-1461, :1931-1935)
+HIST_OBJECTIVES = ('patchhist', 'patchhist_noDC', 'dict', 'dict_noDC', 'patchdict', 'patchdict_noDC')
+
+
+def hist_objective_config(objective):
+    """SoftHistogramLoss settings of a histogram / dictionary objective (reference :536-543): 256 bins on [0, 1], patch size 6 when 'patch'
+    is in the name (else 1), temperature 5e-4 for histograms and 1e-3 for dictionaries, the patch DC removed for '_noDC'."""
+    if 'no_localSTD' in objective or 'localSTD' in objective:
+        raise NotImplementedError("Z objective '%s': the local-STD histogram variants (no_patch_STD and the STD-preserving term) are not part of "
+                                  "this build" % objective)
+    if objective not in HIST_OBJECTIVES + ('hist',):
+        raise ValueError("'%s' is not a histogram / dictionary objective" % objective)
+    return dict(bins=256, min=0, max=1, patch_size=6 if 'patch' in objective else 1, temperature=5e-4 if 'hist' in objective else 1e-3,
+                dictionary_not_histogram='dict' in objective, no_patch_DC='noDC' in objective)
+
+
 class Z_optimizer():
     MIN_LR = 1e-5
-    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG']
+    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES)
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
-                 initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, **unsupported):
+                 initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
+                 **unsupported):
+        if 'localSTD' in objective:
+            hist_objective_config(objective)            # raises, naming the variant
+        if objective in HIST_OBJECTIVES and auto_set_hist_temperature:
+            raise NotImplementedError("Z objective '%s': auto_set_hist_temperature (the temperature search differentiates through the generator "
+                                      "twice) is not part of this build" % objective)
         if objective not in self.SUPPORTED or ((image_mask is not None or Z_mask is not None) and ('l1' in objective or 'VGG' in objective)):
             raise NotImplementedError("Z objective '%s': implemented are %s (optionally with image_mask / Z_mask, except 'l1' and the VGG ones); the GUI's other "
                                       "editing objectives are not part of this build" % (objective, self.SUPPORTED))
@@ -175,6 +299,11 @@ class Z_optimizer():
             self.loss = SoftHistogramLoss(bins=256, min=0, max=1, desired_hist_image=[d.to(self.device) for d in data['desired']] if data is not None else None,
                                           desired_hist_image_mask=data.get('Desired_Im_Mask') if data is not None else None, input_im_HR_mask=self.image_mask,
                                           gray_scale=True, patch_size=1, temperature=5e-4)
+        if objective in HIST_OBJECTIVES:
+            # image_mask None: the patches cover the whole output (the reference's all-ones mask, :372-374); Desired_Im_Mask None: the whole
+            # desired image(s).  With the default temperatures and the missing-mass bin, as :536-543.
+            self.loss = SoftHistogramLoss(desired_hist_image=self._desired_list(data), desired_hist_image_mask=data.get('Desired_Im_Mask') if data else None,
+                                          input_im_HR_mask=self.image_mask, gray_scale=True, **hist_objective_config(objective))
         self.optimizer = torch.optim.Adam(self.Z_model.parameters(), lr=initial_LR) if existing_optimizer is None else existing_optimizer
         self.LR = initial_LR
         self.cur_iter = 0
@@ -196,9 +325,18 @@ class Z_optimizer():
         with torch.no_grad():
             self.GT_HR_VGG = self.model.netF(self.desired_im).detach()
 
+    def _desired_list(self, data):
+        if data is None or data.get('desired') is None:
+            return None
+        d = data['desired']
+        return [im.to(self.device) for im in (d if isinstance(d, (list, tuple)) else [d])]
+
     def feed_data(self, data):
         self.data = data
         self.cur_iter = 0
+        if self.objective in HIST_OBJECTIVES and data.get('desired') is not None:
+            # a new desired image rebuilds the bins and the desired histogram (the reference's Feed_Desired_Hist_Im is broken for the KDE forms)
+            self.loss.Feed_Desired_Hist_Im(self._desired_list(data), data.get('Desired_Im_Mask'))
         if 'l1' in self.objective:
             self.desired_im = data['desired'].to(self.device)
         if 'VGG' in self.objective:
@@ -253,8 +391,10 @@ class Z_optimizer():
             self.output_image = self.model.Output_Batch(within_0_1=True)
             if self.model_training:
                 self.output_image = self.HR_unpadder(self.output_image)
-            if self.objective == 'hist':
-                Z_loss = self.loss(self.output_image).reshape(1)
+            if self.objective == 'hist' or self.objective in HIST_OBJECTIVES:
+                # a dictionary gives one value per image; a histogram's KL is one mean over the local [B, bins + 1] (scaled below)
+                Z_loss = self.loss(self.output_image)
+                Z_loss = Z_loss.reshape(-1) if self.loss.dictionary_not_histogram else Z_loss.reshape(1)
             elif 'l1' in self.objective:
                 Z_loss = (self.output_image - self.desired_im).abs().mean(dim=(1, 2, 3))
             elif 'VGG' in self.objective:

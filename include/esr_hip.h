@@ -377,6 +377,22 @@ int64_t esr_soft_hist_slabs(int64_t n);
 int esr_soft_hist_fwd(const float* v, int64_t n, int K, float lo, float hi, float T, float eps, double* partial, esr_stream_t stream);
 int esr_soft_hist_bwd(const float* v, int64_t n, int K, float lo, float hi, float T, float eps, const float* gh, float* gv, esr_stream_t stream);
 
+/* ---- pairwise KDE between D-dimensional points (csrc/esr_kde.hip): the patch-histogram and dictionary Z objectives ----
+ * s_ij = (1/D) sum_d (w(x_id - b_jd) + 1e-7)^2 with w the distance wrapped with period `period`, k_ij = exp(-s_ij / T); `scale` = 1 / (D T).
+ * D is 1, 4, 9, 16, 25, 36, 49 or 64 (esr_kde_dim_supported).  Nothing of size N x M is stored.
+ * esr_kde_fwd: for every outer point o and inner range r (ranges[2r] .. ranges[2r+1], indices into `inner`):
+ *   psum[r * n_outer + o] * exp(pmax[r * n_outer + o]) = sum over the range of k_oi   (log-domain: a running max and a scaled double sum).
+ * esr_kde_bwd: dxpart[s][i][d] for tiles (b, row0, row1) of at most 256 rows of one image b and bin slab s = [s * bins_per_slab, ...):
+ *   sum_j g_row[i] g_bin[b][j] exp(-s_ij / T - l_row[i] - l_bin[b][j]) d(-s_ij / T)/dx_id;  g_row / l_row may be null (1 / 0), g_bin and l_bin
+ *   are both null (1 / 0) or both [B][M].  The caller sums the slabs.
+ * esr_kde_dedup: keep[i] = 0 iff some j > i has |b_id - b_jd| < half_width in every d (the reference's Desired_Im_2_Bins). */
+int esr_kde_dim_supported(int D);
+int esr_kde_fwd(const float* outer, int64_t n_outer, const float* inner, const int32_t* ranges, int n_ranges, int D, float period, float scale, float* pmax,
+                double* psum, esr_stream_t stream);
+int esr_kde_bwd(const float* X, int64_t R, const int32_t* tiles, int n_tiles, const float* bins, int M, int bins_per_slab, int n_slabs, int D, float period,
+                float scale, const float* g_row, const float* l_row, const float* g_bin, const float* l_bin, float* dxpart, esr_stream_t stream);
+int esr_kde_dedup(const float* bins, int M, int D, float half_width, int32_t* keep, esr_stream_t stream);
+
 /* ---- Adam over many tensors in one launch ----
  * The reference steps both networks with torch.optim.Adam (codes/models/SRRaGAN_model.py:147-160: lr, betas, weight decay from the options);
  * torch's multi-tensor implementation costs ~4 ms of host time per step for the generator's 702 tensors.  Same update rule, same fp32

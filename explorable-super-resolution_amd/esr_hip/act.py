@@ -221,6 +221,55 @@ class ActBuf:
 NO_VIEW = ActView(None, None, 0, 0, 0, 0, 0, 0)
 
 
+# activation tensors: the same layout as a torch tensor [planes][B][CG][H+2][W+2][8] bf16 (the critic and the VGG extractor)
+def new_at(planes, B, ncg, H, W, device):
+    """Uninitialised: for destinations whose producer writes the one-pixel zero border itself (pack_nchw, esr_bn_apply, the pools) or that are
+    only ever read at interior pixels (conv outputs, data gradients)."""
+    return torch.empty(planes, B, ncg, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
+
+
+def new_zeroed(planes, B, ncg, H, W, device):
+    """With its zero border (and zero interior): conv outputs that become conv inputs; the conv kernels never write borders."""
+    return torch.zeros(planes, B, ncg, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
+
+
+def view_of(t, cg0=0, ncg=None, b0=0):
+    """View of channel groups [cg0, cg0 + ncg) starting at image b0 (the view has no batch size: the launch says how many images)."""
+    if getattr(t, '_esr_stacked', False):              # [planes][CG][B][H+2][W+2][8]: see stacked_at()
+        P, CG, B, Hp, Wp, _ = t.shape
+        n = CG - cg0 if ncg is None else ncg
+        cs = B * Hp * Wp
+        hi = t.data_ptr() + (cg0 * cs + b0 * Hp * Wp) * 16
+        return ActView(hi, hi + t.stride(0) * 2 if P == 2 else None, n, Hp - 2, Wp - 2, Hp * Wp, cs, 0)
+    P, B, CG, Hp, Wp, _ = t.shape
+    n = CG - cg0 if ncg is None else ncg
+    cs = Hp * Wp
+    off = (cg0 * cs + b0 * CG * cs) * 16
+    hi = t.data_ptr() + off
+    lo = hi + t.stride(0) * 2 if P == 2 else None
+    return ActView(hi, lo, n, Hp - 2, Wp - 2, CG * cs, cs, 0)
+
+
+def stacked_at(planes, B, ncg, H, W, device):
+    """Group-major activation tensor [planes][CG][B][H+2][W+2][8] for SMALL feature maps: the B images of one channel group are stacked
+    vertically, each with its own zero border rows, so that the whole batch is ONE image of B*(H+2) - 2 rows to a conv launch (tall_view):
+    a tile then spans several images, and the layer's weights are fetched once per ~384 pixels instead of once per 16- or 64-pixel image.
+    The rows between two images are their bottom / top borders: zero in every conv INPUT (the producers write them), garbage in conv
+    OUTPUTS (which are only ever read at interior pixels)."""
+    t = torch.empty(planes, ncg, B, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
+    t._esr_stacked = True
+    return t
+
+
+def tall_view(t, b0=0, nb=None):
+    """Images [b0, b0 + nb) of the stacked tensor as one image per channel group (B' = 1): (view, rows)."""
+    P, CG, B, Hp, Wp, _ = t.shape
+    cs = B * Hp * Wp
+    hi = t.data_ptr() + b0 * Hp * Wp * 16
+    rows = (B - b0 if nb is None else nb) * Hp - 2
+    return ActView(hi, hi + t.stride(0) * 2 if P == 2 else None, CG, rows, Wp - 2, cs * CG, cs, 0), rows
+
+
 def pack_nchw(src, dst_view, c0, nc, pad=0, down=1, hw=None, batch_stride=0, channels=None):
     """fp32 NCHW (or a raw HR `view` of it: hw/batch_stride/channels given explicitly) -> act view."""
     require_gpu(src, 'input')
@@ -354,18 +403,28 @@ class PackedConv:
 
 
 class PackedConvSlices:
-    """Forward pack of a conv with MORE than 64 output channels (a multiple of 64): one 64-row pack per output slice, back to back in one buffer
-    — the layout esr_conv3x3 takes for cout > 64 (output slices of one launch, include/esr_hip.h); the bias is the parameter itself, indexed by
-    absolute channel.  Same duck type as PackedConv for the engine's batched re-pack (prepare / jobs / weights / after_pack)."""
+    """A conv weight as PackedConv slices of up to 64 rows, back to back in one buffer — the layout esr_conv3x3 takes for more than 64 output
+    channels (output slices of one launch, include/esr_hip.h).  Forward: one slice per 64 output channels (one slice of cout rows for
+    cout <= 64); the bias is indexed by absolute channel.  transposed=True: the data-gradient pack (transposed + flipped, no bias), one slice per
+    64 INPUT channels.  `weight` is any fp32 tensor of a 3x3 conv's shape (the critic packs the 3x3 embedding of its 4x4 weights).  Same duck
+    type as PackedConv for the batched re-pack (prepare / jobs / weights / after_pack)."""
 
-    def __init__(self, weight, bias, lat, split=True):
-        assert weight.shape[0] % 64 == 0 and weight.shape[0] > 64
-        self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, bias, lat, split, False
-        self.parts = [PackedConv(weight, None, lat, split=split, rows=list(range(64 * s, 64 * s + 64))) for s in range(weight.shape[0] // 64)]
+    def __init__(self, weight, bias, lat=0, split=True, transposed=False):
+        cout, cin = weight.shape[0], weight.shape[1]
+        self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, (None if transposed else bias), lat, split, transposed
+        if transposed:
+            assert lat == 0
+            if cin > 64 and cin % 64:
+                raise EsrError('conv weight %s: the data gradient needs up to 64 or a multiple of 64 input channels' % (tuple(weight.shape),))
+            self.parts = [PackedConv(weight, None, 0, split=split, transposed=True, m_slice=(m0, min(cin, m0 + 64))) for m0 in range(0, cin, 64)]
+        else:
+            assert cout <= 64 or cout % 64 == 0
+            self.parts = [PackedConv(weight, None, lat, split=split, rows=list(range(m0, min(cout, m0 + 64)))) for m0 in range(0, cout, 64)]
         self._key, self.wpack, self.bias = None, None, None
 
     def weights(self):
-        return (self.weight,)
+        # the bias too: without an epoch, PackBatch.run lets a pack with a shared bias re-read its address (after_pack) only when one of these moved
+        return (self.weight,) if self.bias_p is None else (self.weight, self.bias_p)
 
     def key(self):
         w = self.weight
@@ -378,13 +437,15 @@ class PackedConvSlices:
         if self.wpack is None:
             w = self.weight
             require_gpu(w, 'conv weight')
-            ncg_in = (1 if self.lat else 0) + (w.shape[1] - self.lat + 7) // 8
-            per = _lib.lib.esr_conv_wpack_bytes(ncg_in, 64, fmt_code(self.split))
+            if self.transposed:                   # (K groups, M rows) of one slice
+                ncg_in, m = (w.shape[0] + 7) // 8, min(w.shape[1], 64)
+            else:
+                ncg_in, m = (1 if self.lat else 0) + (w.shape[1] - self.lat + 7) // 8, min(w.shape[0], 64)
+            per = _lib.lib.esr_conv_wpack_bytes(ncg_in, m, fmt_code(self.split))
             self.wpack = torch.empty(len(self.parts) * per, dtype=torch.uint8, device=w.device)
             for s, pk in enumerate(self.parts):
                 pk.wpack = self.wpack[s * per:(s + 1) * per]
-                pk.prepare()
-                assert pk.ncg_in == ncg_in
+                pk.prepare()                      # (checks that its slice is as long as its pack)
             bp = self.bias_p
             if bp is not None and bp.dtype == torch.float32 and bp.is_contiguous():
                 self.bias, self._bias_shared = bp.detach(), True

@@ -21,7 +21,8 @@ import torch
 
 from . import _lib
 from . import act as A
-from ._lib import ActView, BnDesc, EsrError, check
+from .act import new_at, stacked_at, tall_view, view_of
+from ._lib import BnDesc, EsrError, check
 
 SLOPE = 0.2
 _state = {'input_grad_only': 0, 'group': None, 'only': None}
@@ -55,14 +56,6 @@ def _hints_for(S):
     return True, _state['group']
 
 
-
-# ------------------------------------------------------------------------------------------------ activation tensors
-def new_at(planes, B, ncg, H, W, device):
-    """Uninitialised: conv outputs and data gradients are only ever read at interior pixels; everything that becomes a conv (or weight-
-    gradient) INPUT is produced by pack_nchw or esr_bn_apply, which write the one-pixel zero border themselves."""
-    return torch.empty(planes, B, ncg, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
-
-
 def _tap_masks():
     """Per parity s = 2 py + px of the space-to-depth input: the taps (bit 3 ty + tx) of the embedded 3x3 weight that are non-zero — rows
     ty in {1 - py, 2 - py}, columns tx in {1 - px, 2 - px} (module docstring: dy = 2 ty + py - 1) — and the same for the flipped taps of the
@@ -81,43 +74,6 @@ def _tap_masks():
 
 
 MASK_FWD, MASK_FLIPPED = _tap_masks()       # (module attributes; None: multiply the structural zeros too — same results)
-
-
-def view_of(t, cg0=0, ncg=None, b0=0):
-    """View of channel groups [cg0, cg0 + ncg) starting at image b0 (the view has no batch size: the launch says how many images)."""
-    if getattr(t, '_esr_stacked', False):              # [planes][CG][B][H+2][W+2][8]: see stacked_at()
-        P, CG, B, Hp, Wp, _ = t.shape
-        n = CG - cg0 if ncg is None else ncg
-        cs = B * Hp * Wp
-        hi = t.data_ptr() + (cg0 * cs + b0 * Hp * Wp) * 16
-        return ActView(hi, hi + t.stride(0) * 2 if P == 2 else None, n, Hp - 2, Wp - 2, Hp * Wp, cs, 0)
-    P, B, CG, Hp, Wp, _ = t.shape
-    n = CG - cg0 if ncg is None else ncg
-    cs = Hp * Wp
-    off = (cg0 * cs + b0 * CG * cs) * 16
-    hi = t.data_ptr() + off
-    lo = hi + t.stride(0) * 2 if P == 2 else None
-    return ActView(hi, lo, n, Hp - 2, Wp - 2, CG * cs, cs, 0)
-
-
-def stacked_at(planes, B, ncg, H, W, device):
-    """Group-major activation tensor [planes][CG][B][H+2][W+2][8] for SMALL feature maps: the B images of one channel group are stacked
-    vertically, each with its own zero border rows, so that the whole batch is ONE image of B*(H+2) - 2 rows to a conv launch (tall_view):
-    a tile then spans several images, and the layer's weights are fetched once per ~384 pixels instead of once per 16- or 64-pixel image.
-    The rows between two images are their bottom / top borders: zero in every conv INPUT (the producers write them), garbage in conv
-    OUTPUTS (which are only ever read at interior pixels)."""
-    t = torch.empty(planes, ncg, B, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
-    t._esr_stacked = True
-    return t
-
-
-def tall_view(t, b0=0, nb=None):
-    """Images [b0, b0 + nb) of the stacked tensor as one image per channel group (B' = 1): (view, rows)."""
-    P, CG, B, Hp, Wp, _ = t.shape
-    cs = B * Hp * Wp
-    hi = t.data_ptr() + b0 * Hp * Wp * 16
-    rows = (B - b0 if nb is None else nb) * Hp - 2
-    return ActView(hi, hi + t.stride(0) * 2 if P == 2 else None, CG, rows, Wp - 2, cs * CG, cs, 0), rows
 
 
 def conv_io(t_in, t_out, B, h, w, b0=0):
@@ -225,38 +181,14 @@ class CriticEngine:
         return (((co * (4 * cin) + ch) * 3 + ty) * 3 + tx).reshape(-1)
 
     def _build_packs(self, L):
-        dev = L.conv.weight.device
-        fmt = self.split
+        w = L.conv.weight
         if L.strided:
-            L.E = torch.zeros(L.cout, 4 * L.cin, 3, 3, dtype=torch.float32, device=dev)
-            L.E_index = self._embed_index(L.cout, L.cin, dev)
-            w, cin_e = L.E, 4 * L.cin
-        else:
-            w, cin_e = L.conv.weight, L.cin
-        L.cin_e, L.wsrc = cin_e, w
-        ncg_in = (cin_e + 7) // 8
-        # forward: one 64-row pack per output slice, back to back in one buffer (esr_conv3x3_desc.cout > 64)
-        nsl = L.cout // 64
-        per = _lib.lib.esr_conv_wpack_bytes(ncg_in, 64, A.fmt_code(fmt))
-        buf = torch.empty(nsl * per, dtype=torch.uint8, device=dev)
-        L.fwd_packs = []
-        for s in range(nsl):
-            pk = A.PackedConv(w, None, 0, split=fmt, rows=list(range(64 * s, 64 * s + 64)))
-            pk.wpack = buf[s * per:(s + 1) * per]
-            L.fwd_packs.append(pk)
-        L.fwd = _SlicedPack(buf, L.conv.bias, fmt)
-        # data gradient: transposed + flipped, one pack per 64 INPUT channels
-        ncg_k = L.cout // 8
-        m = min(cin_e, 64)
-        nsl_t = max(cin_e // 64, 1)
-        per_t = _lib.lib.esr_conv_wpack_bytes(ncg_k, m, A.fmt_code(fmt))
-        buf_t = torch.empty(nsl_t * per_t, dtype=torch.uint8, device=dev)
-        L.tr_packs = []
-        for s in range(nsl_t):
-            pk = A.PackedConv(w, None, 0, split=fmt, transposed=True, m_slice=(64 * s, min(cin_e, 64 * s + 64)))
-            pk.wpack = buf_t[s * per_t:(s + 1) * per_t]
-            L.tr_packs.append(pk)
-        L.tr = _SlicedPack(buf_t, None, fmt)
+            L.E = torch.zeros(L.cout, 4 * L.cin, 3, 3, dtype=torch.float32, device=w.device)
+            L.E_index = self._embed_index(L.cout, L.cin, w.device)
+            w = L.E
+        L.cin_e = w.shape[1]
+        L.fwd = A.PackedConvSlices(w, L.conv.bias, split=self.split)
+        L.tr = A.PackedConvSlices(w, None, split=self.split, transposed=True)
 
     def pointer_fingerprint(self):
         """Everything a recorded launch list points at besides the buffer set: parameter / running-statistics storages and the weight packs."""
@@ -275,12 +207,11 @@ class CriticEngine:
         packs = []
         for L in self.layers:
             A.require_gpu(L.conv.weight, 'critic weight')
-            if L.fwd is None:
+            if L.fwd is None or L.fwd.bias_p is not L.conv.bias:         # (a bias parameter replaced by another: packs that read the new one)
                 self._build_packs(L)
             if L.strided:
                 L.E.view(-1)[L.E_index] = L.conv.weight.detach().float().reshape(-1)
-            L.fwd.bias = L.conv.bias.detach()
-            packs += L.fwd_packs + L.tr_packs
+            packs += [L.fwd, L.tr]
         self._batch.run(packs)
         self._fp = fp
 
@@ -307,32 +238,21 @@ class CriticEngine:
             dw = dw.view(-1)[L.E_index].view(L.cout, L.cin, 4, 4)
         return dw, db
 
-    def _bn_desc(self, L, y, st, s2d, dz=None, u=None, out0=None, out1=None, sums2=None, sums3=None):
-        d = BnDesc()
-        d.y = view_of(y)
-        for name, t in (('dz', dz), ('u', u), ('out0', out0), ('out1', out1)):
-            setattr(d, name, view_of(t) if t is not None else A.NO_VIEW)
-        d.B, d.groups, d.C = y.shape[1], 1, L.cout
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        d.scale, d.shift, d.mean, d.rstd = ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.rstd)
-        d.gamma = ptr(st.gamma)
-        d.sums2, d.sums3 = ptr(sums2), ptr(sums3)
-        d.slope, d.const_stats, d.s2d = SLOPE, 1 if st.const else 0, 1 if s2d else 0
-        return d
-
-
-class _SlicedPack:
-    """What A.conv3x3 needs of a weight pack: the packed bytes (64-row slices back to back), the bias array and the operand format."""
-
-    def __init__(self, wpack, bias, split):
-        self.wpack, self.bias, self.split = wpack, (bias.detach() if bias is not None else None), split
-
 
 class _Stats:
     """Per-layer normalisation state of one forward call (plain tensors: constants of the autograd graph; the dependence of the batch
-    statistics on the conv output is inside the closed-form gradients)."""
-    scale = shift = mean = rstd = gamma = None
+    statistics on the conv output is inside the closed-form gradients) — or, as _desc takes it, their addresses (_pointers, _BufSet.stats)."""
+    scale = shift = mean = rstd = gamma = sums2 = sums3 = None
     const = True
+
+
+def _pointers(st, sums2=None, sums3=None):
+    """The pointer form _desc takes of a per-layer call's tensor _Stats (and of the sums its backward passes accumulate)."""
+    p = _Stats()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    p.scale, p.shift, p.mean, p.rstd, p.gamma, p.sums2, p.sums3 = map(ptr, (st.scale, st.shift, st.mean, st.rstd, st.gamma, sums2, sums3))
+    p.const = st.const
+    return p
 
 
 # ------------------------------------------------------------------------------------------------ autograd
@@ -445,7 +365,7 @@ class _BNAct(torch.autograd.Function):
                 sums = buf[:Cc * 16].view(torch.float64)
                 f = buf[Cc * 16:].view(torch.float32)
                 st.mean, st.rstd, st.scale, st.shift = f[:Cc], f[Cc:2 * Cc], f[2 * Cc:3 * Cc], f[3 * Cc:]
-                d = eng._bn_desc(L, yd, st, False)
+                d = _desc(L, B, yd, _pointers(st), False)
                 check(_lib.lib.esr_bn_reduce(C.byref(d), 0, sums.data_ptr(), A.stream_ptr()), 'esr_bn_reduce')
                 mom = bn.momentum if bn.momentum is not None else 0.1
                 track = bn.track_running_stats and bn.running_mean is not None
@@ -465,7 +385,7 @@ class _BNAct(torch.autograd.Function):
         if s2d and (H % 2 or W % 2):
             raise EsrError('critic: odd feature-map size %dx%d in front of a stride-2 conv' % (H, W))
         z = new_at(P, B, CG * 4 if s2d else CG, Ho, Wo, dev)
-        d = eng._bn_desc(L, yd, st, s2d, out0=z)
+        d = _desc(L, B, yd, _pointers(st), s2d, out0=z)
         check(_lib.lib.esr_bn_apply(C.byref(d), 0, A.stream_ptr()), 'esr_bn_apply')
         ctx.eng, ctx.L, ctx.st, ctx.s2d = eng, L, st, s2d
         ctx.save_for_backward(y, gamma)
@@ -494,13 +414,13 @@ class _BNActBwd(torch.autograd.Function):
         if not st.const:
             Cc = L.cout
             sums2 = torch.zeros(Cc * 2, dtype=torch.float64, device=dev)
-            d = eng._bn_desc(L, yd, st, s2d, dz=dzd)
+            d = _desc(L, B, yd, _pointers(st), s2d, dz=dzd)
             check(_lib.lib.esr_bn_reduce(C.byref(d), 1, sums2.data_ptr(), A.stream_ptr()), 'esr_bn_reduce')
             pg = torch.empty(2, Cc, dtype=torch.float32, device=dev)
             dgamma, dbeta = pg[0], pg[1]
             check(_lib.lib.esr_bn_param_grads(sums2.data_ptr(), None, None, 1, Cc, B * (Hp - 2) * (Wp - 2), dgamma.data_ptr(), dbeta.data_ptr(), None,
                                               A.stream_ptr()), 'esr_bn_param_grads')
-        d = eng._bn_desc(L, yd, st, s2d, dz=dzd, out0=dy, sums2=sums2)
+        d = _desc(L, B, yd, _pointers(st, sums2), s2d, dz=dzd, out0=dy)
         check(_lib.lib.esr_bn_apply(C.byref(d), 1, A.stream_ptr()), 'esr_bn_apply')
         ctx.eng, ctx.L, ctx.st, ctx.s2d, ctx.sums2 = eng, L, st, s2d, sums2
         ctx.save_for_backward(y, gamma, dz)
@@ -524,13 +444,13 @@ class _BNActBwd(torch.autograd.Function):
         if not st.const:
             Cc = L.cout
             sums3 = torch.zeros(Cc * 3, dtype=torch.float64, device=dev)
-            d = eng._bn_desc(L, yd, st, s2d, dz=dzd, u=ud)
+            d = _desc(L, B, yd, _pointers(st), s2d, dz=dzd, u=ud)
             check(_lib.lib.esr_bn_reduce(C.byref(d), 2, sums3.data_ptr(), A.stream_ptr()), 'esr_bn_reduce')
             if gamma is not None and ctx.needs_input_grad[5]:
                 g_gamma = torch.empty(Cc, dtype=torch.float32, device=dev)
                 check(_lib.lib.esr_bn_param_grads(ctx.sums2.data_ptr(), sums3.data_ptr(), st.rstd.data_ptr(), 1, Cc, B * (Hp - 2) * (Wp - 2), None, None,
                                                   g_gamma.data_ptr(), A.stream_ptr()), 'esr_bn_param_grads')
-        d = eng._bn_desc(L, yd, st, s2d, dz=dzd, u=ud, out0=g_dz, out1=g_y, sums2=ctx.sums2, sums3=sums3)
+        d = _desc(L, B, yd, _pointers(st, ctx.sums2, sums3), s2d, dz=dzd, u=ud, out0=g_dz, out1=g_y)
         check(_lib.lib.esr_bn_apply(C.byref(d), 2, A.stream_ptr()), 'esr_bn_apply')
         return None, None, None, None, (g_y if not st.const else None), g_gamma, g_dz
 
@@ -637,7 +557,6 @@ class _BufSet:
         """Statistics pointers of block i, starting at group g (a launch over ONE group passes g and groups = 1)."""
         L = eng.layers[i]
         st = _Stats()
-        st.sums2 = st.sums3 = None
         if L.bn is None:
             return st
         st.gamma = L.bn.weight.data_ptr() if L.bn.weight is not None else None

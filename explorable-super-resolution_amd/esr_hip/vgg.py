@@ -19,8 +19,8 @@ import torch
 
 from . import _lib
 from . import act as A
+from .act import new_at, new_zeroed, view_of
 from ._lib import EsrError, check
-from .critic import _SlicedPack, view_of
 
 # torchvision.models.vgg cfgs ('M' = MaxPool2d(2, 2)); features = [Conv2d(cin, v, 3, padding=1), ReLU(inplace=True)] per number
 CFGS = {
@@ -57,16 +57,6 @@ def parse_arch(arch, use_bn=False):
             feature_layer = int(arch[len('vgg11_'):])
         arch = arch[:len('vgg11')]
     return arch, feature_layer
-
-
-def new_zeroed(planes, B, ncg, H, W, device):
-    """Activation tensor with its zero border (and zero interior): conv outputs that become conv inputs; the conv kernels never write borders."""
-    return torch.zeros(planes, B, ncg, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
-
-
-def new_at(planes, B, ncg, H, W, device):
-    """Uninitialised: for destinations whose producer writes the border itself (pack, pool, pool backward) or that are read at interior pixels only."""
-    return torch.empty(planes, B, ncg, H + 2, W + 2, 8, dtype=torch.bfloat16, device=device)
 
 
 class _Op:
@@ -131,32 +121,6 @@ class VGGEngine:
         return H, W
 
     # ------------------------------------------------------------------ weights
-    def _build_packs(self, op):
-        w, dev, fmt = op.conv.weight, op.conv.weight.device, self.split
-        ncg_in = (op.cin + 7) // 8
-        # forward: one 64-row pack per output slice, back to back in one buffer (esr_conv3x3_desc.cout > 64)
-        nsl, rows = max(op.cout // 64, 1), min(op.cout, 64)
-        per = _lib.lib.esr_conv_wpack_bytes(ncg_in, rows, A.fmt_code(fmt))
-        buf = torch.empty(nsl * per, dtype=torch.uint8, device=dev)
-        op.fwd_packs = []
-        for s in range(nsl):
-            pk = A.PackedConv(w, None, 0, split=fmt, rows=list(range(64 * s, 64 * s + rows)))
-            pk.wpack = buf[s * per:(s + 1) * per]
-            op.fwd_packs.append(pk)
-        op.fwd = _SlicedPack(buf, op.conv.bias, fmt)
-        # data gradient: transposed + flipped, one pack per 64 INPUT channels
-        m, nsl_t = min(op.cin, 64), max(op.cin // 64, 1)
-        if op.cin > 64 and op.cin % 64:
-            raise EsrError('VGG conv %r: the data gradient needs up to 64 or a multiple of 64 input channels' % (op.conv,))
-        per_t = _lib.lib.esr_conv_wpack_bytes((op.cout + 7) // 8, m, A.fmt_code(fmt))
-        buf_t = torch.empty(nsl_t * per_t, dtype=torch.uint8, device=dev)
-        op.tr_packs = []
-        for s in range(nsl_t):
-            pk = A.PackedConv(w, None, 0, split=fmt, transposed=True, m_slice=(64 * s, min(op.cin, 64 * s + 64)))
-            pk.wpack = buf_t[s * per_t:(s + 1) * per_t]
-            op.tr_packs.append(pk)
-        op.tr = _SlicedPack(buf_t, None, fmt)
-
     def refresh(self):
         """Pack the (frozen) weights: once, and again only when a weight's storage or version changed (load_state_dict, .to())."""
         convs = [op for op in self.ops if op.kind == 'conv']
@@ -168,10 +132,10 @@ class VGGEngine:
             A.require_gpu(op.conv.weight, 'VGG weight')
             if op.conv.weight.dtype != torch.float32 or op.conv.bias.dtype != torch.float32:
                 raise EsrError('VGG weights: fp32')
-            if op.fwd is None:
-                self._build_packs(op)
-            op.fwd.bias = op.conv.bias.detach().contiguous()
-            packs += op.fwd_packs + op.tr_packs
+            if op.fwd is None or op.fwd.bias_p is not op.conv.bias:
+                op.fwd = A.PackedConvSlices(op.conv.weight, op.conv.bias, split=self.split)
+                op.tr = A.PackedConvSlices(op.conv.weight, None, split=self.split, transposed=True)
+            packs += [op.fwd, op.tr]
         self._batch.run(packs)
         self._fp = fp
 

@@ -386,8 +386,8 @@ def test_split_k_convs_match_float64_like_the_unsplit_launch(precision):
         xa = K._PackIn.apply(xin, P)
         err = []
         for w in (None, ws):
-            y = K.new_at(P, B, L.cout // 8, h, h, 'cuda')
-            A.conv3x3(L.fwd, K.view_of(xa), B, h, h, L.cout, out=K.view_of(y), reverse=False, k_split_ws=w, **kw)
+            y = A.new_at(P, B, L.cout // 8, h, h, 'cuda')
+            A.conv3x3(L.fwd, A.view_of(xa), B, h, h, L.cout, out=A.view_of(y), reverse=False, k_split_ws=w, **kw)
             err.append(rel(K._UnpackOut.apply(y, L.cout), ref))
         assert bool(torch.isfinite(ws[:4096]).all()), ('forward did not split', li)
         assert err[1] < 1.05 * err[0] + 1e-7 and err[0] < (1e-5 if precision == 'split' else 5e-3), (li, err)
@@ -402,8 +402,8 @@ def test_split_k_convs_match_float64_like_the_unsplit_launch(precision):
             kw = {}
         err = []
         for w in (None, ws):
-            dx = K.new_at(P, B, L.cin_e // 8, h, h, 'cuda')
-            A.conv3x3(L.tr, K.view_of(dya), B, h, h, L.cin_e, out=K.view_of(dx), use_bias=False, reverse=False, k_split_ws=w, **kw)
+            dx = A.new_at(P, B, L.cin_e // 8, h, h, 'cuda')
+            A.conv3x3(L.tr, A.view_of(dya), B, h, h, L.cin_e, out=A.view_of(dx), use_bias=False, reverse=False, k_split_ws=w, **kw)
             err.append(rel(K._UnpackOut.apply(dx, L.cin_e), refdx))
         assert bool(torch.isfinite(ws[:4096]).all()), ('data gradient did not split', li)
         assert err[1] < 1.05 * err[0] + 1e-7 and err[0] < (1e-5 if precision == 'split' else 5e-3), (li, err)
@@ -489,3 +489,25 @@ def test_finalize_folded_into_the_normalise_launch_equals_the_separate_launch(mo
         if max(float(u.norm()), float(v.norm())) < 1e-6 * scale:
             continue
         assert rel(v, u) < 1e-6, (i, rel(v, u))
+
+
+def test_critic_follows_a_replaced_bias():
+    """The fused passes read each conv's bias in place, through launch lists recorded once: a bias parameter replaced by a new one, or given new
+    storage while the weight keeps its own, is what the next call reads.  The first conv's bias (no BatchNorm behind it) moves the logits."""
+    from esr_hip import critic as K
+    netD = make_D(64)
+    eng = K.CriticEngine(netD, 'split')
+    x = seeded_uniform((4, 3, 64, 64), 51).cuda()
+    conv = eng.layers[0].conv
+    with torch.no_grad():
+        prev = K.critic_forward(eng, x)
+        for replace, seed in (('parameter', 52), ('storage', 53)):
+            new = conv.bias.detach() + 2 * seeded_uniform((64,), seed).cuda() - 1
+            if replace == 'parameter':
+                conv.bias = torch.nn.Parameter(new)
+            else:
+                conv.bias.data = new
+            got, ref = K.critic_forward(eng, x), netD(x)
+            assert rel(got, ref) < 1e-3, (replace, rel(got, ref))
+            assert rel(got, prev) > 0.1, (replace, rel(got, prev))
+            prev = got

@@ -262,3 +262,50 @@ def test_batched_weight_pack_is_bit_identical_to_the_single_tensor_pack(split):
     torch.cuda.synchronize()
     for i, (pk, ref) in enumerate(zip(batch, want)):
         assert torch.equal(pk.wpack, ref), (i, kinds[i]['weight'].shape, int((pk.wpack != ref).sum()))
+
+
+@pytest.mark.parametrize('precision', ['split', 'bf16'])
+def test_sliced_packs_of_every_engine_are_their_slices_packed_alone(precision):
+    """A.PackedConvSlices as the critic, the VGG extractor and an nf = 128 generator pack it (one batched re-pack): the forward buffer is the
+    64-row output slices (one slice of cout rows up to 64), the data-gradient buffer the 64-channel input slices, each packed stand-alone by
+    PackedConv, back to back.  Critic: a stride-2 layer (its 3x3 embedding) and a 64 -> 128 one; VGG: the 3-channel first conv and a
+    256 -> 256 one; generator: its first conv (latent group, 128 rows)."""
+    from esr_hip import act as A
+    from esr_hip import critic as K
+    from esr_hip import vgg as V
+    from test_gpu_critic import make_D
+    import models.modules.architecture as arch
+
+    def alone(pk):
+        w, split = pk.weight, pk.split
+        n = w.shape[1] if pk.transposed else w.shape[0]
+        if pk.transposed:
+            parts = [A.PackedConv(w, None, 0, split=split, transposed=True, m_slice=(m0, min(n, m0 + 64))) for m0 in range(0, n, 64)]
+        else:
+            parts = [A.PackedConv(w, None, pk.lat, split=split, rows=list(range(m0, min(n, m0 + 64)))) for m0 in range(0, n, 64)]
+        return torch.cat([p.get().wpack for p in parts])
+
+    cases = []
+    ceng = K.CriticEngine(make_D(64), precision)
+    ceng.refresh()
+    assert ceng.layers[1].strided and ceng.layers[1].cin_e == 256 and ceng.layers[2].cout == 128
+    cases += [('critic%d %s' % (i, d), getattr(ceng.layers[i], d)) for i in (1, 2) for d in ('fwd', 'tr')]
+    torch.manual_seed(4)
+    feats = torch.nn.Sequential(torch.nn.Conv2d(3, 64, 3, padding=1), torch.nn.ReLU(), torch.nn.Conv2d(64, 256, 3, padding=1), torch.nn.ReLU(),
+                                torch.nn.Conv2d(256, 256, 3, padding=1)).cuda()
+    veng = V.VGGEngine(feats, precision=precision)
+    veng.refresh()
+    cases += [('vgg%d %s' % (i, d), getattr(veng.ops[i], d)) for i in (0, 2) for d in ('fwd', 'tr')]
+    net = arch.RRDBNet(in_nc=3, out_nc=3, nf=128, nb=1, gc=32, upscale=4, norm_type=None, act_type='leakyrelu', mode='CNA', upsample_mode='upconv',
+                       latent_input='all_layers_HR_downscaled', num_latent_channels=3)
+    fill_formula_weights(net, gain=0.5)
+    net = net.cuda()
+    net.set_precision(precision)
+    gpk = net.engine.packed()['fea']
+    assert isinstance(gpk, A.PackedConvSlices) and gpk.lat == 3 and gpk.weight.shape[0] == 128
+    cases.append(('generator fea', gpk))
+    torch.cuda.synchronize()
+    for name, pk in cases:
+        assert isinstance(pk, A.PackedConvSlices), name
+        want = alone(pk)
+        assert pk.wpack.shape == want.shape and torch.equal(pk.wpack, want), (name, int((pk.wpack != want).sum()))

@@ -65,7 +65,7 @@ def gpu_pattern(net, saved):
 
 def _unpack(t, nc):
     from esr_hip import _lib
-    from esr_hip.critic import view_of
+    from esr_hip.act import view_of
     B = t.shape[1]
     out = torch.empty(B, nc, t.shape[3] - 2, t.shape[4] - 2, dtype=torch.float32, device=t.device)
     assert _lib.lib.esr_unpack_nchw(C.byref(view_of(t)), B, nc, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
@@ -75,8 +75,7 @@ def _unpack(t, nc):
 def _pack(x, planes):
     """fp32 NCHW (GPU) -> activation tensor [planes][B][CG][H+2][W+2][8] (no normalisation)."""
     from esr_hip import _lib
-    from esr_hip.critic import view_of
-    from esr_hip.vgg import new_at
+    from esr_hip.act import new_at, view_of
     B, Cc, H, W = x.shape
     t = new_at(planes, B, (Cc + 7) // 8, H, W, x.device)
     assert _lib.lib.esr_pack_nchw_norm(x.data_ptr(), B, Cc, H, W, None, None, C.byref(view_of(t)), C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
@@ -116,8 +115,7 @@ def test_maxpool_forward_backward(precision, shape):
     """esr_maxpool2x2 copies the window maximum (hi and lo bit for bit, torch's argmax); esr_maxpool2x2_grad scatters dy to that argmax,
     with and without the fused ReLU backward.  Against F.max_pool2d on the values the activation tensor holds: exact."""
     from esr_hip import _lib
-    from esr_hip.critic import view_of
-    from esr_hip.vgg import new_at
+    from esr_hip.act import new_at, view_of
     P = 2 if precision == 'split' else 1
     B, Cc, H, W = shape
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -145,8 +143,7 @@ def test_maxpool_forward_backward(precision, shape):
 def test_maxpool_exact_ties_and_nan_follow_torch(precision):
     """Windows full of exact ties (values from {0, 1, 2}): the first maximum in row-major order wins, as in torch; a NaN propagates."""
     from esr_hip import _lib
-    from esr_hip.critic import view_of
-    from esr_hip.vgg import new_at
+    from esr_hip.act import new_at, view_of
     P = 2 if precision == 'split' else 1
     B, Cc, H, W = 2, 8, 8, 10
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -108,8 +108,7 @@ def part_step(a, wfile):
 def part_extractor(a, wfile):
     import models.modules.architecture as arch
     from esr_hip import _lib
-    from esr_hip.critic import view_of
-    from esr_hip.vgg import new_at
+    from esr_hip.act import new_at, view_of
     dev = torch.device('cuda', 0)
     sd = torch.load(wfile)
     net = arch.VGGFeatureExtractor(state_dict=sd).to(dev).eval()

@@ -154,8 +154,9 @@ struct FetchState {
 };
 
 // Flattened-tile pixel p -> (row, column) with the pitch division as a multiplication (m_P = ceil(2^20 / P): exact for p * P < 2^20, and
-// p < 1024, P <= 386), nearest-upsample source coordinate (c - 1 + ups) / ups the same way (m_ups = ceil(2^16 / ups): exact for
-// coordinates < 2^15, checked by the host; ups = 1: the identity).
+// p < 1024, P <= 386), nearest-upsample source coordinate (c - 1 + ups) / ups the same way (m_ups = ceil(2^16 / ups): for ups = 1, 2, 3, 4,
+// 6 and 8 — the factors the host accepts — exact at every padded coordinate c <= ups * W_in + 1 of an image with W + 2 < 2^15; for 5 and 7 it
+// is one too large from c = 16380 / 13104 on).
 template <int MAXS>
 __device__ __forceinline__ FetchState<MAXS> setup_tile(const ConvArgs& a, int x0, int y0, int wave, int lane) {
     FetchState<MAXS> f;
@@ -405,9 +406,10 @@ constexpr int S2D_FWD[4] = {432, 216, 54, 27}, S2D_FLIP[4] = {27, 54, 216, 432};
 //
 // What depends only on (tile, lane) is computed ONCE, in front of the K loop where a lone workgroup waits for its first copies anyway
 // (epi_coords): per column tile the lane's byte offset inside an activation plane and `lim` = how many output groups the lane may store
-// (0: its pixel is pitch padding or outside the image; ncg_out - half otherwise, so that one compare `cg0 < lim` covers both the pixel and
-// the existence of group cg0 + half).  KIND 1 (fp32 NCHW destination): poff = byte offset inside a channel plane, lim without the half
-// term (every lane stores its own 4 channels of both groups); KIND 2 (pixel-shuffle store): poff = Y << 16 | X.
+// (-1: its pixel is pitch padding or outside the image; ncg_out - half otherwise, so that one compare `cg0 < lim` covers both the pixel and
+// the existence of group cg0 + half; `cg0 < lim + half`: the pixel is inside and the pair has its group cg0 — both halves of the wave compute
+// such a pair, the lane exchanges need both).  KIND 1 (fp32 NCHW destination): poff = byte offset inside a channel plane, lim without the
+// half term, 0 outside (every lane stores its own 4 channels of both groups); KIND 2 (pixel-shuffle store): poff = Y << 16 | X.
 template <int R>
 struct EpiCoord {
     int lim[R];
@@ -423,7 +425,7 @@ __device__ __forceinline__ EpiCoord<R> epi_coords(const ConvArgs& a, int x0, int
         const unsigned rr = __umul24(q, a.m_P) >> 20, cc = q - rr * a.P;
         const unsigned Y = y0 + rr, X = x0 + cc;
         const bool valid = (rr < (unsigned)a.TH) && (cc < (unsigned)a.TW) && (Y < (unsigned)a.H) && (X < (unsigned)a.W);
-        e.lim[r] = valid ? (KIND == 1 ? a.ncg_out : a.ncg_out - half) : 0;
+        e.lim[r] = valid ? (KIND == 1 ? a.ncg_out : a.ncg_out - half) : (KIND == 1 ? 0 : -1);
         if (KIND == 1) e.poff[r] = (__umul24(Y, a.W) + X) * 4;
         else if (KIND == 2) e.poff[r] = (Y << 16) | X;
         else e.poff[r] = valid ? (__umul24(Y + 1, a.W + 2) + X + 1) * 16 : 0;
@@ -511,7 +513,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
 #pragma unroll
             for (int gp = 0; gp < 2; ++gp) {
                 const int cg0 = m * 4 + gp * 2;                  // this pair: output groups cg0, cg0+1
-                if (!(cg0 < ec.lim[r])) continue;                // per lane: pixel inside the image and group cg0 + half exists
+                // per lane: pixel inside the image and group cg0 exists.  Lane i + 32 computes channels 4-7 of group cg0 for lane i's store (the
+                // exchanges below), so both halves compute the last pair of an odd group count; only lanes whose group cg0 + half exists store.
+                if (!(cg0 < ec.lim[r] + (NCHW ? 0 : half))) continue;
+                const bool store = cg0 < ec.lim[r];
                 f32x2 v[2][2];                                   // [group k][channel pair]: this lane's 4 channels of both groups
 #pragma unroll
                 for (int k = 0; k < 2; ++k)
@@ -601,12 +606,14 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
                     const int Y = ec.poff[r] >> 16, X = ec.poff[r] & 0xFFFF;
                     off = ((unsigned)(rg / r2) * (unsigned)a.out.cs + (unsigned)(a.ps * Y + sp / a.ps + 1) * (a.ps * a.W + 2) + (a.ps * X + sp % a.ps + 1)) * 16;
                 } else off = ec.poff[r] + ho + cg0 * ((unsigned)a.out.cs * 16);
-                *(uint4*)(oh + off) = hv;
-                if (NPL == 2 && (!PARTLO || ol)) *(uint4*)(ol + off) = lv;
-                if constexpr (OUT2) {
-                    const unsigned off2 = ec.poff[r] + ho2 + cg0 * ((unsigned)a.out2.cs * 16);
-                    *(uint4*)(o2h + off2) = hv;
-                    if (NPL == 2 && o2l) *(uint4*)(o2l + off2) = lv;
+                if (store) {
+                    *(uint4*)(oh + off) = hv;
+                    if (NPL == 2 && (!PARTLO || ol)) *(uint4*)(ol + off) = lv;
+                    if constexpr (OUT2) {
+                        const unsigned off2 = ec.poff[r] + ho2 + cg0 * ((unsigned)a.out2.cs * 16);
+                        *(uint4*)(o2h + off2) = hv;
+                        if (NPL == 2 && o2l) *(uint4*)(o2l + off2) = lv;
+                    }
                 }
             }
         }
@@ -659,7 +666,10 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
         a.wpack += sl * a.wslice;
         a.bias += sl * (MT * 32) * a.bias_stride;
         auto shift = [&](DView& v) { if (v.hi) { v.hi += sl * (MT * 4) * v.cs; if (v.lo) v.lo += sl * (MT * 4) * v.cs; } };
-        shift(a.out); shift(a.out2); shift(a.res1); shift(a.res2); shift(a.mask);
+        shift(a.out); shift(a.out2); shift(a.res1); shift(a.res2);
+        // mask_src is group mask_cg0 of the output, not group 0: the slice moves the window instead ([mask_cg0, mask_cg1) in the slice's groups)
+        a.mask_cg0 -= (int)sl * (MT * 4);
+        a.mask_cg1 -= (int)sl * (MT * 4);
         if constexpr ((EPI & EPI_RESIN) != 0) a.resin_g0 += (int)sl * (MT * 4);      // the slice's residual groups: further along the input
         if constexpr ((EPI & EPI_NCHW) != 0) {
             a.out_nchw += sl * (MT * 32) * (long long)a.H * a.W;           // (slices with an fp32 destination: the split-K partial sums, B == 1 per image row below)
@@ -1140,10 +1150,44 @@ extern "C" int esr_pack_batch_run(const void* workspace, int n, int64_t nblocks,
     return ESR_OK;
 }
 
+// The kernel form a launch runs and its tile geometry (esr_conv3x3, esr_conv3x3_tiling).
+// A 64-channel layer whose launch would leave every workgroup alone on its CU (no more tiles than CUs: the 52 x 52 training crops, a single
+// image of the Z search) runs as TWO 32-channel output slices of the MT = 1 kernel instead (mslice; grid y; same pack, ConvArgs.wtap): twice the
+// workgroups, so that two are resident per CU and cover each other's copy issue and waits — at the price of staging the input tile twice
+// (the second copy comes out of the same XCD's L2).  Same arithmetic per output channel: results are bit-identical to the 64-channel form.
+static TileCfg conv_tiling(const esr_conv3x3_desc* d, int npl, int mt, int nslices, int ps, bool& mslice) {
+    mslice = false;
+    auto all_taps = [](const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); };
+    if (nslices == 1 && mt == 2 && d->cout == 64 && !d->out_nchw && !ps && d->lds_stages == 0 && !d->k_split_ws && all_taps(d->tap_mask_k) &&
+        all_taps(d->tap_mask_m) && (!d->mask_src.hi || (d->mask_cg0 == 0 && d->mask_cg1 >= 8))) {
+        const TileCfg t2 = pick_tile(d->H, d->W, npl, 2, WGS_MT2);
+        mslice = t2.TH != 0 && (long long)t2.tiles_x * t2.tiles_y * d->B <= 320;
+    }
+    const int mt_k = mslice ? 1 : mt;
+    return pick_tile(d->H, d->W, npl, mt_k, mt_k == 1 ? WGS_MT1 : WGS_MT2);
+}
+
+extern "C" int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling) {
+    if (!d || !tiling || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return ESR_E_ARG;
+    if (d->cout > 64 && d->cout % 64) return ESR_E_UNSUPPORTED;
+    const int nslices = d->cout > 64 ? d->cout / 64 : 1;
+    const int mt = nslices > 1 ? 2 : (d->cout + 31) / 32;
+    bool mslice = false;
+    const TileCfg t = conv_tiling(d, d->in1.lo ? 2 : 1, mt, nslices, d->pixel_shuffle > 1 ? d->pixel_shuffle : 0, mslice);
+    if (t.TH == 0) return ESR_E_UNSUPPORTED;
+    tiling[0] = t.tiles_x;
+    tiling[1] = t.tiles_y;
+    tiling[2] = mslice ? 1 : mt;
+    tiling[3] = mslice ? 2 : nslices;
+    return ESR_OK;
+}
+
 extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     if (!d || !d->in1.hi || !d->wpack || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return ESR_E_ARG;
     if (!d->out.hi && !d->out_nchw) return ESR_E_ARG;
     const int ups = d->upsample <= 0 ? 1 : d->upsample;
+    // the kernel forms the source coordinate (c - 1 + ups) / ups as a multiplication (setup_tile): exact for these factors only
+    if (ups > 8 || ups == 5 || ups == 7) return ESR_E_UNSUPPORTED;
     if (ups > 1 && d->in0.hi) return ESR_E_UNSUPPORTED;
     if (d->in1.H * ups != d->H || d->in1.W * ups != d->W) return ESR_E_ARG;
     if (d->in0.hi && (d->in0.H != d->H || d->in0.W != d->W)) return ESR_E_ARG;
@@ -1188,20 +1232,9 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     a.H = d->H;
     a.W = d->W;
     const int npl = split ? 2 : 1;
-    // A 64-channel layer whose launch would leave every workgroup alone on its CU (no more tiles than CUs: the 52 x 52 training crops, a single
-    // image of the Z search) runs as TWO 32-channel output slices of the MT = 1 kernel instead (grid y; same pack, ConvArgs.wtap): twice the
-    // workgroups, so that two are resident per CU and cover each other's copy issue and waits — at the price of staging the input tile twice
-    // (the second copy comes out of the same XCD's L2).  Same arithmetic per output channel: results are bit-identical to the 64-channel form.
     bool mslice = false;
-    auto all_taps = [](const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); };
-    if (nslices == 1 && mt == 2 && d->cout == 64 && !d->out_nchw && !ps && d->lds_stages == 0 && !d->k_split_ws && all_taps(d->tap_mask_k) &&
-        all_taps(d->tap_mask_m) && (!d->mask_src.hi || (d->mask_cg0 == 0 && d->mask_cg1 >= 8))) {
-        const TileCfg t2 = pick_tile(d->H, d->W, npl, 2, WGS_MT2);
-        mslice = t2.TH != 0 && (long long)t2.tiles_x * t2.tiles_y * d->B <= 320;
-    }
+    const TileCfg t = conv_tiling(d, npl, mt, nslices, ps, mslice);
     const int mt_k = mslice ? 1 : mt;                              // M tiles per workgroup of the kernel that runs
-    const int wgs_per_cu = mt_k == 1 ? WGS_MT1 : WGS_MT2;
-    const TileCfg t = pick_tile(d->H, d->W, npl, mt_k, wgs_per_cu);
     if (t.TH == 0) return ESR_E_UNSUPPORTED;
     if (mslice) { a.cout = 32; a.nslices = 2; }
     a.TH = t.TH; a.TW = t.TW; a.P = t.P; a.NPIX_T = t.NPIX_T; a.NPIX_L = t.NPIX_L;
@@ -1219,7 +1252,7 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     a.nslots = (a.NPIX_L + 63) / 64;
     a.ncg_out = (a.cout + 7) >> 3;
     // (udiv_magic is exact while n * d < 2^32: tile / tiles_x with tile < ntiles, and trow / tiles_y with trow < B * tiles_y)
-    if (d->H + 2 >= 32768 || d->W + 2 >= 32768 || ups > 8 || (long long)a.ntiles * a.tiles_x >= 0x100000000ll ||
+    if (d->H + 2 >= 32768 || d->W + 2 >= 32768 || (long long)a.ntiles * a.tiles_x >= 0x100000000ll ||
         (long long)a.B * a.tiles_y * a.tiles_y >= 0x100000000ll)
         return ESR_E_UNSUPPORTED;
     {

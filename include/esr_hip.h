@@ -73,9 +73,16 @@ typedef struct {
  *   out = alpha * act(conv(in0 ++ in1) + bias) + beta1*res1 + beta2*res2
  *
  * Limits checked by the entry point (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise): 0 <= act_slope <= 1 and alpha >= 0 (the epilogue evaluates
- * alpha * LeakyReLU(y) as max(alpha*y, alpha*act_slope*y); act_slope = 0 is ReLU, torchvision VGG's nn.ReLU(inplace=True)); H + 2 and W + 2 below 32768, upsample <= 8; every view's image (ncg * cg_stride * 16
+ * alpha * LeakyReLU(y) as max(alpha*y, alpha*act_slope*y); act_slope = 0 is ReLU, torchvision VGG's nn.ReLU(inplace=True)); H + 2 and W + 2 below 32768; upsample
+ * 0 or 1 (none), 2, 3, 4, 6 or 8 (ESR_E_UNSUPPORTED otherwise, checked before anything touches the device: the kernel maps an output coordinate to its
+ * source by a multiplication that is exact for these factors only); every view's image (ncg * cg_stride * 16
  * bytes) and the fp32 destination's image below 4 GiB (per-lane addresses are a uniform per-image base + a 32-bit offset); res1 / res2 cover
  * every output group (ncg * 8 >= cout); mask_src covers the masked groups.
+ * Epilogues with a kernel (ESR_E_UNSUPPORTED otherwise): plain; res1; res1 + res2; out_nchw; out2; mask_src; res1 + mask_src (bf16 formats only);
+ * pixel_shuffle — res2 only together with res1, and out2, out_nchw, mask_src and pixel_shuffle each on its own (besides res1 + mask_src).
+ * Without pixel_shuffle, an act-layout `out` (and out2) is written at the interior pixels of groups [0, ceil(cout / 8)) only: never its border, never a group behind them.  The
+ * channels past cout of a partial last group are written too, with a zero conv and bias: beta1*res1 + beta2*res2 of those channels, masked like
+ * the rest (zero when the residuals hold zero there).
  *
  * When res1 is a channel-group slice of in1 itself (same strides; the RDB's  conv5*0.2 + x, block.py:235) and act_slope == 1,
  * the library notices it from the pointers and takes the residual from the input tile it stages on chip anyway (no extra reads);
@@ -84,7 +91,7 @@ typedef struct {
 typedef struct {
     esr_act_view in0;        /* optional leading segment (latent Z group); ncg = 0 when absent */
     esr_act_view in1;        /* main segment; with upsample>1 it is read as in1[y/upsample][x/upsample] */
-    int32_t upsample;        /* 1, 2 or 3 */
+    int32_t upsample;        /* 0 or 1: none; 2, 3, 4, 6 or 8 (the limits above) */
     const void* wpack;       /* weights packed by esr_pack_conv_weights for (in0.ncg + in1.ncg) groups */
     const float* bias;       /* [mtiles*32] fp32, zero padded; NULL = no bias */
     int32_t cout;            /* real output channels: <= 64, or a multiple of 64 — then the launch covers cout/64 output slices at once and `wpack`
@@ -101,7 +108,8 @@ typedef struct {
     /* data-gradient helper: multiply the result for output groups [mask_cg0, mask_cg1) by
      * act'(mask_src) = (mask_src > 0 ? 1 : mask_slope) AFTER the residual add (LeakyReLU backward of
      * the layer that produced those channels; block.py:18; mask_slope = 0: ReLU backward, the gradient passes where the stored output
-     * is > 0, as torch's in-place ReLU). mask_src.hi == NULL: disabled. */
+     * is > 0, as torch's in-place ReLU). mask_src.hi == NULL: disabled.  Group 0 of mask_src is output group mask_cg0; only the sign of its
+     * hi plane is read, in either element format.  With output slices the window is in absolute groups and may span slices. */
     esr_act_view mask_src; int32_t mask_cg0, mask_cg1; float mask_slope;
     /* scheduling hint, no effect on the result: walk the tiles (and so the images) last to first.  Consecutive layers of a network
      * re-read what the previous launch just touched; alternating the direction lets the tail of one launch, still in the 256 MB
@@ -113,7 +121,9 @@ typedef struct {
     int32_t weight_planes;
     /* fp16 formats only: number of LEADING channel groups of in1 whose lo plane carries data (0 = all of them).  The groups behind
      * them are single-plane intermediates (a dense block's conv outputs, consumed only inside the block, where 11 bits suffice): their
-     * lo plane is neither read nor multiplied.  Likewise `out.lo == NULL` with hi+lo inputs stores the result as one fp16 plane. */
+     * lo plane is neither read nor multiplied — counted in K chunks of two groups, in0's included: when in0.ncg + in1_lo_groups is odd, the
+     * lo plane of the first group behind them is multiplied too and must hold zero (or that group's residue).  < 0: no lo plane is multiplied.
+     * Likewise `out.lo == NULL` with hi+lo inputs stores the result as one fp16 plane. */
     int32_t in1_lo_groups;
     /* pixel-shuffle store (codes/models/modules/block.py:278-291: conv to out_nc*r^2 channels, nn.PixelShuffle(r), act): with
      * pixel_shuffle = r > 1 the launch's output rows are taken in groups of 8 ("row groups"); row group g = ps_rowgroup0 + (row / 8)
@@ -153,6 +163,12 @@ typedef struct {
 } esr_conv3x3_desc;
 
 int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream);
+
+/* Host-only query (no device access, nothing launched): how esr_conv3x3 would tile the launch `d` describes, without split K.
+ * tiling[0] / [1] = output tiles per image along x / y, [2] = M tiles (32 output channels) per workgroup, [3] = output slices (grid y; 2 when a
+ * 64-channel layer of a small launch runs as two 32-channel slices).  The launch has tiling[0] * tiling[1] * B * tiling[3] workgroups; up to 320
+ * of them take the small-launch (multi-stage) form.  Checks only the sizes it needs (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise). */
+int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling);
 
 /* Adjoint of the pixel-shuffle store: dst[b][g*r^2 + s][y][x] = src[b][g][r*y + s / r][r*x + s % r] for every group g of `src`
  * (dst.ncg == src.ncg * r^2, src.H == r*dst.H): the gradient of the shuffled tensor laid out in the conv's row-group order

@@ -288,6 +288,25 @@ def test_cabi_argument_validation_without_a_gpu():
     assert h.esr_conv3x3(None, None) == E_ARG
     d = _lib.Conv3x3Desc()                                   # all-zero descriptor: no input view, no weights
     assert h.esr_conv3x3(C.byref(d), None) == E_ARG
+    # upsample factors without an exact source-coordinate map (5, 7) or above 8: refused before the device is touched (the pointers below
+    # are never dereferenced)
+    for ups in (5, 7, 9):
+        d = _lib.Conv3x3Desc()
+        d.in1 = _lib.ActView(16, None, 1, 1, 2, 12, 12, 0)
+        d.out = _lib.ActView(32, None, 1, ups, 2 * ups, (ups + 2) * (2 * ups + 2), (ups + 2) * (2 * ups + 2), 0)
+        d.wpack, d.cout, d.B, d.H, d.W, d.upsample = 48, 8, 1, ups, 2 * ups, ups
+        assert h.esr_conv3x3(C.byref(d), None) == E_UNSUPPORTED, ups
+    # the tiling query is host arithmetic too (the geometry cases of tests/test_gpu_conv_contract.py are placed with it)
+    t = (C.c_int32 * 4)()
+    assert h.esr_conv3x3_tiling(None, t) == E_ARG
+    d = _lib.Conv3x3Desc()
+    d.in1 = _lib.ActView(16, 16, 1, 4, 4, 0, 0, 0)
+    d.B, d.H, d.W, d.cout = 321, 4, 4, 64
+    assert h.esr_conv3x3_tiling(C.byref(d), t) == 0 and tuple(t) == (1, 1, 2, 1)
+    d.B = 320                                                 # no more tiles than the small form allows: two 32-channel slices
+    assert h.esr_conv3x3_tiling(C.byref(d), t) == 0 and tuple(t) == (1, 1, 1, 2)
+    d.cout = 96
+    assert h.esr_conv3x3_tiling(C.byref(d), t) == E_UNSUPPORTED
     assert h.esr_pack_conv_weights(None, 32, 64, None, 8, None, 1, 0, 1, 1.0, None, None) == E_ARG
     assert h.esr_pack_nchw(None, 0, 1, 3, 8, 8, 0, 3, 0, 1, None, None) < 0
     assert h.esr_cem_downscale(None, 1, 3, 8, 8, 4, 1, None, 17, None, 0, None, None) == E_ARG

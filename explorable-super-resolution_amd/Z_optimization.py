@@ -8,8 +8,19 @@ reduction torch ops on the SR output.  Implemented objectives: 'max_STD', 'min_S
 'hist' (gray-level histogram), and the patch-histogram / dictionary objectives of the GUI's "Imitate histogram" and "Imitate patch histogram"
 tools: 'patchhist', 'patchhist_noDC', 'dict', 'dict_noDC', 'patchdict', 'patchdict_noDC' (SoftHistogramLoss on the pairwise KDE kernels),
 whole-image or restricted to a user-marked region (image_mask: where the objective looks; Z_mask: which latent entries may move — the
-GUI's region tools, GUI.py:1925-2057).  The GUI's scribble / periodicity / adversarial / 'local_*' patch objectives, the '*_localSTD' histogram
-variants and the automatic histogram temperature are not part of this build and raise NotImplementedError.
+GUI's region tools, GUI.py:1925-2057), and the GUI's local-variance, TV and periodicity tools (what its LOCAL_STD_4_OPT / RELATIVE_STD_OPT
+flags make it send, GUI.py:79-86, :1925-1937):
+  'local_max_STD' / 'local_min_STD'            -/+ mean_p S[p, b]
+  'local_STD_increase' / 'local_STD_decrease'  mean_p (S[p, b] - desired[p])^2, desired = initial x 1.05^(+-1) or initial +- data['STD_increment']
+  'local_STD_TV'                               mean_p 100 (S[p, b] - initial[p])^2 + TV_Loss(clamp(out) * mask)_b
+  '[local_STD_][nonInt_]periodicity[_1D]'      20 mean_{p,b'} (S - initial)^2 + sum_points mean M |GS+(out) - GS-(out)| (data['periodicity_points'];
+                                               'nonInt': bilinear grid_sample on the reference's coordinate lines, else integer crops)
+where S is the unbiased STD of every 7 x 7 window inside the opened image mask of the gray output (esr_hip.local.patch_std, csrc/esr_local.hip;
+whole-image Masked_STD for the periodicity names without 'local') and initial its value on the FIRST image of the model's output at
+construction.  A flat window's gradient is 0 here, NaN in the reference (torch.std's backward at 0).
+Not part of this build (NotImplementedError): the GUI's scribble / adversarial objectives, the 'Plus' / 'Mag' variants, 'local_*' names
+without STD (the overlap-0.5 patch selection with its non-covered pixels), the local / periodicity objectives in training mode (HR_unpadder)
+or with non_local_Z_optimization on a partial image mask, the '*_localSTD' histogram variants and the automatic histogram temperature.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective).  Like the reference, the loss is the
 mean over the WHOLE batch, so each shard scales its local sum by 1/B_global; the loss history that picks the best iterate is
@@ -21,6 +32,7 @@ import numpy as np
 import torch
 
 from esr_hip import dist as esr_dist
+from esr_hip import local as esr_local
 
 
 def ArcTanH(input_tensor):
@@ -238,15 +250,35 @@ def hist_objective_config(objective):
                 dictionary_not_histogram='dict' in objective, no_patch_DC='noDC' in objective)
 
 
+# the local-STD and periodicity objectives (reference :391-398, :459-509, :616-627, :712-733, :799-815; what the GUI's variance, TV and
+# periodicity tools send, GUI.py:1457-1459, :1481-1482, :1925-1937)
+LOCAL_STD_OBJECTIVES = ('local_max_STD', 'local_min_STD', 'local_STD_increase', 'local_STD_decrease', 'local_STD_TV')
+PERIODICITY_OBJECTIVES = tuple(pre + mid + 'periodicity' + post for pre in ('local_STD_', '') for mid in ('nonInt_', '') for post in ('', '_1D'))
+
+
 class Z_optimizer():
     MIN_LR = 1e-5
-    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES)
+    PATCH_SIZE_4_STD = 7
+    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES) + \
+        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES)
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
                  **unsupported):
         if 'localSTD' in objective:
             hist_objective_config(objective)            # raises, naming the variant
+        new_objective = objective in LOCAL_STD_OBJECTIVES or objective in PERIODICITY_OBJECTIVES
+        for variant in ('Plus', 'Mag'):
+            if variant in objective:
+                raise NotImplementedError("Z objective '%s': the '%s' variant (the GUI's special-behaviour button) is not part of this build" % (objective, variant))
+        if 'local' in objective and 'STD' not in objective:
+            raise NotImplementedError("Z objective '%s': 'local' objectives without STD (their overlap-0.5 greedy patch selection and non-covered pixel "
+                                      "set) are not part of this build" % objective)
+        if new_objective and HR_unpadder is not None:
+            raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder): the reference has no initial STD there" % objective)
+        if new_objective and unsupported.get('non_local_Z_optimization') and image_mask is not None and np.mean(image_mask) < 1:
+            raise NotImplementedError("Z objective '%s' with non_local_Z_optimization on a partial image mask (the GUI's region-constraint mode: Z-mask "
+                                      "rebuild and constraining L1) is not part of this build" % objective)
         if objective in HIST_OBJECTIVES and auto_set_hist_temperature:
             raise NotImplementedError("Z objective '%s': auto_set_hist_temperature (the temperature search differentiates through the generator "
                                       "twice) is not part of this build" % objective)
@@ -276,6 +308,14 @@ class Z_optimizer():
                                      initial_pre_tanh_Z=initial_pre_tanh_Z, Z_mask=Z_mask, random_perturbations=random_Z_inits, device=self.device)
         assert (initial_LR is not None) or (existing_optimizer is not None), 'Should either supply optimizer from previous iterations or initial LR for new optimizer'
         self.image_mask = None if image_mask is None else torch.from_numpy(np.asarray(image_mask, dtype=np.float32)).to(self.device)
+        self.local_STD = objective.startswith('local_')
+        if self.local_STD:
+            # every 7 x 7 window inside the opened image mask (ReturnPatchExtractionMat with overlap 1, :391-398); no mask: the whole output
+            H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
+            self.patches = esr_local.PatchSet(image_mask, H, W)
+        if objective in PERIODICITY_OBJECTIVES:
+            H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
+            self.periodicity_pairs = [esr_local.ShiftPair(p, H, W, interpolated='nonInt' in objective) for p in data['periodicity_points']]
         if not self.model_training and 'fake_H' in model.__dict__:
             self.initial_output = model.Output_Batch(within_0_1=True).detach()
             # every sample's own initial STD (the reference's first_image_only flag is honoured by its 'local' objectives only,
@@ -313,6 +353,10 @@ class Z_optimizer():
         self.STD_PRESERVING_WEIGHT = 100 if 'TV' in objective else 20      # reference Z_optimization.py:508-509 (TV), :471 (others)
 
     def Masked_STD(self, first_image_only=False):
+        if self.local_STD:
+            # the STD of every selected 7 x 7 window [P, B] (reference :616-627); first_image_only: image 0 only, [P, 1]
+            x = self.model.fake_H[:1] if first_image_only else self.model.fake_H
+            return esr_local.patch_std(x, self.patches)
         # whole-image objectives: the STD of EVERY sample, [1, B], whatever the flag says (as the reference, see __init__)
         if self.model.fake_H.is_cuda:        # clamp, mask and the two moments in one pass over the batch (esr_img_stats)
             from esr_hip import zobj
@@ -399,6 +443,10 @@ class Z_optimizer():
                 Z_loss = (self.output_image - self.desired_im).abs().mean(dim=(1, 2, 3))
             elif 'VGG' in self.objective:
                 Z_loss = self.loss(self.model.netF(self.output_image), self.GT_HR_VGG).reshape(1)
+            elif 'periodicity' in self.objective:
+                # one STD-preserving scalar over the whole (local) batch and all patches, added to every sample (reference :799-815)
+                Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean() + \
+                    esr_local.shift_l1(self.model.fake_H, self.image_mask, self.periodicity_pairs)
             elif 'TV' in self.objective:
                 Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean(0) + \
                     (TV_Loss(self.model.fake_H, self.image_mask, clamp01=True) if not self.model_training else

@@ -440,6 +440,26 @@ int esr_img_stats(const float* x, int B, int C, int H, int W, const float* mask,
 int esr_img_stats_grad(const float* x, int B, int C, int H, int W, const float* mask, int clamp01, int kind, const float* coef, float* dx, int accumulate,
                        esr_stream_t stream);
 
+/* ---- local-STD and periodicity Z objectives (csrc/esr_local.hip; reference codes/Z_optimization.py:459-509, 616-627, 799-815) ----
+ * x: fp32 [B][C][H][W]; every kernel reads v = clamp(x, 0, 1) (channel mean for the patch STD).
+ * esr_patch_std: for every corner (cy, cx) of the uint8 map corners [H-6][W-6] that is nonzero, the 7 x 7 window with that top-left corner of
+ *   v = mean_c clamp(x_c, 0, 1): mean[b][cy][cx] and the unbiased std S[b][cy][cx]; unselected corners get 0.  H, W >= 7.
+ * esr_patch_std_grad: dx (+)= d/dx sum_p dS[p] S[p] with dS on the same [B][H-6][W-6] grid; the terms with S = 0 contribute 0 (not NaN).
+ * esr_shift_l1: one period point.  Separable bilinear samplers (grid_sample, zero padding) for the signs + (index 0) and - (index 1):
+ *   base_x / frac_x [2][nx] per output column, base_y / frac_y [2][ny] per output row, weights (1 - frac, frac) on (base, base + 1).
+ *   partial[b][i] = sum_{c,j} M(i,j) |GS+(v)(c,i,j) - GS-(v)(c,i,j)| (double), M = GS+(mask) GS-(mask), mask [H][W] (required).
+ * esr_shift_l1_grad: dx (+)= d/dx sum_b g[b] sum_{c,i,j} M |GS+ - GS-| through work [B][C][ny][nx] (scratch); ranges_x [2][W][2] and
+ *   ranges_y [2][H][2] are, per sign and source column / row, the half-open range of output columns / rows whose taps may touch it
+ *   (a superset is fine: the kernel checks every tap).  Deterministic (no atomics). */
+int esr_patch_std(const float* x, int B, int C, int H, int W, const uint8_t* corners, float* S, float* mean, esr_stream_t stream);
+int esr_patch_std_grad(const float* x, int B, int C, int H, int W, const uint8_t* corners, const float* S, const float* mean, const float* dS, float* dx,
+                       int accumulate, esr_stream_t stream);
+int esr_shift_l1(const float* x, int B, int C, int H, int W, const float* mask, int nx, int ny, const int32_t* base_x, const float* frac_x,
+                 const int32_t* base_y, const float* frac_y, double* partial, esr_stream_t stream);
+int esr_shift_l1_grad(const float* x, int B, int C, int H, int W, const float* mask, int nx, int ny, const int32_t* base_x, const float* frac_x,
+                      const int32_t* base_y, const float* frac_y, const int32_t* ranges_x, const int32_t* ranges_y, const float* g, float* work, float* dx,
+                      int accumulate, esr_stream_t stream);
+
 /* ---- the critic's glue: BatchNorm2d (training mode) + LeakyReLU, its gradient and the gradient of its gradient ----
  * Reference: Discriminator_VGG_128 (codes/models/modules/architecture.py:446-508): conv_block = nn.Conv2d -> nn.BatchNorm2d(affine, batch
  * statistics while training; block.py:25-35,129-146) -> LeakyReLU(0.2); the WGAN-GP penalty (codes/models/modules/loss.py:260-279)

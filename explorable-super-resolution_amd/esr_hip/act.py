@@ -2,6 +2,8 @@
 and packed conv weights.  PyTorch is only the allocator / stream provider here."""
 import ctypes as C
 import functools
+import itertools
+import math
 import threading
 
 import torch
@@ -843,18 +845,52 @@ def conv3x3_wgrad(dy, x_main, x_lat, lat, wshape, B, H, W, alpha, upsample, devi
     return dw, db
 
 
-_WGB = {}        # fallback cache for callers without an engine: {device index: [(descriptor bytes, workspace tensor, plan), ...]}
+class WgradTable:
+    """One descriptor array on the device for the batched weight-gradient launch (esr_conv3x3_wgrad_batch_upload; _part_upload when unit > 0:
+    the array is one PART of a larger set, every layer's pixel sum sliced as in the one-launch form — unit = wgrad_batch_unit of the whole set —
+    so the results are bit-identical to it).  The caller keeps every dy / x buffer alive and unmodified until a launch has run.  ptr: the
+    flat-buffer address the descriptors' dW / db pointers were built against (follow())."""
+
+    def __init__(self, descs, device, unit=0, ptr=0):
+        self.arr, self.unit, self.ptr, n = (_lib.WgradDesc * len(descs))(*descs), unit, ptr, len(descs)
+        need = _lib.lib.esr_conv3x3_wgrad_batch_part_workspace_bytes(self.arr, n, unit) if unit else _lib.lib.esr_conv3x3_wgrad_batch_workspace_bytes(self.arr, n)
+        check(min(need, 0), 'esr_conv3x3_wgrad_batch_workspace_bytes')
+        self.ws, self.plan = torch.empty(int(need), dtype=torch.uint8, device=device), _lib.WgradBatchPlan()
+        args = (self.arr, n, self.ws.data_ptr(), self.ws.numel(), C.byref(self.plan))
+        if unit:
+            check(_lib.lib.esr_conv3x3_wgrad_batch_part_upload(*args, unit, stream_ptr()), 'esr_conv3x3_wgrad_batch_part_upload')
+        else:
+            check(_lib.lib.esr_conv3x3_wgrad_batch_upload(*args, stream_ptr()), 'esr_conv3x3_wgrad_batch_upload')
+
+    def follow(self, ptr):
+        """The flat gradient buffer now lives at ptr: the table's dW / db pointers move with it, on the device (stream-ordered, no host copy) —
+        and only if it moved."""
+        if ptr != self.ptr:
+            check(_lib.lib.esr_conv3x3_wgrad_batch_rebase(self.ws.data_ptr(), C.byref(self.plan), ptr - self.ptr, stream_ptr()), 'esr_conv3x3_wgrad_batch_rebase')
+            self.ptr = ptr
+
+    def run(self):
+        check(_lib.lib.esr_conv3x3_wgrad_batch_run(self.ws.data_ptr(), C.byref(self.plan), stream_ptr()), 'esr_conv3x3_wgrad_batch_run')
+
+    def run_side(self, stream):
+        check(_lib.lib.esr_conv3x3_wgrad_batch_run_side(self.ws.data_ptr(), C.byref(self.plan), stream.cuda_stream), 'esr_conv3x3_wgrad_batch_run_side')
+
+    def emit(self, rec):
+        """The launch as a command of a recorded list, which keeps the workspace alive."""
+        rec.emit(_lib.OP_WGRAD_BATCH_RUN, _lib.CmdWgradBatchRun(self.ws.data_ptr(), self.plan))
+        rec.keep.append(self.ws)
+
+
+_WGB = {}        # fallback cache for callers without an engine: {device index: [(descriptor bytes, WgradTable), ...]}
 _WGB_KEEP = 4    # descriptor sets kept per cache (a dual pass / gradient accumulation alternates between a few)
 
 
 def conv3x3_wgrad_batch(descs, device, cache=None, unit=0):
-    """All recorded layers' weight gradients in one launch (esr_conv3x3_wgrad_batch_upload / _run).  The caller keeps every dy / x buffer
-    alive and unmodified until this returns (the launch is enqueued behind the kernels that produced them).  The descriptor table is
-    uploaded only when it differs from the ones already on the device: with pooled gradient buffers and the allocator handing back the same
-    dW storage, a steady-state training step re-runs a table that is already there (no host->device copy).  `cache`: the owner's dict (one
-    per engine, so that two models — or two streams — never share a table a launch in flight may still be reading); each distinct descriptor
-    set gets its OWN workspace, a small LRU of them is kept.  unit > 0: `descs` is one PART of a larger set launched part by part
-    (wgrad_batch_unit of the whole set: every layer's pixel sum is sliced as in the one-launch form, results bit-identical to it)."""
+    """All recorded layers' weight gradients in one launch (WgradTable).  The descriptor table is uploaded only when it differs from the ones
+    already on the device: with pooled gradient buffers and the allocator handing back the same dW storage, a steady-state training step re-runs
+    a table that is already there (no host->device copy).  `cache`: the owner's dict (one per engine, so that two models — or two streams —
+    never share a table a launch in flight may still be reading); each distinct descriptor set gets its OWN workspace, a small LRU of them is
+    kept.  unit: see WgradTable."""
     if not descs:
         return
     arr = (_lib.WgradDesc * len(descs))(*descs)
@@ -863,14 +899,13 @@ def conv3x3_wgrad_batch(descs, device, cache=None, unit=0):
     entries = (_WGB if cache is None else cache).setdefault(key, [])
     hit = next((e for e in entries if e[0] == raw), None)
     if hit is None:
-        ws, plan = wgrad_batch_upload(arr, device, unit)
-        hit = (raw, ws, plan)
+        hit = (raw, WgradTable(arr, device, unit))
         entries.insert(0, hit)
         del entries[_WGB_KEEP:]
     elif entries[0] is not hit:
         entries.remove(hit)
         entries.insert(0, hit)
-    check(_lib.lib.esr_conv3x3_wgrad_batch_run(hit[1].data_ptr(), C.byref(hit[2]), stream_ptr()), 'esr_conv3x3_wgrad_batch_run')
+    hit[1].run()
 
 
 def wgrad_batch_unit(descs):
@@ -881,18 +916,26 @@ def wgrad_batch_unit(descs):
     return int(unit)
 
 
-def wgrad_batch_upload(arr, device, unit=0):
-    """(workspace tensor, plan) of a descriptor array uploaded for esr_conv3x3_wgrad_batch_run; unit: see conv3x3_wgrad_batch."""
-    n = len(arr)
-    need = _lib.lib.esr_conv3x3_wgrad_batch_part_workspace_bytes(arr, n, unit) if unit else _lib.lib.esr_conv3x3_wgrad_batch_workspace_bytes(arr, n)
-    check(min(need, 0), 'esr_conv3x3_wgrad_batch_workspace_bytes')
-    ws = torch.empty(int(need), dtype=torch.uint8, device=device)
-    plan = _lib.WgradBatchPlan()
-    if unit:
-        check(_lib.lib.esr_conv3x3_wgrad_batch_part_upload(arr, n, ws.data_ptr(), ws.numel(), C.byref(plan), unit, stream_ptr()), 'esr_conv3x3_wgrad_batch_part_upload')
-    else:
-        check(_lib.lib.esr_conv3x3_wgrad_batch_upload(arr, n, ws.data_ptr(), ws.numel(), C.byref(plan), stream_ptr()), 'esr_conv3x3_wgrad_batch_upload')
-    return ws, plan
+class FlatGrads:
+    """The weight and bias gradients of a list of conv layers in ONE fp32 buffer, layer after layer: dW [cout][cin][kh][kw], then db [cout]."""
+
+    def __init__(self, wshapes, device):
+        self.wshapes, self.device = [tuple(s) for s in wshapes], device
+        self.sizes = [k for s in self.wshapes for k in (math.prod(s), s[0])]
+        ends = list(itertools.accumulate(self.sizes))
+        self.offsets, self.n = [0] + ends[1:-1:2], ends[-1]
+
+    def bounds(self):
+        """[(start, end)] of every layer in the buffer."""
+        return list(zip(self.offsets, self.offsets[1:] + [self.n]))
+
+    def zeros(self):
+        return torch.zeros(self.n, dtype=torch.float32, device=self.device)
+
+    def views(self, flat):
+        """[(dW, db)] of every layer: views of flat."""
+        parts = flat.split(self.sizes)
+        return [(parts[2 * k].view(s), parts[2 * k + 1]) for k, s in enumerate(self.wshapes)]
 
 
 _WS = {}

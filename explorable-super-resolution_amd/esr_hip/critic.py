@@ -138,7 +138,6 @@ class CriticEngine:
             raise EsrError('critic layout: a 3x3 first conv and the Linear classifier (num_2_strides = 5)')
         self._fp = None
         self._batch = A.PackBatch()
-        self._wgb = {}
         self._free_sets = {}
         self.set_precision(precision)
 
@@ -693,60 +692,38 @@ def _fwd_pass(eng, x, training, groups=1):
 
 
 class _WgradSet:
-    """The weight-gradient launch of one pass kind over one buffer set: descriptors built once; per call a fresh zeroed flat dW buffer, the
-    table re-pointed only if its address moved (engine.WGrad.rebind's scheme)."""
+    """The weight-gradient launch of one pass kind over one buffer set: descriptors built and uploaded once (A.WgradTable); per call a fresh
+    zeroed flat dW buffer (A.FlatGrads) that the table follows."""
 
     def __init__(self, eng, bs, pairs, b0=0, nb=None):
-        self.eng, self.pairs = eng, pairs
         nb = bs.B - b0 if nb is None else nb                       # the images the sum runs over: [b0, b0 + nb)
-        self.sizes = [L.cout * L.cin_e * 9 + L.cout for L, _, _ in pairs]
-        self.n = sum(self.sizes)
-        flat = torch.zeros(self.n, dtype=torch.float32, device=bs.dev)
-        descs, off = [], 0
-        for (L, dy, xin), n in zip(pairs, self.sizes):
-            nw = L.cout * L.cin_e * 9
+        self.layers = [L for L, _, _ in pairs]
+        self.layout = A.FlatGrads([(L.cout, L.cin_e, 3, 3) for L in self.layers], bs.dev)
+        self._first = self.layout.zeros()
+        descs = []
+        for (L, dy, xin), out in zip(pairs, self.layout.views(self._first)):
             vx, vdy, Bc, hc, wc = conv_io(xin, dy, nb, dy.shape[3] - 2, dy.shape[4] - 2, b0)     # (stacked maps: one tall image; their borders are zero)
-            d, _, _ = A.wgrad_desc(vdy, vx, None, 0, (L.cout, L.cin_e, 3, 3), Bc, hc, wc, 1.0, 1, bs.dev,
-                                   out=(flat[off:off + nw], flat[off + nw:off + n]), tap_masks=MASK_FWD if (L.strided and MASK_FWD) else None)
-            descs.append(d)
-            off += n
-        self.arr = (_lib.WgradDesc * len(descs))(*descs)
-        self.flat_ptr = flat.data_ptr()
-        need = _lib.lib.esr_conv3x3_wgrad_batch_workspace_bytes(self.arr, len(descs))
-        check(min(need, 0), 'esr_conv3x3_wgrad_batch_workspace_bytes')
-        self.ws = torch.empty(int(need), dtype=torch.uint8, device=bs.dev)
-        self.plan = None
-        self._first = flat
+            descs.append(A.wgrad_desc(vdy, vx, None, 0, (L.cout, L.cin_e, 3, 3), Bc, hc, wc, 1.0, 1, bs.dev, out=out,
+                                      tap_masks=MASK_FWD if (L.strided and MASK_FWD) else None)[0])
+        self.table = A.WgradTable(descs, bs.dev, ptr=self._first.data_ptr())
         # the embedded stride-2 layers' 4x4 gradients are gathered out of their 3x3 x 4 cin blocks by ONE index launch for all of them
-        idx, self.gather, off, g0 = [], {}, 0, 0
-        for (L, _, _), n in zip(pairs, self.sizes):
+        idx, self.gather, g0 = [], {}, 0
+        for L, off in zip(self.layers, self.layout.offsets):
             if L.strided:
                 idx.append(L.E_index + off)
                 self.gather[L.index] = (g0, g0 + L.E_index.numel())
                 g0 += L.E_index.numel()
-            off += n
         self.gather_idx = torch.cat(idx) if idx else None
 
     def run(self):
         """-> {layer index: (dW in the parameter's shape, db)}"""
-        flat, self._first = (self._first, None) if self._first is not None else (torch.zeros(self.n, dtype=torch.float32, device=self.ws.device), None)
-        delta = flat.data_ptr() - self.flat_ptr
-        if self.plan is None:
-            self.plan = _lib.WgradBatchPlan()
-            check(_lib.lib.esr_conv3x3_wgrad_batch_upload(self.arr, len(self.arr), self.ws.data_ptr(), self.ws.numel(), C.byref(self.plan), A.stream_ptr()),
-                  'esr_conv3x3_wgrad_batch_upload')
-        elif delta:            # a new flat buffer: move the table's dW / db pointers on the device (no host copy)
-            check(_lib.lib.esr_conv3x3_wgrad_batch_rebase(self.ws.data_ptr(), C.byref(self.plan), delta, A.stream_ptr()), 'esr_conv3x3_wgrad_batch_rebase')
-            self.flat_ptr += delta
-        check(_lib.lib.esr_conv3x3_wgrad_batch_run(self.ws.data_ptr(), C.byref(self.plan), A.stream_ptr()), 'esr_conv3x3_wgrad_batch_run')
-        out, off = {}, 0
+        flat, self._first = (self._first, None) if self._first is not None else (self.layout.zeros(), None)
+        self.table.follow(flat.data_ptr())
+        self.table.run()
+        out = {}
         picked = flat[self.gather_idx] if self.gather_idx is not None else None
-        for (L, _, _), n in zip(self.pairs, self.sizes):
-            nw = L.cout * L.cin_e * 9
-            dw, db = flat[off:off + nw], flat[off + nw:off + n]
-            dw = picked[self.gather[L.index][0]:self.gather[L.index][1]].view(L.cout, L.cin, 4, 4) if L.strided else dw.view(L.cout, L.cin_e, 3, 3)
-            out[L.index] = (dw, db)
-            off += n
+        for L, (dw, db) in zip(self.layers, self.layout.views(flat)):
+            out[L.index] = (picked[self.gather[L.index][0]:self.gather[L.index][1]].view(L.cout, L.cin, 4, 4) if L.strided else dw, db)
         return out
 
 

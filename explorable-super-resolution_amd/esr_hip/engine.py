@@ -803,9 +803,52 @@ def _side_kernel_capped(f16):
     return _SIDE_CAPPED[f16]
 
 
+def cover_spans(spans, n):
+    """[lo, hi) runs of a buffer of n elements, stretched over the gaps between them: each from where the one before it (in buffer order) ends
+    to its own end, the first from 0, the last to n.  Disjoint runs come out disjoint and covering [0, n) exactly (no torch, no GPU)."""
+    order = sorted(range(len(spans)), key=lambda g: spans[g][0])
+    out = [None] * len(spans)
+    for k, g in enumerate(order):
+        out[g] = (spans[order[k - 1]][1] if k else 0, spans[g][1] if k + 1 < len(order) else n)
+    return out
+
+
+def wgrad_groups(layers, desc_layer, ready, bucket_bytes=None, overlap=0):
+    """The weight-gradient launches of one backward pass: [(flat lo, flat hi, [descriptor indices], on the second stream?, position)].
+    layers: (start, end) of every layer in the flat gradient buffer, in its order; desc_layer: the layer of each recorded descriptor; ready: the
+    launch-list position at which each was recorded.  [lo, hi) is the group's stretch of the buffer (what an exchange hands on); position: where
+    a second-stream group is enqueued (None: behind the pass, on the main stream).
+      * overlap (RRDBEngine.wgrad_overlap, where the two-stream form applies: G, or the groups' shares of the layers): groups in readiness
+        order, all but the last on the second stream, each behind the launch that wrote its last dy (= where the next layer was recorded);
+      * else bucket_bytes (an exchange attached): one group per gradient bucket, contiguous runs of layers of about bucket_bytes each in the
+        buffer's order — also where the readiness groups' stretches of the buffer would overlap (an exotic layer order);
+      * else ONE group."""
+    n, nd = layers[-1][1], len(desc_layer)
+    if overlap:
+        fr = overlap if isinstance(overlap, (tuple, list)) else None
+        G = len(fr) if fr else int(overlap)
+        cut = [nd * g // G for g in range(G + 1)] if not fr else [0] + [min(nd, int(round(nd * sum(fr[:g + 1]) / sum(fr)))) for g in range(G)]
+        idx = [list(range(cut[g], cut[g + 1])) for g in range(G)]
+        # the backward meets the layers in (roughly) the reverse of the buffer's order, so a group is a contiguous run of it
+        spans = [(min(layers[desc_layer[i]][0] for i in ix), max(layers[desc_layer[i]][1] for i in ix)) for ix in idx]
+        s = sorted(spans)
+        if bucket_bytes is None or all(a[1] <= b[0] for a, b in zip(s, s[1:])):
+            return [(lo, hi, ix, g + 1 < G, ready[cut[g + 1]] if g + 1 < G else None) for g, ((lo, hi), ix) in enumerate(zip(cover_spans(spans, n), idx))]
+    if bucket_bytes is None:
+        return [(0, n, list(range(nd)), False, None)]
+    runs, k0 = [], 0
+    for k, (start, end) in enumerate(layers):             # bucket boundaries at layer boundaries of the flat layout
+        if (end - layers[k0][0]) * 4 >= bucket_bytes or k + 1 == len(layers):
+            ix = [i for i, l in enumerate(desc_layer) if k0 <= l <= k]
+            if ix:
+                runs.append(((layers[k0][0], end), ix))
+            k0 = k + 1
+    return [(lo, hi, ix, False, None) for (lo, hi), (_, ix) in zip(cover_spans([r for r, _ in runs], n), runs)]
+
+
 class WGrad:
     """Weight / bias gradient collection.  Layers are only RECORDED while the data-gradient pass walks the network; result() runs
-    them all in one batched launch (esr_conv3x3_wgrad_batch), which is why every gradient / activation buffer a record refers to
+    them all in batched launches (A.WgradTable, grouped by wgrad_groups), which is why every gradient / activation buffer a record refers to
     is kept alive here until then."""
 
     def __init__(self, engine, enabled, B, hi_only=False):
@@ -816,37 +859,36 @@ class WGrad:
         self.hi_only, self.gscale = hi_only, None
         self.scaled = []              # (flat offset, length, gscale)
         self.grads = {} if enabled else None
-        self.mods = {name: c for name, c, _ in engine._convs()} if enabled else None
-        self.lats = {name: lat for name, _, lat in engine._convs()} if enabled else None
-        self.descs, self.keep, self.permuted, self.desc_off, self.ready = [], [], [], [], []
+        self.descs, self.keep, self.permuted, self.desc_layer, self.ready = [], [], [], [], []
+        # ex: the exchange this pass's launches hand their buckets to (decided by result(), kept for the replays); tables: a recorded pass's
+        # uploaded descriptor tables, one per group
+        self.ex, self.tables, self._cur_flat = None, [], None
         if enabled:
+            convs = engine._convs()
+            self.convs = {name: (k, c, lat) for k, (name, c, lat) in enumerate(convs)}
+            self.params = [(c.weight, c.bias) for _, c, _ in convs]
+            self.layout = A.FlatGrads([c.weight.shape for _, c, _ in convs], convs[0][1].weight.device)
             # one zeroed flat buffer per backward pass, handed out as views (a fresh one every time: the views become .grad tensors)
-            self.offsets, n = {}, 0
-            for name, c in self.mods.items():
-                self.offsets[name] = n
-                n += c.weight.numel() + c.weight.shape[0]
-            self.flat = torch.zeros(n, dtype=torch.float32, device=next(iter(self.mods.values())).weight.device)
-            self._sizes = [k for c in self.mods.values() for k in (c.weight.numel(), c.weight.shape[0])]
-            self._params = [(c.weight, c.bias) for c in self.mods.values()]
+            self.flat = self.layout.zeros()
+            self.views = self.layout.views(self.flat)
 
     def conv(self, name, dy, x_main, x_lat, H, W, alpha=1.0, upsample=1, keep=(), rows=None):
         """rows: dy's channels are a permutation of the layer's output channels (pixel-shuffle convs): dy channel i is output channel rows[i]."""
         if not self.enabled:
             return
-        c = self.mods[name]
+        k, c, lat = self.convs[name]
         if self.hi_only:
             dy, x_main, x_lat = A.hi_plane(dy), A.hi_plane(x_main), A.hi_plane(x_lat)
-        o, nw = self.offsets[name], c.weight.numel()
-        out = (self.flat[o:o + nw].view(c.weight.shape), self.flat[o + nw:o + nw + c.weight.shape[0]])
+        out = self.views[k]
         if rows is not None:       # accumulate in dy's channel order, un-permute after the launch (result())
             tmp = (torch.zeros_like(out[0]), torch.zeros_like(out[1]))
             self.permuted.append((tmp, out, torch.tensor(rows, dtype=torch.long, device=out[0].device)))
             final, out = out, tmp
         if self.gscale is not None:
-            self.scaled.append((o, nw + c.weight.shape[0], self.gscale))
-        d, dw, db = A.wgrad_desc(dy, x_main, x_lat, self.lats[name], c.weight.shape, self.B, H, W, alpha, upsample, c.weight.device, out=out)
+            self.scaled.append((self.layout.offsets[k], c.weight.numel() + c.weight.shape[0], self.gscale))
+        d, dw, db = A.wgrad_desc(dy, x_main, x_lat, lat, c.weight.shape, self.B, H, W, alpha, upsample, c.weight.device, out=out)
         self.descs.append(d)
-        self.desc_off.append(o)
+        self.desc_layer.append(k)
         rec = A._rec()
         self.ready.append(rec.position() if rec is not None else None)      # (the launch that wrote dy is already in the list)
         self.keep.extend(keep)
@@ -858,194 +900,128 @@ class WGrad:
         else:
             self.keep.append(db)
 
-    def _groups(self):
-        """[(flat start, flat end, [indices into self.descs])]: ONE group normally; with an exchange attached (engine.wgrad_exchange) one per
-        gradient bucket — contiguous runs of layers, in the flat buffer's order, of about exchange.bucket_bytes each."""
-        ex = self.engine.wgrad_exchange
-        n = self.flat.numel() if self.flat is not None else self._n
-        if ex is None or self.permuted or self.scaled:
-            return [(0, n, list(range(len(self.descs))))]
-        names = list(self.mods)
-        bounds, start = [], 0
-        for k, name in enumerate(names):                  # bucket boundaries at layer boundaries of the flat layout
-            end = self.offsets[names[k + 1]] if k + 1 < len(names) else n
-            if (end - start) * 4 >= ex.bucket_bytes or k + 1 == len(names):
-                bounds.append((start, end))
-                start = end
-        groups = []
-        for o0, o1 in bounds:
-            idx = [i for i, o in enumerate(self.desc_off) if o0 <= o < o1]
-            if idx:
-                groups.append((o0, o1, idx))
-        # every element of the flat buffer belongs to exactly one bucket: stretch the groups over the gaps of layers without a recorded gradient
-        for k in range(len(groups)):
-            lo = 0 if k == 0 else groups[k - 1][1]
-            hi = n if k + 1 == len(groups) else groups[k][1]
-            groups[k] = (lo, hi, groups[k][2])
-        return groups or [(0, n, [])]
+    def _groups(self, recorded):
+        """wgrad_groups of this pass: the two-stream form (engine.wgrad_overlap) only for a recorded pass of one-plane gradients that are
+        neither permuted nor rescaled, with at least 4 layers per group, and a build whose side kernel holds its CU alone."""
+        eng = self.engine
+        ov = eng.wgrad_overlap if recorded else 0
+        G = len(ov) if isinstance(ov, (tuple, list)) else int(ov or 0)
+        if G < 2 or self.permuted or self.scaled or len(self.descs) < 4 * G or eng._bwd_split is True \
+                or not _side_kernel_capped(eng._bwd_split in ('mixed', 'f16')):
+            ov = 0
+        return wgrad_groups(self.layout.bounds(), self.desc_layer, self.ready, self.ex.bucket_bytes if self.ex is not None else None, ov)
 
     def result(self):
-        if self.enabled and self.descs:
-            rec = A._rec()
-            dev = self.flat.device
-            groups = self._groups()
-            # several launches slice every layer's pixel sum exactly as the one launch over all layers would (bit-identical gradients)
-            unit = A.wgrad_batch_unit(self.descs) if len(groups) > 1 else 0
-            # (pixel-shuffle layers' gradients are un-permuted after the launch, 'mixed' gradients are still multiplied by this RANK's power-of-two
-            # scales until the loop at the end of this function: both are exchanged by the caller, after the backward — summing scaled buffers
-            # across ranks and dividing by the local scale would give every rank different, wrong gradients)
-            ex = None if (self.permuted or self.scaled) else self.engine.wgrad_exchange
-            if rec is not None:
-                # recorded pass: the descriptor tables go to the device now, their launches into the list; rebind() serves the replays
-                self._flat_ptr = self.flat.data_ptr()
-                self._cur_flat = self.flat if ex is not None else None      # (only an exchange slices it; without one nothing here outlives the step)
-                self._tables = []                 # [(descriptor array, workspace, plan)] one per group
-                if self._overlap_groups(rec, dev):
-                    rec.keep.extend(self.keep)
-                    self._n, self._dev = self.flat.numel(), dev
-                    grads, self.descs, self.keep, self.flat, self.grads, self.ready = self.grads, [], [], None, None, []
-                    return grads
-                for gi, (o0, o1, idx) in enumerate(groups):
-                    if idx:
-                        arr = (_lib.WgradDesc * len(idx))(*[self.descs[i] for i in idx])
-                        ws, plan = A.wgrad_batch_upload(arr, dev, unit)
-                        self._tables.append((arr, ws, plan))
-                        rec.emit(_lib.OP_WGRAD_BATCH_RUN, _lib.CmdWgradBatchRun(ws.data_ptr(), plan))
-                        rec.keep.append(ws)
-                    if ex is not None:            # replayed between two segments of the list: the bucket of the launch just enqueued
-                        A.host_op(lambda ctx, wg=self, gi=gi, o0=o0, o1=o1, last=(gi + 1 == len(groups)): wg._exchange(gi, o0, o1, last))
-                rec.keep.extend(self.keep)
-                assert not self.permuted and not self.scaled
-                self._n, self._dev = self.flat.numel(), dev
-                grads, self.descs, self.keep, self.flat, self.grads = self.grads, [], [], None, None      # hold no reference to a step's gradients
-                return grads
-            self._cur_flat = self.flat if ex is not None else None
-            for gi, (o0, o1, idx) in enumerate(groups):
-                if idx:
-                    A.conv3x3_wgrad_batch([self.descs[i] for i in idx], dev, cache=self.engine._wgb, unit=unit)
-                if ex is not None:
-                    self._exchange(gi, o0, o1, gi + 1 == len(groups))
-            for (tdw, tdb), (dw, db), rows in self.permuted:
-                dw.index_copy_(0, rows, tdw)
-                db.index_copy_(0, rows, tdb)
-            # undo the gradient scaling: consecutive layers recorded under the same scale are contiguous in `flat` more often than not
-            runs = []
-            for o, n, g in sorted(self.scaled, key=lambda t: t[0]):
-                if runs and runs[-1][2] is g and runs[-1][0] + runs[-1][1] == o:
-                    runs[-1][1] += n
-                else:
-                    runs.append([o, n, g])
-            for o, n, g in runs:
-                self.flat[o:o + n].div_(g)
-            self.descs, self.keep = [], []
+        if not (self.enabled and self.descs):
+            return self.grads
+        rec, dev = A._rec(), self.flat.device
+        # (pixel-shuffle layers' gradients are un-permuted after the launch, 'mixed' gradients are still multiplied by this RANK's power-of-two
+        # scales until the loop at the end of this function: both are exchanged by the caller, after the backward — summing scaled buffers
+        # across ranks and dividing by the local scale would give every rank different, wrong gradients)
+        fixed_up = bool(self.permuted or self.scaled)
+        if rec is not None and fixed_up:
+            raise EsrError('a recorded backward pass cannot un-permute or rescale weight gradients (pixel-shuffle / mixed passes launch directly)')
+        self.ex = None if fixed_up else self.engine.wgrad_exchange
+        groups = self._groups(rec is not None)
+        # several launches slice every layer's pixel sum exactly as the one launch over all layers would (bit-identical gradients)
+        unit = A.wgrad_batch_unit(self.descs) if len(groups) > 1 else 0
+        self._cur_flat = self.flat if self.ex is not None else None      # (only an exchange slices it; without one nothing here outlives the step)
+        if rec is not None:
+            # recorded pass: the descriptor tables go to the device now, their launches into the list; rebind() serves the replays
+            self.tables = [A.WgradTable([self.descs[i] for i in idx], dev, unit, self.flat.data_ptr()) for _, _, idx, _, _ in groups]
+            self._record(rec, groups)
+            rec.keep.extend(self.keep)
+            grads, self.descs, self.keep, self.flat, self.views, self.grads, self.ready = self.grads, [], [], None, None, None, []   # hold no reference to a step's gradients
+            return grads
+        for gi, (lo, hi, idx, _, _) in enumerate(groups):
+            A.conv3x3_wgrad_batch([self.descs[i] for i in idx], dev, cache=self.engine._wgb, unit=unit)
+            self._exchange(gi, lo, hi, gi + 1 == len(groups))
+        for (tdw, tdb), (dw, db), rows in self.permuted:
+            dw.index_copy_(0, rows, tdw)
+            db.index_copy_(0, rows, tdb)
+        # undo the gradient scaling: consecutive layers recorded under the same scale are contiguous in `flat` more often than not
+        runs = []
+        for o, n, g in sorted(self.scaled, key=lambda t: t[0]):
+            if runs and runs[-1][2] is g and runs[-1][0] + runs[-1][1] == o:
+                runs[-1][1] += n
+            else:
+                runs.append([o, n, g])
+        for o, n, g in runs:
+            self.flat[o:o + n].div_(g)
+        self.descs, self.keep = [], []
         return self.grads
 
-    def _overlap_groups(self, rec, dev):
-        """engine.wgrad_overlap: the recorded launches as groups in readiness order — all but the last on the engine's second stream, each
-        enqueued (a host step of the list) right behind the main-stream launch that completed its last dy; the last group and the join at the
-        end of the list.  With an exchange attached (engine.wgrad_exchange) the groups are its buckets: each group's stretch of the flat buffer
-        is handed to exchange.start() behind an event recorded after its own launch — the collective waits for that launch only and runs under
-        everything that follows — and exchange.finish() comes behind the join.  False: not applicable here (permuted / rescaled gradients, too few layers, hi+lo
-        gradients)."""
-        eng = self.engine
-        fr = eng.wgrad_overlap if isinstance(eng.wgrad_overlap, (tuple, list)) else None      # (experiments: the groups' shares of the layers)
-        G = len(fr) if fr else int(eng.wgrad_overlap or 0)
-        if G < 2 or self.permuted or self.scaled or len(self.descs) < 4 * G or eng._bwd_split is True:
-            return False
-        if not _side_kernel_capped(eng._bwd_split in ('mixed', 'f16')):
-            return False                               # (this build's side instantiation is not one workgroup per CU: the one-stream backward)
-        if eng._side is None:
-            eng._side = torch.cuda.Stream(device=dev)
-        side, ex = eng._side, eng.wgrad_exchange
-        unit = A.wgrad_batch_unit(self.descs)          # every group slices its layers' pixel sums as the one launch would
-        n = len(self.descs)
-        bounds = [n * g // G for g in range(G + 1)] if not fr else [0] + [min(n, int(round(n * sum(fr[:g + 1]) / sum(fr)))) for g in range(G)]
-        # the groups' stretches of the flat buffer: the backward meets the layers in (roughly) the reverse of the buffer's order, so a group is
-        # a contiguous run of it; the runs are stretched over layers without a recorded gradient so that every element belongs to one group
-        names = list(self.mods)
-        ends = {self.offsets[nm]: (self.offsets[names[k + 1]] if k + 1 < len(names) else self.flat.numel()) for k, nm in enumerate(names)}
-        spans = [(min(self.desc_off[i] for i in range(bounds[g], bounds[g + 1])), max(ends[self.desc_off[i]] for i in range(bounds[g], bounds[g + 1]))) for g in range(G)]
-        order = sorted(range(G), key=lambda g: spans[g][0])
-        disjoint = all(spans[order[k]][1] <= spans[order[k + 1]][0] for k in range(G - 1))
-        if ex is not None and not disjoint:
-            return False                               # (an exotic layer order: the bucketed launches of result() serve the exchange)
-        cover = {}
-        for k, g in enumerate(order):
-            cover[g] = (0 if k == 0 else spans[order[k - 1]][1], self.flat.numel() if k + 1 == G else spans[g][1])
+    def _record(self, rec, groups):
+        """The launches of a recorded pass.  One stream: the groups' launches behind the pass, each followed (exchange attached) by a host step
+        that hands its bucket on.  Two streams (engine.wgrad_overlap): every second-stream group enqueued by a host step at its position, the
+        last group and the join at the end of the list; with an exchange attached each second-stream group's stretch of the flat buffer is
+        handed to exchange.start() behind an event recorded after its own launch — the collective waits for that launch only and runs under
+        everything that follows — and exchange.finish() comes behind the join."""
+        eng, G = self.engine, len(groups)
+        if not groups[0][3]:
+            for gi, (t, (lo, hi, _, _, _)) in enumerate(zip(self.tables, groups)):
+                t.emit(rec)
+                if self.ex is not None:           # replayed between two segments of the list: the bucket of the launch just enqueued
+                    rec.host(lambda ctx, gi=gi, lo=lo, hi=hi: self._exchange(gi, lo, hi, gi + 1 == G))
+            return
+        side, done, hooks = eng._side, {}, []
+        if side is None:
+            side = eng._side = torch.cuda.Stream(device=self.tables[0].ws.device)
+        for g, (t, (_, _, _, on_side, pos)) in enumerate(zip(self.tables, groups)):
+            if not on_side:
+                t.emit(rec)
+                continue
 
-        def exchange(g, last=False):
-            if ex is not None and self._cur_flat is not None:
-                ex.start(g, self._cur_flat[cover[g][0]:cover[g][1]])
-                if last:
-                    ex.finish()
-                    self._cur_flat = None
-        hooks, done = [], {}
-        for g in range(G):
-            idx = range(bounds[g], bounds[g + 1])
-            arr = (_lib.WgradDesc * len(idx))(*[self.descs[i] for i in idx])
-            ws, plan = A.wgrad_batch_upload(arr, dev, unit)
-            self._tables.append((arr, ws, plan))
-            rec.keep.append(ws)
-            if g + 1 < G:
-                def launch(ctx, ws=ws, plan=plan, g=g):
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    side.wait_event(ev)
-                    _lib.check(_lib.lib.esr_conv3x3_wgrad_batch_run_side(ws.data_ptr(), C.byref(plan), side.cuda_stream), 'esr_conv3x3_wgrad_batch_run_side')
-                    if ex is not None:
-                        done[g] = torch.cuda.Event()
-                        done[g].record(side)
-                # behind the launch that wrote the group's last dy = where the NEXT layer was recorded
-                hooks.append((self.ready[bounds[g + 1]], launch))
-            else:
-                rec.emit(_lib.OP_WGRAD_BATCH_RUN, _lib.CmdWgradBatchRun(ws.data_ptr(), plan))
+            def launch(ctx, t=t, g=g):
+                ev = torch.cuda.Event()
+                ev.record()
+                side.wait_event(ev)
+                t.run_side(side)
+                if self.ex is not None:
+                    done[g] = torch.cuda.Event()
+                    done[g].record(side)
+            hooks.append((pos, launch))
 
         def join(ctx):
             # The collectives are issued HERE, when the host has enqueued the whole pass (it runs milliseconds ahead of the GPU), not between the
             # segments of the chain: a collective call may block the host until the stream it waits for has caught up (a one-rank RCCL group does:
             # 2.0-2.7 ms per call with the group's launch still running — profiles/r05_c3_exchange_ab.log), and the chain's 12 us launches must
             # not wait for the host.  Each one still waits only for its own group's launch (the event recorded behind it on the second stream).
-            if ex is not None:
+            if self.ex is not None:
                 if eng._xs is None:
-                    eng._xs = torch.cuda.Stream(device=dev)
+                    eng._xs = torch.cuda.Stream(device=side.device)
                 for g in range(G - 1):
                     eng._xs.wait_event(done.pop(g))
                     with torch.cuda.stream(eng._xs):
-                        exchange(g)
+                        self._exchange(g, groups[g][0], groups[g][1], False)
             torch.cuda.current_stream().wait_stream(side)
-            exchange(G - 1, last=True)
+            self._exchange(G - 1, groups[-1][0], groups[-1][1], True)
         rec.host(join)
         for pos, fn in reversed(hooks):                # (positions grow with the layer order: last first)
             rec.insert_host(pos, fn)
-        return True
 
-    def _exchange(self, gi, o0, o1, last):
-        ex = self.engine.wgrad_exchange
-        if ex is None or self._cur_flat is None:
+    def _exchange(self, gi, lo, hi, last):
+        if self.ex is None or self._cur_flat is None:
             return
-        ex.start(gi, self._cur_flat[o0:o1])
+        self.ex.start(gi, self._cur_flat[lo:hi])
         if last:
-            ex.finish()
+            self.ex.finish()
             self._cur_flat = None
 
     def rebind(self):
-        """Replay of a recorded pass: a fresh zeroed flat buffer (its views become the parameters' .grad), the descriptor table re-pointed
-        (and re-uploaded) only if the allocator did not hand back the same storage.  Returns {param: grad}."""
+        """Replay of a recorded pass: a fresh zeroed flat buffer (its views become the parameters' .grad), the descriptor tables re-pointed only
+        if the allocator did not hand back the same storage.  Returns {param: grad}."""
         if not self.enabled:
             return None
-        flat = torch.zeros(self._n, dtype=torch.float32, device=self._dev)
-        # what the recorded exchange hooks slice (WGrad._exchange) — and only then: a plan that kept the previous step's 67 MB buffer alive would
+        flat = self.layout.zeros()
+        # what the recorded exchange hooks slice (_exchange) — and only then: a plan that kept the previous step's 67 MB buffer alive would
         # keep the allocator from handing the same block back, i.e. re-base every table every step
-        self._cur_flat = flat if self.engine.wgrad_exchange is not None else None
-        delta = flat.data_ptr() - self._flat_ptr
-        if delta:             # the tables' dW / db pointers move with the buffer: patched on the device (no host copy, stream-ordered)
-            for arr, ws, plan in self._tables:
-                _lib.check(_lib.lib.esr_conv3x3_wgrad_batch_rebase(ws.data_ptr(), C.byref(plan), delta, A.stream_ptr()), 'esr_conv3x3_wgrad_batch_rebase')
-            self._flat_ptr += delta
-        parts = flat.split(self._sizes)
+        self._cur_flat = flat if self.ex is not None else None
+        for t in self.tables:
+            t.follow(flat.data_ptr())
         grads = {}
-        for i, (w, b) in enumerate(self._params):
-            grads[w] = parts[2 * i].view(w.shape)
+        for (w, b), (dw, db) in zip(self.params, self.layout.views(flat)):
+            grads[w] = dw
             if b is not None:
-                grads[b] = parts[2 * i + 1]
+                grads[b] = db
         return grads

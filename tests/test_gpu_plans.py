@@ -4,6 +4,7 @@ code itself), across replays with NEW input / output tensors (the patched pointe
 import ctypes as C
 import os
 import sys
+import weakref
 
 import pytest
 import torch
@@ -95,6 +96,45 @@ def test_weight_gradients_under_the_data_gradient_chain_are_bit_identical(groups
     for (dx0, dw0, t0), (dx1, dw1, t1) in zip(ref, got):
         assert torch.equal(dx0, dx1) and torch.equal(t0, t1)
         assert all(torch.equal(a, b) for a, b in zip(dw0, dw1))
+
+
+@pytest.mark.parametrize('groups', [0, 3])
+def test_steady_state_replay_reuses_the_weight_gradient_tables(groups):
+    """A replayed backward runs the descriptor tables uploaded when it was recorded: no upload at all, at most one rebase per table (only when
+    the allocator moved the flat gradient buffer); and with no exchange attached nothing keeps the previous step's flat buffer alive."""
+    from esr_hip import _lib
+    net = make_net(nb=2, precision='bf16')
+    net.engine.wgrad_overlap = groups
+
+    def step(i):
+        x = inputs(2, 3, 4, 16, 20, 200 + i).requires_grad_(True)
+        for p in net.parameters():
+            p.grad = None
+        y = net(x)
+        (y * seeded_uniform(tuple(y.shape), 210 + i).cuda()).sum().backward()
+    step(0)                                          # records
+    (_, wg), = [v for b in net.engine._bufs.values() for k, v in b['_plans'].items() if k[0] == 'bwd']
+    assert len(wg.tables) == max(groups, 1)
+    made = []
+
+    def zeros(real=wg.layout.zeros):                 # every flat buffer the replays allocate, by weak reference
+        t = real()
+        made.append(weakref.ref(t))
+        return t
+    wg.layout.zeros = zeros
+    names = ('esr_conv3x3_wgrad_batch_upload', 'esr_conv3x3_wgrad_batch_part_upload', 'esr_conv3x3_wgrad_batch_rebase')
+    calls = dict.fromkeys(names, 0)
+    step(1)                                          # replays
+    try:
+        for n in names:
+            setattr(_lib.lib, n, (lambda n, real: lambda *a: (calls.__setitem__(n, calls[n] + 1), real(*a))[1])(n, getattr(_lib.lib, n)))
+        step(2)                                      # steady state
+    finally:
+        for n in names:
+            _lib.lib.__dict__.pop(n, None)
+    torch.cuda.synchronize()
+    assert calls[names[0]] == calls[names[1]] == 0 and calls[names[2]] <= len(wg.tables), calls
+    assert len(made) == 2 and made[0]() is None      # (step 2 dropped the .grad views of step 1: nothing else held their buffer)
 
 
 def test_replay_follows_weight_updates_and_gradient_accumulation():

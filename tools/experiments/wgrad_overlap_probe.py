@@ -67,7 +67,7 @@ eng = net.engine
 entry = [v for bufs in eng._bufs.values() for k, v in bufs['_plans'].items() if isinstance(v, tuple)]
 assert len(entry) == 1, len(entry)
 plan, wg = entry[0]
-tables = wg._tables
+tables = wg.tables
 dummy = torch.zeros(64, dtype=torch.uint8, device=dev)
 found = []
 for item in plan.items:
@@ -91,8 +91,8 @@ print('  without the weight-gradient launch:       %.2f ms' % timed())
 # (2) the launch on the side stream, enqueued when the backward starts (previous step's tables)
 def side_launch():
     side.wait_stream(torch.cuda.current_stream())
-    for arr, ws, p in tables:
-        _lib.check(_lib.lib.esr_conv3x3_wgrad_batch_run(ws.data_ptr(), C.byref(p), side.cuda_stream), 'esr_conv3x3_wgrad_batch_run')
+    for t in tables:
+        _lib.check(_lib.lib.esr_conv3x3_wgrad_batch_run(t.ws.data_ptr(), C.byref(t.plan), side.cuda_stream), 'esr_conv3x3_wgrad_batch_run')
 
 
 hook[0] = side_launch
@@ -103,8 +103,8 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 with torch.cuda.stream(side):
     e0.record()
     for _ in range(5):
-        for arr, ws, p in tables:
-            _lib.lib.esr_conv3x3_wgrad_batch_run(ws.data_ptr(), C.byref(p), side.cuda_stream)
+        for t in tables:
+            _lib.lib.esr_conv3x3_wgrad_batch_run(t.ws.data_ptr(), C.byref(t.plan), side.cuda_stream)
     e1.record()
 torch.cuda.synchronize()
 print('  the weight-gradient launch alone:         %.2f ms' % (e0.elapsed_time(e1) / 5))

@@ -597,7 +597,6 @@ class PackedSum:
 
 _launch_parity = 0
 LDS_STAGES = 0              # esr_conv3x3_desc.lds_stages of every launch built here: 0 = the library picks by launch size, 1 / 2 = that form
-ALTERNATE_ORDER = True        # module attribute (experiments may clear it): consecutive launches walk the tile space in opposite directions
 
 
 def reset_launch_parity():
@@ -662,7 +661,7 @@ def conv3x3(pc, in1, B, H, W, cout, in0=None, upsample=1, act_slope=1.0, alpha=1
     # consecutive launches alternate the direction in which they walk the images (cache-reuse hint, see esr_conv3x3_desc)
     global _launch_parity
     if reverse is None:
-        reverse = bool(_launch_parity & 1) and ALTERNATE_ORDER
+        reverse = bool(_launch_parity & 1)
         _launch_parity += 1
     d.reverse_order = 1 if reverse else 0
     d.lds_stages = LDS_STAGES

@@ -17,13 +17,6 @@ def _prep(x, what):
 
 
 USE_SEPARABLE = True          # module attribute: the tests compare the separable kernels with the 2-D ones by clearing it
-# project(): batches whose generator output exceeds PROJECT_CHUNK_BYTES run the three kernels per chunk of this many images (0: never).
-# OFF by default — measured on MI355X at configs[1] (tools/experiments/cem_time.py, profiles/r04_cem_chunk{0,8}_pmc.json): the whole batch
-# 0.225 ms, chunks of 16 / 8 / 4 images 0.267 / 0.283 / 0.370 ms, and the counters see the same 0.64 GB per projection either way (FETCH_SIZE
-# counts L2 misses; what the Infinity Cache absorbs is invisible to it) — four times the launches of kernels that are 30-100 us each cost more
-# than the second reading of `g` from HBM.  Kept as a switch (results are bit-identical, tests/test_gpu_parity.py).
-PROJECT_CHUNK_IMAGES = 0
-PROJECT_CHUNK_BYTES = 64 << 20
 
 
 def _taps_entry(t, dev):
@@ -106,14 +99,12 @@ def lr_filter_raw(x, taps):
     return out
 
 
-def upscale_raw(f, taps, sf, pre, f2=None, g=None, crop=0, mode=0, rng=0.0, out=None):
+def upscale_raw(f, taps, sf, pre, f2=None, g=None, crop=0, mode=0, rng=0.0):
     f = _prep(f, 'LR image')
     sep, taps = _sep(taps, f.device), _taps(taps, f.device)
     B, Cc, h, w = f.shape
     Ho, Wo = sf * h - 2 * crop, sf * w - 2 * crop
-    if out is None:
-        out = torch.empty(B, Cc, Ho, Wo, dtype=torch.float32, device=f.device)
-    assert out.shape == (B, Cc, Ho, Wo) and out.dtype == torch.float32 and out.is_contiguous()
+    out = torch.empty(B, Cc, Ho, Wo, dtype=torch.float32, device=f.device)
     out2 = torch.empty_like(out) if mode == 3 else None
     if f2 is not None:
         f2 = _prep(f2, 'LR image')
@@ -141,7 +132,7 @@ FUSE_FILTER_UPSCALE = None
 FOLD_MAX_TILES = 512
 
 
-def filter_upscale_raw(e, taps_inv, taps_up, sf, pre, e2=None, g=None, crop=0, mode=0, rng=0.0, out=None):
+def filter_upscale_raw(e, taps_inv, taps_up, sf, pre, e2=None, g=None, crop=0, mode=0, rng=0.0):
     """upscale_raw(lr_filter_raw(e, taps_inv), taps_up, ..., f2=lr_filter_raw(e2, taps_inv)) — as ONE launch (esr_cem_filter_upscale_sep: every tile
     filters its own window of e on chip, bit-identical to the two launches) when both filters are separable and the windows fit, else as the two
     (three) launches."""
@@ -156,8 +147,7 @@ def filter_upscale_raw(e, taps_inv, taps_up, sf, pre, e2=None, g=None, crop=0, m
         fold = B * Cc * ((Ho + 63) // 64) * ((Wo + 63) // 64) <= FOLD_MAX_TILES and \
             _lib.lib.esr_cem_sep_form(2, sf, int(_taps(taps_inv, e.device).shape[0]), pre, h, w) == 0
     if fold and sep_i is not None and sep_u is not None:
-        o = out if out is not None else torch.empty(B, Cc, Ho, Wo, dtype=torch.float32, device=e.device)
-        assert o.shape == (B, Cc, Ho, Wo) and o.dtype == torch.float32 and o.is_contiguous()
+        o = torch.empty(B, Cc, Ho, Wo, dtype=torch.float32, device=e.device)
         o2 = torch.empty_like(o) if mode == 3 else None
         e2p = _prep(e2, 'LR image') if e2 is not None else None
         gp = _prep(g, 'generated image') if g is not None else None
@@ -172,7 +162,7 @@ def filter_upscale_raw(e, taps_inv, taps_up, sf, pre, e2=None, g=None, crop=0, m
             return (o, o2) if mode == 3 else o
     f = lr_filter_raw(e, taps_inv)
     f2 = lr_filter_raw(e2, taps_inv) if e2 is not None else None
-    return upscale_raw(f, taps_up, sf, pre, f2=f2, g=g, crop=crop, mode=mode, rng=rng, out=out)
+    return upscale_raw(f, taps_up, sf, pre, f2=f2, g=g, crop=crop, mode=mode, rng=rng)
 
 
 def adjoint_raw(dy, tabs, kind, sf, pre, in_shape, base=None, alpha=1.0):
@@ -235,19 +225,6 @@ def project(lr, g, taps_down, taps_inv, taps_up, sf, pre, lr_pad=0, crop=0, sigm
         from . import autograd as AG
         return AG.cem_project_with_grad(lr, g, taps_down, taps_inv, taps_up, sf, pre, lr_pad, crop, sigmoid_range, decomposed)
     if sigmoid_range is None and not decomposed:
-        B = g.shape[0]
-        nb = min(PROJECT_CHUNK_IMAGES, PROJECT_CHUNK_BYTES // max(g[0].numel() * 4, 1))
-        if nb >= 2 and B > nb and g.is_contiguous() and lr.is_contiguous() and g.dtype == torch.float32 and lr.dtype == torch.float32 and \
-                PROJECT_CHUNK_BYTES < g.numel() * 4:
-            # `g` is read twice — by the strided downscale and again by the upscale that adds the correction to it.  A whole batch of it
-            # (configs[1]: 135 MB) is gone from the 256 MB Infinity Cache by the time the upscale comes back to it behind the other two kernels'
-            # traffic; a chunk of a few images (8 x 4.2 MB at 592 x 592) is still there.  Same kernels, same values, image by image.
-            out = torch.empty(B, g.shape[1], g.shape[2] - 2 * crop, g.shape[3] - 2 * crop, dtype=torch.float32, device=g.device)
-            for b0 in range(0, B, nb):
-                gc, lc = g[b0:b0 + nb], lr[b0:b0 + nb]
-                e = downscale_raw(gc, taps_down, sf, pre, lr=lc, lr_pad=lr_pad)
-                filter_upscale_raw(e, taps_inv, taps_up, sf, pre, g=gc, crop=crop, mode=1, out=out[b0:b0 + nb])
-            return out
         e = downscale_raw(g, taps_down, sf, pre, lr=lr, lr_pad=lr_pad)       # x - D(g) on the padded frame
         return filter_upscale_raw(e, taps_inv, taps_up, sf, pre, g=g, crop=crop, mode=1)       # crop(g + U(K(x - D g)))
     lr_p = torch.nn.functional.pad(lr, (lr_pad,) * 4, mode='replicate') if lr_pad else lr

@@ -73,7 +73,7 @@ def _tap_masks():
     return fwd, flipped
 
 
-MASK_FWD, MASK_FLIPPED = _tap_masks()       # (module attributes; None: multiply the structural zeros too — same results)
+MASK_FWD, MASK_FLIPPED = _tap_masks()
 
 
 def conv_io(t_in, t_out, B, h, w, b0=0):
@@ -218,14 +218,14 @@ class CriticEngine:
     def conv_fwd(self, L, x, use_bias=True):
         P, B, _, Hp, Wp, _ = x.shape
         y = new_at(P, B, L.cout // 8, Hp - 2, Wp - 2, x.device)
-        kw = dict(tap_mask_k=MASK_FWD, tap_mask_k_shift=1) if (L.strided and MASK_FWD) else {}      # chunk cp = group pair: parity of quad cp >> 1
+        kw = dict(tap_mask_k=MASK_FWD, tap_mask_k_shift=1) if L.strided else {}      # chunk cp = group pair: parity of quad cp >> 1
         A.conv3x3(L.fwd, view_of(x), B, Hp - 2, Wp - 2, L.cout, out=view_of(y), use_bias=use_bias, reverse=False, **kw)
         return y
 
     def conv_dgrad(self, L, dy):
         P, B, _, Hp, Wp, _ = dy.shape
         dx = new_at(P, B, (L.cin_e + 7) // 8, Hp - 2, Wp - 2, dy.device)
-        kw = dict(tap_mask_m=MASK_FLIPPED) if (L.strided and MASK_FLIPPED) else {}                     # 32-row output tile j = input quad j
+        kw = dict(tap_mask_m=MASK_FLIPPED) if L.strided else {}                     # 32-row output tile j = input quad j
         A.conv3x3(L.tr, view_of(dy), B, Hp - 2, Wp - 2, L.cin_e, out=view_of(dx), use_bias=False, reverse=False, **kw)
         return dx
 
@@ -454,7 +454,7 @@ class _BNActBwd(torch.autograd.Function):
         return None, None, None, None, (g_y if not st.const else None), g_gamma, g_dz
 
 
-def critic_forward(eng, x):
+def _critic_forward_per_layer(eng, x):
     """Logits [B, 1] of the critic for fp32 NCHW images `x`, differentiable to any order the WGAN-GP step needs."""
     A.require_gpu(x, 'critic input')
     net = eng.net
@@ -665,7 +665,7 @@ def _fwd_pass(eng, x, training, groups=1):
         for i, L in enumerate(eng.layers):
             h, w = bs.hw[i]
             y, z = bs.y[i], bs.z[i]
-            kw = dict(tap_mask_k=MASK_FWD, tap_mask_k_shift=1) if (L.strided and MASK_FWD) else {}
+            kw = dict(tap_mask_k=MASK_FWD, tap_mask_k_shift=1) if L.strided else {}
             vi, vo, Bc, hc, wc = conv_io(t, y, B, h, w)
             A.conv3x3(L.fwd, vi, Bc, hc, wc, L.cout, out=vo, reverse=False, k_split_ws=bs.ksw, **kw)
             st = bs.stats(eng, i, training)
@@ -704,7 +704,7 @@ class _WgradSet:
         for (L, dy, xin), out in zip(pairs, self.layout.views(self._first)):
             vx, vdy, Bc, hc, wc = conv_io(xin, dy, nb, dy.shape[3] - 2, dy.shape[4] - 2, b0)     # (stacked maps: one tall image; their borders are zero)
             descs.append(A.wgrad_desc(vdy, vx, None, 0, (L.cout, L.cin_e, 3, 3), Bc, hc, wc, 1.0, 1, bs.dev, out=out,
-                                      tap_masks=MASK_FWD if (L.strided and MASK_FWD) else None)[0])
+                                      tap_masks=MASK_FWD if L.strided else None)[0])
         self.table = A.WgradTable(descs, bs.dev, ptr=self._first.data_ptr())
         # the embedded stride-2 layers' 4x4 gradients are gathered out of their 3x3 x 4 cin blocks by ONE index launch for all of them
         idx, self.gather, g0 = [], {}, 0
@@ -794,7 +794,7 @@ def _bwd_pass(eng, S, d_feat, g_ys, want_dx, want_params, group=None):
                 A.act_combine(view_of(dy, b0=ib0), inb, A_=view_of(dy, b0=ib0), alpha=1.0, Bv=view_of(bs.g_y[i], b0=ib0), beta=1.0, s=1)
             if i > 0 or want_dx:
                 dx = bs.dz[i - 1] if i > 0 else bs.dx0
-                kw = dict(tap_mask_m=MASK_FLIPPED) if (L.strided and MASK_FLIPPED) else {}
+                kw = dict(tap_mask_m=MASK_FLIPPED) if L.strided else {}
                 vi, vo, Bc, hc, wc = conv_io(dy, dx, B, h, w, b0)
                 A.conv3x3(L.tr, vi, Bc, hc, wc, L.cin_e, out=vo, use_bias=False, reverse=False, k_split_ws=bs.ksw, **kw)
         if want_dx:
@@ -847,7 +847,7 @@ def _bwd2_pass(eng, S, u, want_params, group=None):
             y, gdy = bs.y[i], bs.gdy[i]
             h, w = bs.hw[i]
             st = bs.stats(eng, i, training, g0)
-            kw = dict(tap_mask_k=MASK_FWD, tap_mask_k_shift=1) if (L.strided and MASK_FWD) else {}
+            kw = dict(tap_mask_k=MASK_FWD, tap_mask_k_shift=1) if L.strided else {}
             vi, vo, Bc, hc, wc = conv_io(ut, gdy, B, h, w, b0)
             A.conv3x3(L.fwd, vi, Bc, hc, wc, L.cout, out=vo, use_bias=False, reverse=False, k_split_ws=bs.ksw, **kw)
             if not st.const:
@@ -942,7 +942,6 @@ class _CriticBwd(torch.autograd.Function):
 
 
 FUSED = True        # False: one autograd node and several FFI calls per layer (the readable definition; cross-checked by the tests)
-_critic_forward_per_layer = critic_forward
 
 
 def critic_forward(eng, x):
@@ -953,9 +952,6 @@ def critic_forward(eng, x):
     return critic_forward_group(eng, [x])[0]
 
 
-GROUPED = True      # False: a grouped call runs its batches one by one
-
-
 def critic_forward_group(eng, xs):
     """[critic(x) for x in xs] for equally shaped batches — the same values as separate calls in this order (each batch is normalised with
     its own batch statistics, the running statistics see the batches one after the other) — executed as ONE pass over the concatenated
@@ -963,7 +959,7 @@ def critic_forward_group(eng, xs):
     become one launch, and autograd has one graph to walk.  The WGAN-GP step calls it with [real, fake, interpolated]
     (models/SRRaGAN_model.py); `input_grad_only(group=2)` around the penalty's autograd.grad keeps that pass on the interpolated images."""
     xs = list(xs)
-    if not FUSED or not GROUPED or any(x.shape != xs[0].shape for x in xs):
+    if not FUSED or any(x.shape != xs[0].shape for x in xs):
         return [critic_forward(eng, x) for x in xs]
     for x in xs:
         A.require_gpu(x, 'critic input')

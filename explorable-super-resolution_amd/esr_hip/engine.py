@@ -53,12 +53,6 @@ class RRDBEngine:
         # data gradient reads nothing but the signs (LeakyReLU'); 'full' — every RDB's whole 24-group hi+lo buffer, as training needs (the
         # weight gradient contracts the activations themselves).  Same gradients bit for bit; 1/3 of the memory per RDB.
         self.stash = 'masks'
-        # 'mixed' only: format of its backward pass, 'f16' (as the forward) or 'bf16' (hi+lo gradients, 3 MFMAs per product); see _bwd_split
-        self.mixed_bwd = 'f16'
-        # 'mixed' only: which dense-block convs multiply the residual stream's lo plane as well: 'none' (default), 'conv4' or 'all' 
-        self.mixed_xlo = 'none'
-        # 'mixed' backward: renormalise the fp16 gradient of every RRDB's input (False: one scale for the whole pass)
-        self.grad_renorm = True
         self._ptr_fp, self._ptr_epoch = None, 0   # parameter storages the recorded descriptors point into; epoch moves when any changes
         self.generation = 0  # bumped by invalidate(): consumers that cache derived state (GraphedForward) compare it
         self._ev = None      # optional (start, end) torch.cuda.Event pair bracketing the conv launches of one forward (bench.py)
@@ -215,27 +209,11 @@ class RRDBEngine:
             self._pack_batch.run(packs, epoch=(self._ptr_epoch, self._pack_sets))
         self._packs_fp = fp
 
-    @property
-    def _bwd_split(self):
-        """Buffer format of the backward pass.  'mixed' back-propagates (to the input only) the way it runs forward: fp16 planes, the
-        gradient of the residual stream stored hi+lo, one-plane operands inside the dense blocks, with the incoming gradient scaled by a
-        power of two into fp16's range (run_backward).  mixed_bwd = 'bf16' selects the earlier variant: bf16 hi+lo gradients (3 MFMAs
-        per product), the saved fp16 activations serving as LeakyReLU' masks only."""
-        if self.split == 'mixed':
-            return True if self.mixed_bwd == 'bf16' else 'mixed'
-        return self.split
-
-    def _bwd_wfmt(self, rdb):
-        """Weight format of a data-gradient pack (rdb: a dense-block pack)."""
-        if self._bwd_split != 'mixed':
-            return self._bwd_split
-        return 'f16x2' if rdb else 'f16x3'
-
-    def _wfmt(self, name):
-        """Weight format of one layer's forward pack."""
+    def _wfmt(self, rdb):
+        """Weight format of a forward or data-gradient pack (rdb: a dense-block pack)."""
         if self.split != 'mixed':
             return self.split
-        return 'f16x2' if name.startswith('rrdb') else 'f16x3'
+        return 'f16x2' if rdb else 'f16x3'
 
     @property
     def _pshuf(self):
@@ -255,11 +233,11 @@ class RRDBEngine:
             for name, c, lat in self._convs():
                 if name.startswith('up') and self._pshuf:
                     for q in range(self._pshuf ** 2):         # 64 * r^2 conv channels = r^2 launches of 64 rows
-                        d[name, q] = A.PackedConv(c.weight, c.bias, lat, split=self._wfmt(name), rows=self._ps_rows(q))
+                        d[name, q] = A.PackedConv(c.weight, c.bias, lat, split=self._wfmt(name.startswith('rrdb')), rows=self._ps_rows(q))
                 elif c.weight.shape[0] > 64:                  # nf = 128, 192, ...: output slices of one launch
-                    d[name] = A.PackedConvSlices(c.weight, c.bias, lat, split=self._wfmt(name))
+                    d[name] = A.PackedConvSlices(c.weight, c.bias, lat, split=self._wfmt(name.startswith('rrdb')))
                 else:
-                    d[name] = A.PackedConv(c.weight, c.bias, lat, split=self._wfmt(name))
+                    d[name] = A.PackedConv(c.weight, c.bias, lat, split=self._wfmt(name.startswith('rrdb')))
             self._packed = d
             self._pack_sets += 1
             self._pack_gen[0] = self._pack_sets
@@ -277,9 +255,9 @@ class RRDBEngine:
                 main = c.weight.shape[1] - lat
                 rows = self._ps_rows() if (name.startswith('up') and self._pshuf) else None      # K axis in esr_pixel_unshuffle's order
                 for j in range((main + 63) // 64):
-                    d[name, 'm%d' % j] = A.PackedConv(c.weight, None, lat, split=self._bwd_wfmt(False), transposed=True, m_slice=(64 * j, min(main, 64 * j + 64)), rows=rows)
+                    d[name, 'm%d' % j] = A.PackedConv(c.weight, None, lat, split=self._wfmt(False), transposed=True, m_slice=(64 * j, min(main, 64 * j + 64)), rows=rows)
                 if lat:
-                    d[name, 'z'] = A.PackedConv(c.weight, None, lat, split=self._bwd_wfmt(False), transposed=True, m_slice='latent')
+                    d[name, 'z'] = A.PackedConv(c.weight, None, lat, split=self._wfmt(False), transposed=True, m_slice='latent')
             self._packed_t = d
             self._pack_sets += 1
             self._pack_gen[1] = self._pack_sets
@@ -305,11 +283,11 @@ class RRDBEngine:
                     pieces = [(ws[4], s4), (ws[3], 1.0), (ws[2], 1.0), (ws[1], 1.0), (ws[0], 1.0)]
                     for c in (3, 2, 1, 0):
                         rows = list(range(lat + nf + 32 * c, lat + nf + 32 + 32 * c))
-                        d[name, 'g%d' % c] = A.PackedSum(pieces[:4 - c], [rows] * (4 - c), split=self._bwd_wfmt(True))
+                        d[name, 'g%d' % c] = A.PackedSum(pieces[:4 - c], [rows] * (4 - c), split=self._wfmt(True))
                     for j in range((nf + 63) // 64):       # the gradient of the block input: 64 rows per launch
-                        d[name, 'gx%d' % j] = A.PackedSum(pieces, [list(range(lat + 64 * j, lat + min(nf, 64 * j + 64)))] * 5, split=self._bwd_wfmt(True))
+                        d[name, 'gx%d' % j] = A.PackedSum(pieces, [list(range(lat + 64 * j, lat + min(nf, 64 * j + 64)))] * 5, split=self._wfmt(True))
                     if lat:
-                        d[name, 'gz'] = A.PackedSum(pieces, [list(range(lat))] * 5, split=self._bwd_wfmt(True))
+                        d[name, 'gz'] = A.PackedSum(pieces, [list(range(lat))] * 5, split=self._wfmt(True))
             self._packed_rdb_t = d
             self._pack_sets += 1
             self._pack_gen[2] = self._pack_sets
@@ -471,14 +449,10 @@ class RRDBEngine:
         # ---- fea_conv -> fea (shortcut source) and the first RDB buffer
         conv(pk['fea'], bufs['xin'].view(), B, h, w, nf, in0=zlr, out=bufs['fea'].view(), out2=buf_of(0).view(0, ng) if net.nb else None, name='fea_conv')
         # 'mixed': the dense blocks' intermediate activations (outputs of convs 0-3, read only inside their RDB) are ONE fp16 plane; only
-        # the RDB input (groups 0:8, the residual stream) keeps hi+lo.  Their lo planes are never written (they stay zero).
+        # the RDB input (groups 0:8, the residual stream) keeps hi+lo.  Their lo planes are never written (they stay zero), and the dense-block
+        # convs multiply the hi planes only, the residual stream's included.
         mixed = self.split == 'mixed'
-        lo8 = dict(in1_lo_groups=ng) if mixed else {}
-        xlo_mode = self.mixed_xlo
-        lo_in = lo8 if xlo_mode == 'all' else dict(in1_lo_groups=-1)
-        lo_c4 = lo8 if xlo_mode in ('all', 'conv4') else dict(in1_lo_groups=-1)
-        if not mixed:
-            lo_in = lo_c4 = {}
+        hi_only = dict(in1_lo_groups=-1) if mixed else {}
         for r in range(net.nb):
             rrdb_in = buf_of(3 * r)
             for k in range(3):
@@ -486,14 +460,14 @@ class RRDBEngine:
                 for i in range(4):
                     o2 = dict(out2=bufs['stash'][3 * r + k].view(4 * i, 4)) if keep == 'masks' else {}      # the one-plane copy the backward's masks read
                     conv(pk['rrdb%d.rdb%d.conv%d' % (r, k, i)], buf.view(0, ng + 4 * i), B, h, w, 32, in0=zall, act_slope=0.2,
-                         out=buf.view(ng + 4 * i, 4, with_lo=not mixed), name='rrdb%d.rdb%d.conv%d' % (r, k, i), **(lo_in if (i > 0 or xlo_mode != 'all') else {}), **o2)
+                         out=buf.view(ng + 4 * i, 4, with_lo=not mixed), name='rrdb%d.rdb%d.conv%d' % (r, k, i), **hi_only, **o2)
                 name = 'rrdb%d.rdb%d.conv4' % (r, k)
                 if k < 2:     # RDB output: 0.2*conv5 + x            (block.py:235)
-                    conv(pk[name], buf.view(0, nd), B, h, w, nf, in0=zall, alpha=0.2, res1=buf.view(0, ng), beta1=1.0, out=nxt.view(0, ng), name=name, **lo_c4)
+                    conv(pk[name], buf.view(0, nd), B, h, w, nf, in0=zall, alpha=0.2, res1=buf.view(0, ng), beta1=1.0, out=nxt.view(0, ng), name=name, **hi_only)
                 else:         # RRDB output: 0.2*(0.2*conv5 + x) + x_rrdb   (block.py:270); lands in the next RRDB's first buffer
                     # (inference: that is rrdb_in's own buffer when the three buffers rotate; the kernel's in-place residual is safe)
                     conv(pk[name], buf.view(0, nd), B, h, w, nf, in0=zall, alpha=0.04, res1=buf.view(0, ng), beta1=0.2,
-                         res2=rrdb_in.view(0, ng), beta2=1.0, out=nxt.view(0, ng), name=name, **lo_c4)
+                         res2=rrdb_in.view(0, ng), beta2=1.0, out=nxt.view(0, ng), name=name, **hi_only)
         last = buf_of(nrdb).view(0, ng) if net.nb else bufs['fea'].view()
         # LR_conv + trunk shortcut (block.py:96)
         conv(pk['lr_conv'], last, B, h, w, nf, in0=zall, res1=bufs['fea'].view(), beta1=1.0, out=bufs['trunk'].view(), name='LR_conv')
@@ -516,9 +490,6 @@ class RRDBEngine:
     @A.one_stream
     def run_backward(self, x_shape, pad, bufs, dg, need_dx=True, need_dw=False):
         """Gradients of sum(g * dg): returns (dx or None, {param: grad} or None).  `bufs` = run_forward(..., keep=True)[1]."""
-        if self.split == 'mixed' and need_dw and self._bwd_split != 'mixed':
-            raise NotImplementedError("precision 'mixed' with mixed_bwd = 'bf16' back-propagates to the INPUT only (Z optimisation): its saved "
-                                      "activations are fp16, the gradients bf16 — the weight-gradient kernel contracts one element format")
         if self.split in ('f16', 'f16x2'):
             raise NotImplementedError("the fp16 precisions are inference modes: fp16 gradients underflow without loss scaling; "
                                       "use 'split' (fp32-class) or 'bf16' for training / Z optimisation")
@@ -531,7 +502,7 @@ class RRDBEngine:
             self.packed_rdb_t()
         # the launch-list path covers the passes whose only non-library work is allocating dx and the flat dW buffer; 'mixed' (device-side
         # gradient scales read by torch ops in between) and pixel-shuffle networks (index_copy_ of permuted rows) launch directly
-        planned = self.use_plans and self._bwd_split != 'mixed' and not self._pshuf and not bufs.get('_ephemeral') and A._rec() is None \
+        planned = self.use_plans and self.split != 'mixed' and not self._pshuf and not bufs.get('_ephemeral') and A._rec() is None \
             and '_plans' in bufs
         if not planned:
             return self._backward_launches(x_shape, pad, bufs, dg, need_dx, need_dw)
@@ -557,7 +528,7 @@ class RRDBEngine:
         """The launch sequence of one backward pass (issued directly, or collected by an active A.Recorder — then `dx`, the weight-gradient
         collector `wg`, a private gradient-buffer `pool` and the list `keep` that receives every buffer the recorded commands point to are
         supplied by the caller)."""
-        net, sp = self.net, self._bwd_split
+        net, sp = self.net, self.split
         sf = net.upscale
         has_lat = net.latent_input is not None and net.num_latent_channels > 0
         lat1 = net.num_latent_channels if has_lat else 0
@@ -734,7 +705,7 @@ class RRDBEngine:
                     kw = dict(res2=G_rrdb.view(g_lo, g_n), beta2=1.0) if k == 0 else {}
                     conv(pr[name, 'gx%d' % j], G.view(0, nd), B, h, w, 8 * g_n, out=G_next.view(g_lo, g_n), use_bias=False, res1=G.view(g_lo, g_n), beta1=s_out, **kw, **hi_only)
                 G_cur = G_next
-            if f16_bwd and self.grad_renorm:
+            if f16_bwd:
                 # d(input of RRDB r) is complete and not yet recorded anywhere: renormalise it (and the latent gradient accumulated so far)
                 scaler.rescale(B, [G_cur.view(0, ng)] + ([GZ_lr.view()] if zgrad and not zfirst else []), 10)
                 gscale = scaler.current
@@ -906,8 +877,8 @@ class WGrad:
         eng = self.engine
         ov = eng.wgrad_overlap if recorded else 0
         G = len(ov) if isinstance(ov, (tuple, list)) else int(ov or 0)
-        if G < 2 or self.permuted or self.scaled or len(self.descs) < 4 * G or eng._bwd_split is True \
-                or not _side_kernel_capped(eng._bwd_split in ('mixed', 'f16')):
+        if G < 2 or self.permuted or self.scaled or len(self.descs) < 4 * G or eng.split is True \
+                or not _side_kernel_capped(eng.split in ('mixed', 'f16')):
             ov = 0
         return wgrad_groups(self.layout.bounds(), self.desc_layer, self.ready, self.ex.bucket_bytes if self.ex is not None else None, ov)
 

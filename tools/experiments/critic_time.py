@@ -77,7 +77,7 @@ if os.environ.get('CRITIC_ONLY') == 'hip':
     variants = variants[:1]
 if os.environ.get('CRITIC_ONLY') == 'step':          # profiling runs: the critic step alone, 10 + 3 iterations
     variants = []
-    timed(dict(passes(lambda x: K.critic_forward(eng, x), True))['critic step, grouped' if os.environ.get('CRITIC_GROUPED', '1') != '0' else 'WGAN-GP critic step'])
+    timed(dict(passes(lambda x: K.critic_forward(eng, x), True))['critic step, grouped'])
 for name, run in variants:
     for what, fn in passes(run, name.startswith('hip')):
         wall, host = timed(fn)

@@ -4,7 +4,6 @@
 # usage: tools/pmc_workload.sh <tag> "<python script and its arguments>" [kernel-name regex to keep]
 #   tools/pmc_workload.sh r04_wgrad "bench.py --workload c3 --steps 4 --warmup 3" 'wgrad_batch'
 #   tools/pmc_workload.sh r04_c5_f16 "bench.py --workload c5 --precision f16 --steps 2 --warmup 1 --no-cpu-baseline" 'conv3x3_tile'
-#   tools/pmc_workload.sh r04_cem_chunk8 "tools/experiments/cem_project_loop.py 8" 'cem_'
 set -e
 TAG=${1:?tag}; ARGS=${2:?bench arguments}; KEEP=${3:-.}
 cd "$(dirname "$0")/.."

@@ -841,18 +841,22 @@ struct WgradPlan { int tiles_x, tiles_y, ncit_main, ncit, ngroups, nslices, mt, 
 // tile is run in the latent tile's form — the 27 (tap, channel) columns as ONE MFMA tile (wgrad_body<..., LATK>) — instead of nine 32-wide tiles
 // that are 3/32 full: the layer is presented to the kernel as "no main tiles + a latent tile of cin_main channels".
 static bool main_as_latk(const esr_wgrad_desc* d) { return !d->xlat.hi && d->cin_main <= 3 && d->upsample <= 1; }
+// a latent segment of <= 3 channels: its tile runs the 27-column form too
+static bool lat_as_latk(const esr_wgrad_desc* d) { return d->xlat.hi && d->lat > 0 && d->lat <= 3; }
 static bool desc_is_s2d(const esr_wgrad_desc* d) {
     return d->tap_masks[0] == 432 && d->tap_masks[1] == 216 && d->tap_masks[2] == 54 && d->tap_masks[3] == 27 && d->cin_main % 128 == 0 &&
            d->dy.fmt != ESR_FMT_F16;
 }
-// shapes: the launch runs the kernel flavour that has the 16x16 / 32x8 pixel tiles (the space-to-depth one): take the shape with the fewest tiles
+// shapes: the launch runs the kernel flavour that has the 16x16 / 32x8 pixel tiles (the space-to-depth one): take the shape with the fewest tiles.
+// Not for upsampled layers, fp16 operands (no such kernel) or layers with a 27-column tile: that form exists for the 8 x 32 tiles only and walks
+// the layer's tiles_x / tiles_y as 8 x 32 tiles.
 static WgradPlan wgrad_plan(const esr_wgrad_desc* d, int target_wgs = 512, bool shapes = false) {
     WgradPlan p;
     p.mt = (d->cout + 31) / 32;
     p.shape = 0;
     p.tiles_x = (d->W + WG_TW - 1) / WG_TW;
     p.tiles_y = (d->H + WG_TH - 1) / WG_TH;
-    if (shapes && (d->upsample <= 1) && !main_as_latk(d))
+    if (shapes && (d->upsample <= 1) && d->dy.fmt != ESR_FMT_F16 && !main_as_latk(d) && !lat_as_latk(d))
         for (int sh = 1; sh <= 2; ++sh) {
             const int tw = WG_TW >> sh, th = WG_TH << sh;
             const int tx = (d->W + tw - 1) / tw, ty = (d->H + th - 1) / th;
@@ -880,6 +884,8 @@ static int wgrad_validate(const esr_wgrad_desc* d) {
     if ((d->x.lo != nullptr) != split) return ESR_E_ARG;
     if (d->xlat.hi && ((d->xlat.lo != nullptr) != split)) return ESR_E_ARG;
     if (d->x.fmt != d->dy.fmt || (d->xlat.hi && d->xlat.fmt != d->dy.fmt)) return ESR_E_ARG;      // one element format per contraction
+    // the views cover the channels named (the kernel reads a group past a view's end as zeros: the gradient would come back zero, silently)
+    if ((int64_t)d->x.ncg * 8 < d->cin_main || (int64_t)d->dy.ncg * 8 < d->cout || (d->xlat.hi && (int64_t)d->xlat.ncg * 8 < d->lat)) return ESR_E_ARG;
     if (d->dy.fmt == ESR_FMT_F16 && split) return ESR_E_UNSUPPORTED;   // fp16 operands: the hi planes only (one MFMA per product)
     return ESR_OK;
 }
@@ -887,7 +893,7 @@ static int wgrad_validate(const esr_wgrad_desc* d) {
 static WgradArgs wgrad_args(const esr_wgrad_desc* d, const WgradPlan& p, float* ws) {
     WgradArgs a{};
     a.shape = p.shape;
-    a.latk = (d->xlat.hi && d->lat > 0 && d->lat <= 3) ? 1 : 0;
+    a.latk = lat_as_latk(d) ? 1 : 0;
     a.dy = to_dview(d->dy);
     a.x = to_dview(d->x);
     a.xlat = to_dview(d->xlat);
@@ -938,7 +944,10 @@ static size_t wgrad_lds(int npl, int nst) {
 // Work unit = one (layer, input tile, output tile) block over one image tile.  Every layer's pixel sum is cut into as many slices as
 // it takes to keep a workgroup's share near total / 768 (three waves of workgroups over the chip): with hundreds of equal layers
 // that is one slice each (no partial sums at all), a few big high-resolution layers get several, a small net gets many.
-struct BatchPlan { int64_t unit, nwg, table_bytes, map_bytes, partial_floats; };
+struct BatchPlan { int64_t unit, nwg, table_bytes, map_bytes, partial_floats; bool shapes; };
+// esr_conv3x3_wgrad_batch_unit's answer = the slicing granule | this bit when the whole set runs the 16x16 / 32x8 tile shapes (it has a
+// space-to-depth layer): a part without one must still tile its layers as the one launch does
+constexpr int64_t UNIT_SHAPES = (int64_t)1 << 48;
 static WgradPlan batch_entry_plan(const esr_wgrad_desc* d, int64_t unit, bool shapes) {
     WgradPlan p = wgrad_plan(d, 1, shapes);
     const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y * d->B;
@@ -961,13 +970,15 @@ static void entry_work(int i, const WgradPlan& p, std::vector<int4>& pairs) {
 static BatchPlan batch_plan(const esr_wgrad_desc* descs, int n, int64_t unit_override = 0) {
     BatchPlan b{};
     int64_t work = 0;
-    const bool shapes = batch_is_s2d(descs, n);
+    // the tile shapes and slicing of a LARGER set this one is a part of (esr_conv3x3_wgrad_batch_unit)
+    const bool shapes = b.shapes = unit_override > 0 ? (unit_override & UNIT_SHAPES) != 0 : batch_is_s2d(descs, n);
     for (int i = 0; i < n; ++i) {
         const WgradPlan p = wgrad_plan(&descs[i], 1, shapes);
         work += (int64_t)p.ngroups * p.tiles_x * p.tiles_y * descs[i].B;
     }
     b.unit = work / 768 > 0 ? work / 768 : 1;
-    if (unit_override > 0) b.unit = unit_override;      // the slicing of a LARGER set this one is a part of (esr_conv3x3_wgrad_batch_unit)
+    if (unit_override > 0) b.unit = unit_override & (UNIT_SHAPES - 1);
+    if (b.unit < 1) b.unit = 1;
     for (int i = 0; i < n; ++i) {
         const WgradPlan p = batch_entry_plan(&descs[i], b.unit, shapes);
         b.nwg += (int64_t)p.ngroups * p.nslices;
@@ -988,6 +999,23 @@ extern "C" int64_t esr_conv3x3_wgrad_workspace_floats(const esr_wgrad_desc* d) {
     if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || d->cin_main <= 0) return ESR_E_ARG;
     const int64_t n = wgrad_partial_floats(wgrad_plan(d, 512, desc_is_s2d(d)));
     return n > 0 ? n : 1;
+}
+
+extern "C" int esr_conv3x3_wgrad_tiling(const esr_wgrad_desc* d, int32_t* out) {
+    if (!out) return ESR_E_ARG;
+    const int rc = wgrad_validate(d);
+    if (rc != ESR_OK) return rc;
+    const WgradPlan p = wgrad_plan(d, 512, desc_is_s2d(d));
+    const WgradArgs a = wgrad_args(d, p, nullptr);
+    const bool f16 = d->dy.fmt == ESR_FMT_F16, split = d->dy.lo != nullptr;
+    out[0] = p.tiles_x;
+    out[1] = p.tiles_y;
+    out[2] = p.shape;
+    out[3] = p.nslices;
+    // the kernel forms, as esr_conv3x3_wgrad picks them (wgrad_dispatch, the `fast_issue` copies of wgrad_body)
+    out[4] = (lat_as_latk(d) ? ESR_WGRAD_FORM_LAT27 : 0) | (main_as_latk(d) ? ESR_WGRAD_FORM_MAIN27 : 0) |
+             (a.tapmode == 1 && !f16 ? ESR_WGRAD_FORM_S2D : 0) | (!split && a.ups == 1 ? ESR_WGRAD_FORM_FAST_COPY : 0);
+    return ESR_OK;
 }
 
 extern "C" int esr_conv3x3_wgrad(const esr_wgrad_desc* d, esr_stream_t stream) {
@@ -1030,7 +1058,8 @@ extern "C" int64_t esr_conv3x3_wgrad_batch_unit(const esr_wgrad_desc* descs, int
     if (!descs || n <= 0) return ESR_E_ARG;
     for (int i = 0; i < n; ++i)
         if (descs[i].B <= 0 || descs[i].H <= 0 || descs[i].W <= 0 || descs[i].cout <= 0 || descs[i].cin_main <= 0) return ESR_E_ARG;
-    return batch_plan(descs, n).unit;
+    const BatchPlan b = batch_plan(descs, n);
+    return b.unit | (b.shapes ? UNIT_SHAPES : 0);
 }
 
 static int batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan, int64_t unit, esr_stream_t stream);
@@ -1055,7 +1084,7 @@ static int batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int
     std::vector<WgradArgs> table(n);
     std::vector<int4> work;                                      // the work list in its natural order (layer, slice, group)
     work.reserve((size_t)b.nwg);
-    const bool shapes = batch_is_s2d(descs, n);
+    const bool shapes = b.shapes;
     float* partials = (float*)((char*)workspace + b.table_bytes + b.map_bytes);
     int64_t pf = 0;
     int max_red = 0;
@@ -1093,8 +1122,8 @@ static int batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int
     plan->max_red = max_red;
     plan->split = split ? 1 : 0;
     plan->f16 = descs[0].dy.fmt == ESR_FMT_F16 ? 1 : 0;
-    plan->s2d = 0;
-    for (const WgradArgs& t : table) plan->s2d |= t.tapmode == 1 ? 1 : 0;
+    plan->s2d = 0;                                               // the space-to-depth kernel: tap-skipping layers, or the 16x16 / 32x8 tiles
+    for (const WgradArgs& t : table) plan->s2d |= (t.tapmode == 1 || t.shape != 0) ? 1 : 0;
     plan->reserved = 0;
     return ESR_OK;
 }

@@ -320,9 +320,16 @@ int esr_cem_adjoint_sep(const float* dy, int B, int C, int hq, int wq, int sq, i
 /* ---- conv3x3 weight / bias gradient (autograd of nn.Conv2d, block.py:141-142) ----
  *   dw[co][lat+ci][dy][dx] += alpha * sum_{b,y,x} dy[b,co,y,x] * x[b,ci,(y+dy-1)/up,(x+dx-1)/up]     (zero padded)
  *   dw[co][e][dy][dx]      += ... with xlat for the latent channels e < lat;   db[co] += alpha * sum dy
- * dw ([cout][lat+cin_main][3][3]) and db ([cout], may be NULL) are fp32 and ACCUMULATED into (zero them first).
+ * dw ([cout][lat+cin_main][3][3]) and db ([cout], may be NULL) are fp32 and ACCUMULATED into (zero them first); nothing outside them is written.
  * The pixel sum is split over ~3 workgroups per CU; their partial tiles go through `workspace` (caller-owned device memory of at
- * least esr_conv3x3_wgrad_workspace_floats(d) floats, contents undefined afterwards) and a second small kernel folds them. */
+ * least esr_conv3x3_wgrad_workspace_floats(d) floats, contents undefined afterwards) and a second small kernel folds them.
+ * Checked by the entry point (ESR_E_ARG otherwise, before anything touches the device): dy, x, dw given; x.H * upsample == H and
+ * x.W * upsample == W for ANY upsample >= 1 (0 = 1; the source coordinate is an integer division, exact for every factor); dy and xlat are
+ * H x W; xlat only with upsample 1 and 1 <= lat <= 8; the views cover the channels named — dy.ncg * 8 >= cout, x.ncg * 8 >= cin_main,
+ * xlat.ncg * 8 >= lat (a group past a view's end would be read as zeros); all views in one element format and all hi+lo or all hi-only.
+ * fp16 hi+lo operands: ESR_E_UNSUPPORTED (fp16 runs the hi planes only).  Preconditions not checked: every view's one-pixel border is
+ * zero in all 8 lanes (it is the conv's zero padding, and the reads past the image's edge land on it); lanes past cout / cin_main / lat
+ * of a partial last group may hold anything, NaN included — they reach no stored element. */
 typedef struct {
     esr_act_view dy;         /* gradient w.r.t. the conv's (pre-activation) output, cout channels */
     esr_act_view x;          /* the conv's main input (before the nearest upsample when upsample > 1) */
@@ -337,11 +344,23 @@ typedef struct {
     float* workspace;
     int64_t workspace_floats;
     /* a HINT, as esr_conv3x3_desc.tap_mask_k: the weights whose gradient this is are structurally zero outside the taps of tap_masks[i & 3] for
-     * the i-th 32-channel tile of the main input; dw entries outside the masks receive zeros or are left untouched (0 = all taps) */
+     * the i-th 32-channel tile of the main input (0 = all taps).  dw entries inside the masks, and every entry of the latent channels,
+     * receive the gradient.  Entries outside them are the caller's to ignore: the one pattern with a kernel — the space-to-depth masks
+     * {432, 216, 54, 27} with cin_main % 128 == 0 and bf16 operands (ESR_WGRAD_FORM_S2D) — leaves them as they were; every other case
+     * (any other pattern, fp16 operands, cin_main % 128 != 0) adds the true gradient there, as without the hint. */
     int32_t tap_masks[4];
 } esr_wgrad_desc;
 int64_t esr_conv3x3_wgrad_workspace_floats(const esr_wgrad_desc* d);   /* depends on B, H, W, cout, cin_main, lat only; <0: bad argument */
 int esr_conv3x3_wgrad(const esr_wgrad_desc* d, esr_stream_t stream);
+/* Host-only query (no device access, nothing launched), for tests and documentation: how esr_conv3x3_wgrad runs the launch `d` describes.
+ * out[0] / [1] = pixel tiles per image along x / y, [2] = tile shape (0: 8 rows x 32 columns, 1: 16 x 16, 2: 32 x 8 — the latter two only
+ * with ESR_WGRAD_FORM_S2D, for the layer that has fewer tiles so), [3] = slices of the pixel sum (1: the workgroups add straight into dw / db;
+ * more: partial tiles through the workspace and the fold kernel), [4] = ESR_WGRAD_FORM_* bits.  The same checks as esr_conv3x3_wgrad. */
+#define ESR_WGRAD_FORM_LAT27 1       /* the latent segment (lat <= 3) runs as ONE 27-column MFMA tile (channel x tap) */
+#define ESR_WGRAD_FORM_MAIN27 2      /* the main input (cin_main <= 3, no latent, no upsample) runs in that form */
+#define ESR_WGRAD_FORM_S2D 4         /* the space-to-depth kernel: skips the blocks outside the masks, has the 16x16 / 32x8 tiles */
+#define ESR_WGRAD_FORM_FAST_COPY 8   /* one-plane operands without upsample: tile copies from offsets computed once per workgroup */
+int esr_conv3x3_wgrad_tiling(const esr_wgrad_desc* d, int32_t* out);
 /* The weight gradients of MANY layers in one launch (a whole backward pass): with hundreds of layers there are enough
  * (layer, 32-input-channel tile, 32-output-channel tile) blocks to fill the chip without splitting the pixel sum, so the per-layer
  * reduction traffic and launch tails disappear.  `descs` is a HOST array (its workspace fields are ignored); `workspace` is caller-
@@ -373,9 +392,10 @@ int esr_conv3x3_wgrad_batch_run_side(const void* workspace, const esr_wgrad_batc
 int esr_conv3x3_wgrad_side_occupancy(int f16);
 /* A backward pass's layers as SEVERAL launches (one per gradient bucket of a data-parallel job, so that each bucket's all-reduce starts behind its
  * launch and overlaps the launches that follow — torch.distributed over RCCL; the reference's nn.DataParallel reduces after the whole backward,
- * codes/models/SRRaGAN_model.py:418-499): _unit returns the slicing granule the ONE-launch form would use for the whole set; passing it to
- * _part_workspace_bytes / _part_upload for every part keeps each layer's pixel sum cut exactly as in the one launch — the parts' results are
- * bit-identical to it.  _run is the same for parts. */
+ * codes/models/SRRaGAN_model.py:418-499): _unit returns the slicing the ONE-launch form would use for the whole set (an opaque value: the
+ * granule, and whether the set runs the 16x16 / 32x8 tiles because one of its layers is space-to-depth); passing it to _part_workspace_bytes /
+ * _part_upload for every part keeps each layer's tiles and pixel sum cut exactly as in the one launch — the parts' results are bit-identical
+ * to it, whichever parts hold the space-to-depth layers.  _run is the same for parts. */
 int64_t esr_conv3x3_wgrad_batch_unit(const esr_wgrad_desc* descs, int n);
 int64_t esr_conv3x3_wgrad_batch_part_workspace_bytes(const esr_wgrad_desc* descs, int n, int64_t unit);
 int esr_conv3x3_wgrad_batch_part_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan,

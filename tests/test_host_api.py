@@ -324,6 +324,96 @@ def test_cabi_argument_validation_without_a_gpu():
     assert n == 12 * 8 * 9 * 1024 + 2 * 8 * 32               # every tile its own slice (8), 9 x 32 x 32 partial block + bias partials
 
 
+def _wgrad_desc(fmt=0, split=True, B=2, H=16, W=16, cin=128, cout=64, lat=0, ups=1, masks=None):
+    """An esr_wgrad_desc with fake (never dereferenced) pointers and views that cover its channels."""
+    import ctypes as C
+    from esr_hip import _lib
+    v = lambda ncg, h, w, hi=16: _lib.ActView(hi, 32 if split else None, ncg, h, w, 0, 0, fmt)
+    d = _lib.WgradDesc()
+    d.dy, d.x = v((cout + 7) // 8, H, W), v((cin + 7) // 8, H // ups, W // ups)
+    if lat:
+        d.xlat = v(1, H, W)
+    d.lat, d.upsample, d.cout, d.cin_main, d.B, d.H, d.W, d.alpha, d.dw = lat, ups, cout, cin, B, H, W, 1.0, 48
+    if masks:
+        d.tap_masks[:] = masks
+    return d
+
+
+def test_wgrad_refusals_without_a_gpu():
+    """esr_conv3x3_wgrad and its batch form refuse bad descriptors on the host, before the device is touched (fake pointers)."""
+    import ctypes as C
+    from esr_hip import _lib
+    h = _lib.load_library()
+    E_ARG, E_UNSUPPORTED = -1, -2
+    t = (C.c_int32 * 5)()
+
+    def rc(d):
+        d.workspace, d.workspace_floats = 64, 1 << 40
+        r = h.esr_conv3x3_wgrad(C.byref(d), None)
+        assert h.esr_conv3x3_wgrad_tiling(C.byref(d), t) == r       # the query makes the same checks
+        return r
+
+    assert rc(_wgrad_desc(fmt=1, split=True)) == E_UNSUPPORTED       # fp16 hi+lo operands
+    d = _wgrad_desc()
+    d.x.fmt = 1                                                      # mixed element formats
+    assert rc(d) == E_ARG
+    d = _wgrad_desc()
+    d.x.lo = None                                                    # mixed plane counts
+    assert rc(d) == E_ARG
+    assert rc(_wgrad_desc(lat=9)) == E_ARG                           # lat > 8
+    d = _wgrad_desc(ups=2, lat=2)                                    # a latent with upsample
+    d.xlat = _lib.ActView(16, 32, 1, 16, 16, 0, 0, 0)
+    assert rc(d) == E_ARG
+    d = _wgrad_desc(lat=2)
+    d.lat = 0                                                        # xlat given with lat 0
+    assert rc(d) == E_ARG
+    for field, ncg in (('x', 15), ('dy', 7)):                        # views narrower than cin_main / cout
+        d = _wgrad_desc()
+        getattr(d, field).ncg = ncg
+        assert rc(d) == E_ARG, field
+    d = _wgrad_desc(lat=5)
+    d.xlat.ncg = 0
+    assert rc(d) == E_ARG
+    d = _wgrad_desc()
+    need = h.esr_conv3x3_wgrad_workspace_floats(C.byref(d))
+    d.workspace, d.workspace_floats = 64, need - 1                   # too small a workspace
+    assert h.esr_conv3x3_wgrad(C.byref(d), None) == E_ARG
+    # batch: mixed formats, too small a workspace
+    arr = (_lib.WgradDesc * 2)(_wgrad_desc(), _wgrad_desc(split=False))
+    plan = _lib.WgradBatchPlan()
+    assert h.esr_conv3x3_wgrad_batch_upload(arr, 2, 64, 1 << 40, C.byref(plan), None) == E_ARG
+    arr = (_lib.WgradDesc * 2)(_wgrad_desc(), _wgrad_desc(cin=40, cout=24))
+    need = h.esr_conv3x3_wgrad_batch_workspace_bytes(arr, 2)
+    assert need > 0 and h.esr_conv3x3_wgrad_batch_upload(arr, 2, 64, need - 1, C.byref(plan), None) == E_ARG
+    assert h.esr_conv3x3_wgrad_batch(arr, 2, 64, need - 1, None) == E_ARG
+
+
+def test_wgrad_tiling_query():
+    """esr_conv3x3_wgrad_tiling: (tiles x, tiles y, shape, slices, ESR_WGRAD_FORM_* bits) as literals."""
+    import ctypes as C
+    from esr_hip import _lib
+    h = _lib.load_library()
+    S2D = (432, 216, 54, 27)
+
+    def q(**kw):
+        t = (C.c_int32 * 5)()
+        assert h.esr_conv3x3_wgrad_tiling(C.byref(_wgrad_desc(**kw)), t) == 0
+        return tuple(t)
+
+    assert q(B=2, H=9, W=31, cin=13, cout=24) == (1, 2, 0, 4, 0)                     # split: general copies, 4 tiles in 4 slices
+    assert q(split=False, B=2, H=9, W=31, cin=13, cout=24) == (1, 2, 0, 4, 8)        # one plane: fast copies
+    assert q(split=False, B=1, H=8, W=32, cin=40, cout=64) == (1, 1, 0, 1, 8)        # one tile: one slice, straight into dW
+    assert q(B=2, H=9, W=31, cin=40, cout=24, lat=2) == (1, 2, 0, 4, 1)              # 27-column latent tile
+    assert q(split=False, B=2, H=9, W=31, cin=3, cout=24) == (1, 2, 0, 4, 2 | 8)     # main input as the 27-column tile
+    assert q(B=2, H=10, W=14, cin=13, cout=24, ups=2) == (1, 2, 0, 4, 0)
+    assert q(B=2, H=16, W=16, masks=S2D) == (1, 1, 1, 2, 4)                          # space-to-depth: 16x16 tiles
+    assert q(split=False, B=2, H=8, W=8, cin=256, masks=S2D) == (1, 1, 0, 2, 4 | 8)
+    assert q(B=1, H=46, W=4, masks=S2D) == (1, 2, 2, 2, 4)                           # (8 stacked 4x4 maps): 32x8 tiles
+    assert q(B=1, H=16, W=16, lat=2, masks=S2D) == (1, 2, 0, 2, 1 | 4)               # a 27-column latent tile keeps the 8x32 tiles
+    assert q(fmt=1, split=False, B=2, H=16, W=16, masks=S2D) == (1, 2, 0, 4, 8)      # fp16: no space-to-depth kernel
+    assert q(B=2, H=16, W=16, cin=96, masks=S2D) == (1, 2, 0, 4, 0)                  # cin_main % 128 != 0: plain kernel
+
+
 def test_unsupported_generator_configurations_fail_loudly():
     """What the fused kernels do not implement must raise at construction, never run something else silently."""
     import models.modules.architecture as arch

@@ -18,13 +18,22 @@ flags make it send, GUI.py:79-86, :1925-1937):
 where S is the unbiased STD of every 7 x 7 window inside the opened image mask of the gray output (esr_hip.local.patch_std, csrc/esr_local.hip;
 whole-image Masked_STD for the periodicity names without 'local') and initial its value on the FIRST image of the model's output at
 construction.  A flat window's gradient is 0 here, NaN in the reference (torch.std's backward at 0).
-Not part of this build (NotImplementedError): the GUI's scribble / adversarial objectives, the 'Plus' / 'Mag' variants, 'local_*' names
-without STD (the overlap-0.5 patch selection with its non-covered pixels), the local / periodicity objectives in training mode (HR_unpadder)
-or with non_local_Z_optimization on a partial image mask, the '*_localSTD' histogram variants and the automatic histogram temperature.
+'scribble', what the GUI's Draw, brightness, local-TV brush and imprint tools send (GUI.py:1439-1440, :1993-1999; reference :401-448), with an
+image mask, data['desired'], data['scribble_mask'] (1 drawn colour, 2 / 3 brighten / darken by data['brightness_factor'], 4..50 local-TV
+regions): per image the L1 to the desired image (its brightened pixels from the initial output's HSV) on the labels 1-3 plus the 8-neighbour
+TV inside each region (esr_hip.scribble, csrc/esr_scribble.hip).  With non_local_Z_optimization on a partial image mask (the GUI's setting,
+GUI.py:63) the region constraint of :344-364, :385-390, :743-746 comes with it: the Z mask becomes min(1, E + dilate16(image_mask)) and
+1 x l1(out (1 - lm), initial (1 - lm)) holds the output outside the edited region.
+Not part of this build (NotImplementedError): the GUI's adversarial objectives, 'scribble' without an image mask (the reference's plain-L1
+fallback, which the GUI never sends: use 'l1'), the 'Plus' / 'Mag' variants, 'local_*' names without STD (the overlap-0.5 patch selection
+with its non-covered pixels), the local / periodicity / scribble objectives in training mode (HR_unpadder), the region constraint
+(non_local_Z_optimization on a partial image mask) for any objective but 'scribble' (the local and periodicity ones refuse it, the
+whole-image ones ignore it), the '*_localSTD' histogram variants and the automatic histogram temperature.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective).  Like the reference, the loss is the
 mean over the WHOLE batch, so each shard scales its local sum by 1/B_global; the loss history that picks the best iterate is
-all-reduced (one scalar per iteration).
+all-reduced (one scalar per iteration).  The scribble's region constraint contributes its local sum / (B_global 3 H W), and its brightened
+desired image is rank 0's (broadcast once at construction).
 """
 import math
 
@@ -33,6 +42,7 @@ import torch
 
 from esr_hip import dist as esr_dist
 from esr_hip import local as esr_local
+from esr_hip import scribble as esr_scribble
 
 
 def ArcTanH(input_tensor):
@@ -260,13 +270,18 @@ class Z_optimizer():
     MIN_LR = 1e-5
     PATCH_SIZE_4_STD = 7
     SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES) + \
-        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES)
+        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble']
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
                  **unsupported):
         if 'localSTD' in objective:
             hist_objective_config(objective)            # raises, naming the variant
+        if objective == 'scribble' and image_mask is None:
+            raise NotImplementedError("Z objective 'scribble' without an image mask (the reference's plain unmasked L1 fallback, :404-405, which the "
+                                      "GUI never sends) is not part of this build: use 'l1'")
+        if objective == 'scribble' and HR_unpadder is not None:
+            raise NotImplementedError("Z objective 'scribble' in training mode (HR_unpadder): the reference has no initial output there (:346)")
         new_objective = objective in LOCAL_STD_OBJECTIVES or objective in PERIODICITY_OBJECTIVES
         for variant in ('Plus', 'Mag'):
             if variant in objective:
@@ -286,6 +301,17 @@ class Z_optimizer():
             raise NotImplementedError("Z objective '%s': implemented are %s (optionally with image_mask / Z_mask, except 'l1' and the VGG ones); the GUI's other "
                                       "editing objectives are not part of this build" % (objective, self.SUPPORTED))
         assert (image_mask is None) == (Z_mask is None), 'Should either supply both masks or niether'        # (reference :384)
+        if objective == 'scribble':
+            for key in ('desired', 'scribble_mask'):
+                if data is None or data.get(key) is None:
+                    raise ValueError("Z objective 'scribble' needs data['%s']" % key)
+            if np.isin(np.asarray(data['scribble_mask']), (2, 3)).any() and data.get('brightness_factor') is None:
+                raise ValueError("Z objective 'scribble' needs data['brightness_factor'] for its brightness labels 2 / 3")
+        # the region constraint (reference :347, :352-364): the GUI's non_local_Z_optimization on a partial image mask
+        self.non_local_Z_optimization = objective == 'scribble' and bool(unsupported.get('non_local_Z_optimization')) and np.mean(image_mask) < 1
+        if self.non_local_Z_optimization:
+            Z_mask = esr_scribble.rebuilt_z_mask(image_mask)
+        self.Z_mask = Z_mask
         self.objective, self.model, self.data, self.loggers = objective, model, data, loggers
         self.device = model.device
         initial_pre_tanh_Z = None
@@ -331,6 +357,8 @@ class Z_optimizer():
                 self.desired_STD = self.desired_STD + (inc if 'increase' in objective else -inc)
         if 'l1' in objective and data is not None and 'desired' in data:
             self.desired_im = data['desired'].to(self.device)
+        if objective == 'scribble':
+            self._set_scribble(image_mask, data)
         if 'VGG' in objective:           # reference :505-507: L1 between the VGG features of the output and of the desired image
             self.loss = torch.nn.L1Loss().to(self.device)
             if data is not None and 'desired' in data:
@@ -363,6 +391,22 @@ class Z_optimizer():
             return zobj.image_std(self.model.fake_H, self.image_mask, clamp01=True).view(1, -1)
         out = self.model.Output_Batch(within_0_1=True)
         return torch.std(out if self.image_mask is None else out * self.image_mask, dim=(1, 2, 3)).view(1, -1)
+
+    def _set_scribble(self, image_mask, data):
+        """labels, desired image and constraint of the scribble objective (reference :401-448, :385-390), built once"""
+        if 'fake_H' not in self.model.__dict__ or self.model.fake_H is None:
+            raise ValueError("Z objective 'scribble' needs the model's current output (its brightened pixels and the region constraint start from it)")
+        local_bs = self.shard[1] - self.shard[0]
+        initial = self.initial_output
+        if initial.size(0) not in (1, local_bs):
+            raise ValueError("Z objective 'scribble': the model's output has batch %d, the Z search %d on this rank (1 broadcasts)" % (initial.size(0), local_bs))
+        # every rank must edit towards the same image: rank 0's brightened pixels (one broadcast, here only)
+        desired = esr_scribble.desired_image(data['desired'], data['scribble_mask'], initial[0], data.get('brightness_factor'))
+        desired = esr_dist.broadcast_tensor(torch.from_numpy(desired).to(self.device))
+        self.desired_im = desired
+        self.scribble = esr_scribble.ScribbleSpec(data['scribble_mask'], image_mask, desired, constraint=self.non_local_Z_optimization,
+                                                  initial=initial if self.non_local_Z_optimization else None)
+        self.constraining_loss_weight = 1                                   # (reference :447)
 
     def _set_desired_VGG(self, desired):
         self.desired_im = desired.to(self.device)
@@ -441,6 +485,11 @@ class Z_optimizer():
                 Z_loss = Z_loss.reshape(-1) if self.loss.dictionary_not_histogram else Z_loss.reshape(1)
             elif 'l1' in self.objective:
                 Z_loss = (self.output_image - self.desired_im).abs().mean(dim=(1, 2, 3))
+            elif self.objective == 'scribble':
+                # per-image L1 + local TV, and the region constraint's share of l1 over the GLOBAL batch (0 when it is off)
+                H, W = self.model.fake_H.shape[2:]
+                Z_loss, constraint = esr_scribble.scribble_loss(self.model.fake_H, self.scribble,
+                                                                constraint_norm=self.global_batch * self.model.fake_H.size(1) * H * W)
             elif 'VGG' in self.objective:
                 Z_loss = self.loss(self.model.netF(self.output_image), self.GT_HR_VGG).reshape(1)
             elif 'periodicity' in self.objective:
@@ -461,6 +510,8 @@ class Z_optimizer():
             self.latest_Z_loss_values = [v.item() for v in Z_loss.reshape(-1)]
             # mean over the GLOBAL batch (reference :742): this shard contributes sum/B_global
             loss = Z_loss.reshape(-1).sum() / self.global_batch if Z_loss.numel() > 1 else Z_loss.mean() * (self.shard[1] - self.shard[0]) / self.global_batch
+            if self.non_local_Z_optimization:            # (reference :743-746)
+                loss = loss + self.constraining_loss_weight * constraint
             loss.backward()
             self.loss_values.append(esr_dist.all_reduce_mean_scalar(loss.item(), self.device) * esr_dist.world_size())
             self.optimizer.step()

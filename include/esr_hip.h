@@ -480,6 +480,20 @@ int esr_shift_l1_grad(const float* x, int B, int C, int H, int W, const float* m
                       const int32_t* base_y, const float* frac_y, const int32_t* ranges_x, const int32_t* ranges_y, const float* g, float* work, float* dx,
                       int accumulate, esr_stream_t stream);
 
+/* ---- scribble Z objective and its region constraint (csrc/esr_scribble.hip; reference codes/Z_optimization.py:344-364, 385-390, 401-448,
+ * 743-746) ----
+ * x: fp32 [B][C][H][W], read as v = clamp(x, 0, 1); desired [C][H][W] (the desired image D); labels [H][W], one byte per pixel: bit 7 the L1
+ * set (image mask and 0 < scribble < 4), bit 6 the constraint set (outside the image mask), bits 0-5 a TV region id (0 = none); i0: the
+ * initial output [i0_batch][C][H][W] with i0_batch 1 (broadcast) or B, or NULL (bit 6 ignored).
+ * esr_scribble: partial[b][y][5] (doubles) = the row-y parts of (sum_{c,p in L1} |v - D|, the TV pair sums over d = (1,1) and (-1,1), over
+ *   d = (1,0), over d = (0,1): sum_{c,p} [T(p) = T(p + d) > 0] |v(p) - v(p + d)|, and sum_{c,p in constraint} |v - I0|).  The caller sums the
+ *   rows; L_b = l1 / (C H W) + tv_d / (C (H-1)(W-1)) + tv_v / (C (H-1) W) + tv_h / (C H (W-1)).
+ * esr_scribble_grad: dx (+)= d/dx ( sum_b g[b] L_b + g_con sum_{b,c,p in constraint} |v - I0| ).  Deterministic (no atomics). */
+int esr_scribble(const float* x, int B, int C, int H, int W, const float* desired, const uint8_t* labels, const float* i0, int i0_batch, double* partial,
+                 esr_stream_t stream);
+int esr_scribble_grad(const float* x, int B, int C, int H, int W, const float* desired, const uint8_t* labels, const float* i0, int i0_batch, const float* g,
+                      float g_con, float* dx, int accumulate, esr_stream_t stream);
+
 /* ---- the critic's glue: BatchNorm2d (training mode) + LeakyReLU, its gradient and the gradient of its gradient ----
  * Reference: Discriminator_VGG_128 (codes/models/modules/architecture.py:446-508): conv_block = nn.Conv2d -> nn.BatchNorm2d(affine, batch
  * statistics while training; block.py:25-35,129-146) -> LeakyReLU(0.2); the WGAN-GP penalty (codes/models/modules/loss.py:260-279)

@@ -24,13 +24,23 @@ regions): per image the L1 to the desired image (its brightened pixels from the 
 TV inside each region (esr_hip.scribble, csrc/esr_scribble.hip).  With non_local_Z_optimization on a partial image mask (the GUI's setting,
 GUI.py:63) the region constraint of :344-364, :385-390, :743-746 comes with it: the Z mask becomes min(1, E + dilate16(image_mask)) and
 1 x l1(out (1 - lm), initial (1 - lm)) holds the output outside the edited region.
-Not part of this build (NotImplementedError): the GUI's adversarial objectives, 'scribble' without an image mask (the reference's plain-L1
+'random_l1', 'random_l1_limited', 'random_VGG', what the GUI's "produce random alternatives" tool sends (GUI.py:1833-1835; reference :365, :546-550,
+:683-701, :765-766): the samples of the batch are pushed apart from one another.  With D = clamp(out, 0, 1) ('l1') or netF(clamp(out, 0, 1)) ('VGG'):
+  near[b] = min(1, min_{a != b} |D[b] - D[a]|),   Z_loss[b] = -mean_{c,h,w} (near[b] - data['rmse_weight'] |D[b] - initial|) image_mask
+(the second term for '_limited', initial the model's output_image at construction, un-clamped; the mask when masks are given - the 'l1' names
+only), on esr_hip.pairmin / csrc/esr_pairmin.hip, which never builds the reference's [B, B, C, H, W] tensor; an exact tie between two neighbours
+goes to the lowest sample index.  '_limited' starts from randomly perturbed Z (reference :365) and replaces the first loss value by the second.
+Not part of this build (NotImplementedError): 'random_VGG_limited' (the reference subtracts an image from a feature map), the random names with
+'local' (the GUI's LIMITED_RANDOM_WITH_STD_NOT_L1, off as shipped), the random objectives in training mode (HR_unpadder) and 'random_VGG' with
+masks; the GUI's adversarial objectives, 'scribble' without an image mask (the reference's plain-L1
 fallback, which the GUI never sends: use 'l1'), the 'Plus' / 'Mag' variants, 'local_*' names without STD (the overlap-0.5 patch selection
 with its non-covered pixels), the local / periodicity / scribble objectives in training mode (HR_unpadder), the region constraint
 (non_local_Z_optimization on a partial image mask) for any objective but 'scribble' (the local and periodicity ones refuse it, the
 whole-image ones ignore it), the '*_localSTD' histogram variants and the automatic histogram temperature.
 
-Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective).  Like the reference, the loss is the
+Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective - with ONE exception: the random objectives compare
+every sample with every other, so each rank all-gathers the detached D of all ranks once per iteration, esr_hip.dist.all_gather_tensor, and
+differentiates the global loss with respect to its own rows, the neighbour terms of remote rows included).  Like the reference, the loss is the
 mean over the WHOLE batch, so each shard scales its local sum by 1/B_global; the loss history that picks the best iterate is
 all-reduced (one scalar per iteration).  The scribble's region constraint contributes its local sum / (B_global 3 H W), and its brightened
 desired image is rank 0's (broadcast once at construction).
@@ -42,6 +52,7 @@ import torch
 
 from esr_hip import dist as esr_dist
 from esr_hip import local as esr_local
+from esr_hip import pairmin as esr_pairmin
 from esr_hip import scribble as esr_scribble
 
 
@@ -264,13 +275,15 @@ def hist_objective_config(objective):
 # periodicity tools send, GUI.py:1457-1459, :1481-1482, :1925-1937)
 LOCAL_STD_OBJECTIVES = ('local_max_STD', 'local_min_STD', 'local_STD_increase', 'local_STD_decrease', 'local_STD_TV')
 PERIODICITY_OBJECTIVES = tuple(pre + mid + 'periodicity' + post for pre in ('local_STD_', '') for mid in ('nonInt_', '') for post in ('', '_1D'))
+# the random-alternatives objectives (reference :365, :546-550, :683-701, :765-766; the GUI's "produce random alternatives", GUI.py:1833-1835)
+RANDOM_OBJECTIVES = ('random_l1', 'random_l1_limited', 'random_VGG')
 
 
 class Z_optimizer():
     MIN_LR = 1e-5
     PATCH_SIZE_4_STD = 7
     SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES) + \
-        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble']
+        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble'] + list(RANDOM_OBJECTIVES)
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
@@ -282,6 +295,15 @@ class Z_optimizer():
                                       "GUI never sends) is not part of this build: use 'l1'")
         if objective == 'scribble' and HR_unpadder is not None:
             raise NotImplementedError("Z objective 'scribble' in training mode (HR_unpadder): the reference has no initial output there (:346)")
+        if objective.startswith('random_'):
+            if 'local' in objective:
+                raise NotImplementedError("Z objective '%s': the random objectives with 'local' (the GUI's LIMITED_RANDOM_WITH_STD_NOT_L1, off as "
+                                          "shipped; their overlap-0.5 patch selection) are not part of this build" % objective)
+            if 'VGG' in objective and 'limited' in objective:
+                raise NotImplementedError("Z objective '%s': the reference subtracts the initial image from a feature map there (:697); not part of "
+                                          "this build" % objective)
+            if objective in RANDOM_OBJECTIVES and HR_unpadder is not None:
+                raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder) is not part of this build" % objective)
         new_objective = objective in LOCAL_STD_OBJECTIVES or objective in PERIODICITY_OBJECTIVES
         for variant in ('Plus', 'Mag'):
             if variant in objective:
@@ -297,7 +319,8 @@ class Z_optimizer():
         if objective in HIST_OBJECTIVES and auto_set_hist_temperature:
             raise NotImplementedError("Z objective '%s': auto_set_hist_temperature (the temperature search differentiates through the generator "
                                       "twice) is not part of this build" % objective)
-        if objective not in self.SUPPORTED or ((image_mask is not None or Z_mask is not None) and ('l1' in objective or 'VGG' in objective)):
+        if objective not in self.SUPPORTED or ((image_mask is not None or Z_mask is not None) and ('l1' in objective or 'VGG' in objective) and
+                                               objective not in ('random_l1', 'random_l1_limited')):
             raise NotImplementedError("Z objective '%s': implemented are %s (optionally with image_mask / Z_mask, except 'l1' and the VGG ones); the GUI's other "
                                       "editing objectives are not part of this build" % (objective, self.SUPPORTED))
         assert (image_mask is None) == (Z_mask is None), 'Should either supply both masks or niether'        # (reference :384)
@@ -307,6 +330,12 @@ class Z_optimizer():
                     raise ValueError("Z objective 'scribble' needs data['%s']" % key)
             if np.isin(np.asarray(data['scribble_mask']), (2, 3)).any() and data.get('brightness_factor') is None:
                 raise ValueError("Z objective 'scribble' needs data['brightness_factor'] for its brightness labels 2 / 3")
+        self.random = objective in RANDOM_OBJECTIVES
+        if self.random and 'limited' in objective:
+            if data is None or data.get('rmse_weight') is None:
+                raise ValueError("Z objective '%s' needs data['rmse_weight']" % objective)
+            if getattr(model, 'output_image', None) is None:
+                raise ValueError("Z objective '%s' needs the model's current output_image (the image the alternatives stay close to)" % objective)
         # the region constraint (reference :347, :352-364): the GUI's non_local_Z_optimization on a partial image mask
         self.non_local_Z_optimization = objective == 'scribble' and bool(unsupported.get('non_local_Z_optimization')) and np.mean(image_mask) < 1
         if self.non_local_Z_optimization:
@@ -331,7 +360,9 @@ class Z_optimizer():
             eps = torch.finfo(z_now.dtype).eps
             initial_pre_tanh_Z = ArcTanH(torch.clamp(z_now, min=-1 + eps, max=1. - eps))
         self.Z_model = Optimizable_Z(Z_shape=[local_bs, model.num_latent_channels] + list(Z_size), Z_range=Z_range,
-                                     initial_pre_tanh_Z=initial_pre_tanh_Z, Z_mask=Z_mask, random_perturbations=random_Z_inits, device=self.device)
+                                     initial_pre_tanh_Z=initial_pre_tanh_Z, Z_mask=Z_mask, device=self.device,
+                                     random_perturbations=bool((random_Z_inits and 'random' not in objective) or
+                                                               ('random' in objective and 'limited' in objective)))      # (reference :365)
         assert (initial_LR is not None) or (existing_optimizer is not None), 'Should either supply optimizer from previous iterations or initial LR for new optimizer'
         self.image_mask = None if image_mask is None else torch.from_numpy(np.asarray(image_mask, dtype=np.float32)).to(self.device)
         self.local_STD = objective.startswith('local_')
@@ -355,11 +386,17 @@ class Z_optimizer():
                 self.desired_STD = self.desired_STD * (STD_CHANGE_FACTOR if 'increase' in objective else 1 / STD_CHANGE_FACTOR)
             else:
                 self.desired_STD = self.desired_STD + (inc if 'increase' in objective else -inc)
-        if 'l1' in objective and data is not None and 'desired' in data:
+        if 'l1' in objective and not self.random and data is not None and 'desired' in data:
             self.desired_im = data['desired'].to(self.device)
+        if self.random and 'limited' in objective:           # reference :546-548
+            self.initial_image = 1 * model.output_image.detach()
+            if self.initial_image.size(0) not in (1, local_bs):
+                raise ValueError("Z objective '%s': the model's output_image has batch %d, the Z search %d on this rank (1 broadcasts)" %
+                                 (objective, self.initial_image.size(0), local_bs))
+            self.rmse_weight = float(data['rmse_weight'])
         if objective == 'scribble':
             self._set_scribble(image_mask, data)
-        if 'VGG' in objective:           # reference :505-507: L1 between the VGG features of the output and of the desired image
+        if 'VGG' in objective and not self.random:           # reference :505-507: L1 between the VGG features of the output and of the desired image
             self.loss = torch.nn.L1Loss().to(self.device)
             if data is not None and 'desired' in data:
                 self._set_desired_VGG(data['desired'])
@@ -425,9 +462,9 @@ class Z_optimizer():
         if self.objective in HIST_OBJECTIVES and data.get('desired') is not None:
             # a new desired image rebuilds the bins and the desired histogram (the reference's Feed_Desired_Hist_Im is broken for the KDE forms)
             self.loss.Feed_Desired_Hist_Im(self._desired_list(data), data.get('Desired_Im_Mask'))
-        if 'l1' in self.objective:
+        if 'l1' in self.objective and not self.random:
             self.desired_im = data['desired'].to(self.device)
-        if 'VGG' in self.objective:
+        if 'VGG' in self.objective and not self.random:
             self._set_desired_VGG(data['desired'])
 
     def Manage_Model_Grad_Requirements(self, verify_disabled):
@@ -479,7 +516,20 @@ class Z_optimizer():
             self.output_image = self.model.Output_Batch(within_0_1=True)
             if self.model_training:
                 self.output_image = self.HR_unpadder(self.output_image)
-            if self.objective == 'hist' or self.objective in HIST_OBJECTIVES:
+            if self.random:
+                # the one objective that couples the samples: every rank sees the detached D of all ranks (one all-gather, the only data-path
+                # collective of the Z search) and gets its share of the global mean, differentiable with respect to its own rows
+                limited = 'limited' in self.objective
+                if 'VGG' in self.objective:
+                    D, clamp01 = self.model.netF(self.output_image), False
+                else:
+                    D, clamp01 = self.model.fake_H, True         # clamped inside the term, as Output_Batch(within_0_1=True)
+                D_all = None
+                if esr_dist.is_distributed():
+                    D_all = esr_dist.all_gather_tensor(D, [b - a for a, b in (esr_dist.shard_range(self.global_batch, r) for r in range(esr_dist.world_size()))])
+                Z_loss, loss = esr_pairmin.random_share(D, D_all, self.shard[0], clamp01=clamp01, mask=self.image_mask,
+                                                        init=self.initial_image if limited else None, w=self.rmse_weight if limited else 0.0)
+            elif self.objective == 'hist' or self.objective in HIST_OBJECTIVES:
                 # a dictionary gives one value per image; a histogram's KL is one mean over the local [B, bins + 1] (scaled below)
                 Z_loss = self.loss(self.output_image)
                 Z_loss = Z_loss.reshape(-1) if self.loss.dictionary_not_histogram else Z_loss.reshape(1)
@@ -509,7 +559,8 @@ class Z_optimizer():
                 Z_loss = -1 * Z_loss
             self.latest_Z_loss_values = [v.item() for v in Z_loss.reshape(-1)]
             # mean over the GLOBAL batch (reference :742): this shard contributes sum/B_global
-            loss = Z_loss.reshape(-1).sum() / self.global_batch if Z_loss.numel() > 1 else Z_loss.mean() * (self.shard[1] - self.shard[0]) / self.global_batch
+            if loss is None:
+                loss = Z_loss.reshape(-1).sum() / self.global_batch if Z_loss.numel() > 1 else Z_loss.mean() * (self.shard[1] - self.shard[0]) / self.global_batch
             if self.non_local_Z_optimization:            # (reference :743-746)
                 loss = loss + self.constraining_loss_weight * constraint
             loss.backward()
@@ -521,6 +572,10 @@ class Z_optimizer():
             print('Minimum loss observed in %d/%d iteration, discarding subsequent iterations.' % (min_loss_iter + 1, len(self.loss_values)))
             self.Z_model.Z.data = 1 * per_iter_pre_tanh_Z[min_loss_iter]
             self.loss_values = self.loss_values[:min_loss_iter + 1]
+        if self.random and 'limited' in self.objective and len(self.loss_values) > 1:
+            # the first value is close to 0 there (every sample still next to the initial image): a later loss must not look like an increase
+            # against it (reference :765-766, which raises IndexError when a single value is left)
+            self.loss_values[0] = self.loss_values[1]
         self.cur_iter = z_iter + 1
         Z_2_return = self.Z_model.Return_Detached_Z()
         self.Manage_Model_Grad_Requirements(verify_disabled=False)

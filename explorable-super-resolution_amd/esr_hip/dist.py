@@ -2,7 +2,9 @@
 reference's single-process nn.DataParallel (codes/models/networks.py:120-123) which re-broadcasts ~68 MB of parameters every
 forward and gathers outputs / reduces gradients on GPU 0.
 
-  * inference and latent (Z) search shard independent images / Z samples over the ranks — no data-path collective
+  * inference and latent (Z) search shard independent images / Z samples over the ranks — no data-path collective, with one exception: the
+    random-alternatives Z objectives compare every sample with every other, so each rank gathers the others' outputs once per iteration
+    (all_gather_tensor)
   * training all-reduces the generator gradients once per optimiser step, in few large buckets (xGMI is point-to-point:
     ring collectives are per-link bound, so fewer, larger messages; RRDB-23 has 16.7 M parameters = 67 MB fp32)
 Works with backend "gloo" on CPU tensors, which is how the logic is tested without GPUs.
@@ -213,6 +215,25 @@ def broadcast_tensor(t, src=0):
     t = t.contiguous().clone()
     dist.broadcast(t, src)
     return t
+
+
+def all_gather_tensor(t, counts=None):
+    """Every rank's `t` concatenated along dim 0 in rank order, on every rank (detached).  counts[r]: rank r's number of rows (default: the same
+    on every rank); uneven shards are padded to the largest one for the collective and trimmed afterwards.  Identity when not distributed."""
+    t = t.detach().contiguous()
+    if not is_distributed():
+        return t
+    w = world_size()
+    counts = [t.size(0)] * w if counts is None else list(counts)
+    assert len(counts) == w and counts[rank()] == t.size(0), 'all_gather_tensor: counts %s, this rank holds %d rows' % (counts, t.size(0))
+    most = max(counts)
+    if t.size(0) < most:
+        t = torch.cat([t, t.new_zeros((most - t.size(0),) + tuple(t.shape[1:]))], 0)
+    out = t.new_empty((w * most,) + tuple(t.shape[1:]))
+    dist.all_gather(list(out.chunk(w, 0)), t)
+    if all(c == most for c in counts):
+        return out
+    return torch.cat([out[r * most:r * most + c] for r, c in enumerate(counts)], 0)
 
 
 def all_reduce_mean_scalar(value, device=None):

@@ -494,6 +494,25 @@ int esr_scribble(const float* x, int B, int C, int H, int W, const float* desire
 int esr_scribble_grad(const float* x, int B, int C, int H, int W, const float* desired, const uint8_t* labels, const float* i0, int i0_batch, const float* g,
                       float g_con, float* dx, int accumulate, esr_stream_t stream);
 
+/* ---- random-alternatives Z objective (csrc/esr_pairmin.hip; reference codes/Z_optimization.py:683-701) ----
+ * x: fp32 [Bg][C][H][W], the GLOBAL batch, read as I = clamp(x, 0, 1) when clamp01 and as x otherwise (feature tensors); [lo, hi): the rows of
+ * this call; mask: [H][W] or NULL; init: [init_batch][C][H][W] with init_batch 1 (broadcast) or hi - lo, or NULL (then w is ignored).  Per
+ * element e = (c, h, w):  near(r, e) = min(1, min_{a != r} |I_r - I_a|),  v(r, e) = mask(h, w) (near(r, e) - w |I_r - init_r|).
+ * An exact tie between neighbours goes to the LOWEST row index a, the diagonal (distance 1) counting as index r.
+ * esr_pairmin: partial[r - lo][k] (doubles), k < esr_pairmin_blocks(C, H, W): workgroup k's part of sum_e v(r, e); the caller sums over k.
+ *   No atomics: two calls give the same bits.
+ * esr_pairmin_grad: dx [hi - lo][C][H][W] = scale * d/dx[lo:hi] of sum over ALL Bg rows r of sum_e v(r, e): a local row's own term and
+ *   the terms it receives as the nearest neighbour of any row; nothing where the diagonal wins; sign(0) = 0; with clamp01 the gradient
+ *   passes where 0 <= x <= 1.  Gather form, no atomics.
+ * work: scratch of esr_pairmin_work_floats(...) floats (grad = 0 / 1 for the two calls), 0 (work may be NULL) whenever the Bg values of an
+ *   element fit in LDS - Bg up to about 300; larger batches keep them in `work`.  Nothing of size Bg x Bg is allocated in either form. */
+int64_t esr_pairmin_blocks(int C, int H, int W);
+int64_t esr_pairmin_work_floats(int Bg, int C, int H, int W, int lo, int hi, int grad);
+int esr_pairmin(const float* x, int Bg, int C, int H, int W, int lo, int hi, int clamp01, const float* mask, const float* init, int init_batch, float w,
+                float* work, double* partial, esr_stream_t stream);
+int esr_pairmin_grad(const float* x, int Bg, int C, int H, int W, int lo, int hi, int clamp01, const float* mask, const float* init, int init_batch,
+                     float w, float scale, float* work, float* dx, esr_stream_t stream);
+
 /* ---- the critic's glue: BatchNorm2d (training mode) + LeakyReLU, its gradient and the gradient of its gradient ----
  * Reference: Discriminator_VGG_128 (codes/models/modules/architecture.py:446-508): conv_block = nn.Conv2d -> nn.BatchNorm2d(affine, batch
  * statistics while training; block.py:25-35,129-146) -> LeakyReLU(0.2); the WGAN-GP penalty (codes/models/modules/loss.py:260-279)

@@ -30,20 +30,31 @@ GUI.py:63) the region constraint of :344-364, :385-390, :743-746 comes with it: 
 (the second term for '_limited', initial the model's output_image at construction, un-clamped; the mask when masks are given - the 'l1' names
 only), on esr_hip.pairmin / csrc/esr_pairmin.hip, which never builds the reference's [B, B, C, H, W] tensor; an exact tie between two neighbours
 goes to the lowest sample index.  '_limited' starts from randomly perturbed Z (reference :365) and replaces the first loss value by the second.
+'local_Mag_increase' / 'local_Mag_decrease' and '[local_STD_]nonInt_periodicityPlus[_1D]', what the GUI's variance and periodicity tools send
+with its special-behaviour button checked (GUI.py:1926-1937; reference :391-394, :450-455, :470-477, :717-726, :799-806), both with
+data['STD_increment']:
+  'local_Mag_*'            mean over the 49 x P entries of (patches(gray clamp(out_b)) - desired)^2: the half-overlap 7 x 7 patch set of the image
+                           mask (ReturnPatchExtractionMat, overlap 0.5) and, per patch, the initial output's patch (image 0) with its STD
+                           s = max(std, 1/255) moved to s +- increment about the patch mean (esr_hip.patchmag, csrc/esr_patchmag.hip)
+  '...periodicityPlus...'  the periodicity objective with its STD-preserving term replaced by 20 mean_{p,b'} (S - (initial + increment))^2
+(the 'nonInt' form only: the reference's integer periodicityPlus fails, its desired STD is never set).  Both take scribble's region constraint
+(non_local_Z_optimization on a partial image mask: the rebuilt Z mask and w x l1(out (1 - lm), initial (1 - lm)), esr_hip.scribble.region_constraint)
+with w = 255 / 10 x increment^2 ('Mag', :455) or 0.1 ('Plus', :390).  Accepted by exact name: every other 'Plus' / 'Mag' spelling is refused.
 Not part of this build (NotImplementedError): 'random_VGG_limited' (the reference subtracts an image from a feature map), the random names with
 'local' (the GUI's LIMITED_RANDOM_WITH_STD_NOT_L1, off as shipped), the random objectives in training mode (HR_unpadder) and 'random_VGG' with
 masks; the GUI's adversarial objectives, 'scribble' without an image mask (the reference's plain-L1
-fallback, which the GUI never sends: use 'l1'), the 'Plus' / 'Mag' variants, 'local_*' names without STD (the overlap-0.5 patch selection
-with its non-covered pixels), the local / periodicity / scribble objectives in training mode (HR_unpadder), the region constraint
-(non_local_Z_optimization on a partial image mask) for any objective but 'scribble' (the local and periodicity ones refuse it, the
-whole-image ones ignore it), the '*_localSTD' histogram variants and the automatic histogram temperature.
+fallback, which the GUI never sends: use 'l1'), the 'Plus' / 'Mag' spellings other than the six names above, the other 'local_*' names
+without STD (the overlap-0.5 patch selection with its non-covered pixels), the local / periodicity / scribble / patch-magnitude objectives in
+training mode (HR_unpadder), the region constraint (non_local_Z_optimization on a partial image mask) for any objective but 'scribble' and the
+six names above (the other local and periodicity ones refuse it, the whole-image ones ignore it), the '*_localSTD' histogram variants and the
+automatic histogram temperature.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective - with ONE exception: the random objectives compare
 every sample with every other, so each rank all-gathers the detached D of all ranks once per iteration, esr_hip.dist.all_gather_tensor, and
 differentiates the global loss with respect to its own rows, the neighbour terms of remote rows included).  Like the reference, the loss is the
 mean over the WHOLE batch, so each shard scales its local sum by 1/B_global; the loss history that picks the best iterate is
-all-reduced (one scalar per iteration).  The scribble's region constraint contributes its local sum / (B_global 3 H W), and its brightened
-desired image is rank 0's (broadcast once at construction).
+all-reduced (one scalar per iteration).  The region constraint contributes its local sum / (B_global 3 H W); scribble's brightened desired
+image and the patch-magnitude objectives' desired patches are rank 0's (broadcast once at construction).
 """
 import math
 
@@ -53,6 +64,7 @@ import torch
 from esr_hip import dist as esr_dist
 from esr_hip import local as esr_local
 from esr_hip import pairmin as esr_pairmin
+from esr_hip import patchmag as esr_patchmag
 from esr_hip import scribble as esr_scribble
 
 
@@ -277,13 +289,17 @@ LOCAL_STD_OBJECTIVES = ('local_max_STD', 'local_min_STD', 'local_STD_increase', 
 PERIODICITY_OBJECTIVES = tuple(pre + mid + 'periodicity' + post for pre in ('local_STD_', '') for mid in ('nonInt_', '') for post in ('', '_1D'))
 # the random-alternatives objectives (reference :365, :546-550, :683-701, :765-766; the GUI's "produce random alternatives", GUI.py:1833-1835)
 RANDOM_OBJECTIVES = ('random_l1', 'random_l1_limited', 'random_VGG')
+# what the variance and periodicity tools send with the GUI's special-behaviour button checked (GUI.py:1926-1937): the patch-magnitude
+# objectives (reference :391-394, :450-455, :717-722) and periodicityPlus (:470-477, :723-726, :799-806).  Accepted by exact name only.
+MAG_OBJECTIVES = ('local_Mag_increase', 'local_Mag_decrease')
+PLUS_OBJECTIVES = tuple(pre + 'nonInt_periodicityPlus' + post for pre in ('local_STD_', '') for post in ('', '_1D'))
 
 
 class Z_optimizer():
     MIN_LR = 1e-5
     PATCH_SIZE_4_STD = 7
     SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES) + \
-        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble'] + list(RANDOM_OBJECTIVES)
+        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble'] + list(RANDOM_OBJECTIVES) + list(MAG_OBJECTIVES) + list(PLUS_OBJECTIVES)
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
@@ -305,14 +321,20 @@ class Z_optimizer():
             if objective in RANDOM_OBJECTIVES and HR_unpadder is not None:
                 raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder) is not part of this build" % objective)
         new_objective = objective in LOCAL_STD_OBJECTIVES or objective in PERIODICITY_OBJECTIVES
+        special = objective in MAG_OBJECTIVES or objective in PLUS_OBJECTIVES
+        if objective in tuple(name.replace('nonInt_', '') for name in PLUS_OBJECTIVES):
+            raise NotImplementedError("Z objective '%s': the integer periodicityPlus form fails in the reference (its desired STD is set for the 'nonInt' "
+                                      "names only, :473-477); use '%s'" % (objective, objective.replace('periodicityPlus', 'nonInt_periodicityPlus')))
         for variant in ('Plus', 'Mag'):
-            if variant in objective:
+            if variant in objective and not special:
                 raise NotImplementedError("Z objective '%s': the '%s' variant (the GUI's special-behaviour button) is not part of this build" % (objective, variant))
-        if 'local' in objective and 'STD' not in objective:
+        if 'local' in objective and 'STD' not in objective and not special:
             raise NotImplementedError("Z objective '%s': 'local' objectives without STD (their overlap-0.5 greedy patch selection and non-covered pixel "
                                       "set) are not part of this build" % objective)
-        if new_objective and HR_unpadder is not None:
+        if (new_objective or special) and HR_unpadder is not None:
             raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder): the reference has no initial STD there" % objective)
+        if special and (data is None or data.get('STD_increment') is None):
+            raise ValueError("Z objective '%s' needs data['STD_increment']" % objective)
         if new_objective and unsupported.get('non_local_Z_optimization') and image_mask is not None and np.mean(image_mask) < 1:
             raise NotImplementedError("Z objective '%s' with non_local_Z_optimization on a partial image mask (the GUI's region-constraint mode: Z-mask "
                                       "rebuild and constraining L1) is not part of this build" % objective)
@@ -337,7 +359,9 @@ class Z_optimizer():
             if getattr(model, 'output_image', None) is None:
                 raise ValueError("Z objective '%s' needs the model's current output_image (the image the alternatives stay close to)" % objective)
         # the region constraint (reference :347, :352-364): the GUI's non_local_Z_optimization on a partial image mask
-        self.non_local_Z_optimization = objective == 'scribble' and bool(unsupported.get('non_local_Z_optimization')) and np.mean(image_mask) < 1
+        # ('scribble' and the special-behaviour names; every other objective ignores or refuses the flag, see above)
+        self.non_local_Z_optimization = (objective == 'scribble' or special) and bool(unsupported.get('non_local_Z_optimization')) and \
+            image_mask is not None and np.mean(image_mask) < 1
         if self.non_local_Z_optimization:
             Z_mask = esr_scribble.rebuilt_z_mask(image_mask)
         self.Z_mask = Z_mask
@@ -365,12 +389,12 @@ class Z_optimizer():
                                                                ('random' in objective and 'limited' in objective)))      # (reference :365)
         assert (initial_LR is not None) or (existing_optimizer is not None), 'Should either supply optimizer from previous iterations or initial LR for new optimizer'
         self.image_mask = None if image_mask is None else torch.from_numpy(np.asarray(image_mask, dtype=np.float32)).to(self.device)
-        self.local_STD = objective.startswith('local_')
+        self.local_STD = objective.startswith('local_') and objective not in MAG_OBJECTIVES
         if self.local_STD:
             # every 7 x 7 window inside the opened image mask (ReturnPatchExtractionMat with overlap 1, :391-398); no mask: the whole output
             H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
             self.patches = esr_local.PatchSet(image_mask, H, W)
-        if objective in PERIODICITY_OBJECTIVES:
+        if objective in PERIODICITY_OBJECTIVES or objective in PLUS_OBJECTIVES:
             H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
             self.periodicity_pairs = [esr_local.ShiftPair(p, H, W, interpolated='nonInt' in objective) for p in data['periodicity_points']]
         if not self.model_training and 'fake_H' in model.__dict__:
@@ -386,6 +410,8 @@ class Z_optimizer():
                 self.desired_STD = self.desired_STD * (STD_CHANGE_FACTOR if 'increase' in objective else 1 / STD_CHANGE_FACTOR)
             else:
                 self.desired_STD = self.desired_STD + (inc if 'increase' in objective else -inc)
+        if special:
+            self._set_special(image_mask, data)
         if 'l1' in objective and not self.random and data is not None and 'desired' in data:
             self.desired_im = data['desired'].to(self.device)
         if self.random and 'limited' in objective:           # reference :546-548
@@ -444,6 +470,32 @@ class Z_optimizer():
         self.scribble = esr_scribble.ScribbleSpec(data['scribble_mask'], image_mask, desired, constraint=self.non_local_Z_optimization,
                                                   initial=initial if self.non_local_Z_optimization else None)
         self.constraining_loss_weight = 1                                   # (reference :447)
+
+    def _set_special(self, image_mask, data):
+        """what the patch-magnitude and periodicityPlus objectives build once: the desired patches (reference :450-455) or the desired STD
+        (:476-477), and with the region constraint its reference output and weight (:385-390, :455)"""
+        if 'fake_H' not in self.model.__dict__ or self.model.fake_H is None:
+            raise ValueError("Z objective '%s' needs the model's current output (its desired %s from it)" %
+                             (self.objective, 'patches start' if self.objective in MAG_OBJECTIVES else 'STD starts'))
+        inc = float(data['STD_increment'])
+        initial = self.initial_output
+        if self.objective in MAG_OBJECTIVES:
+            # image 0 of the model's output, as the sibling objectives take their initial STD (the reference's view([-1, 1]) accepts batch 1 only)
+            H, W = initial.shape[2:]
+            self.mag = esr_patchmag.MagSpec(image_mask, H, W, initial[0], inc, 1 if 'increase' in self.objective else -1)
+            # every rank must aim at the same patches: rank 0's (one broadcast, here only)
+            if esr_dist.is_distributed():
+                self.mag.replace_desired(esr_dist.broadcast_tensor(self.mag.desired.to(self.device)))
+            self.constraining_loss_weight = 255 / 10 * inc ** 2                 # (reference :455)
+        else:
+            self.desired_STD = self.initial_STD + inc                           # PLUS_MEANS_STD_INCREASE (reference :472, :476-477)
+            self.constraining_loss_weight = 0.1                                 # the default (reference :390)
+        if self.non_local_Z_optimization:
+            local_bs = self.shard[1] - self.shard[0]
+            if initial.size(0) not in (1, local_bs):
+                raise ValueError("Z objective '%s': the model's output has batch %d, the Z search %d on this rank (1 broadcasts)" %
+                                 (self.objective, initial.size(0), local_bs))
+            self.constraint_spec = esr_scribble.constraint_spec(image_mask, initial)
 
     def _set_desired_VGG(self, desired):
         self.desired_im = desired.to(self.device)
@@ -542,6 +594,12 @@ class Z_optimizer():
                                                                 constraint_norm=self.global_batch * self.model.fake_H.size(1) * H * W)
             elif 'VGG' in self.objective:
                 Z_loss = self.loss(self.model.netF(self.output_image), self.GT_HR_VGG).reshape(1)
+            elif self.objective in MAG_OBJECTIVES:
+                Z_loss = esr_patchmag.patch_mag(self.model.fake_H, self.mag)
+            elif self.objective in PLUS_OBJECTIVES:
+                # the STD-preserving term gives way to one that raises the STD by the increment, a scalar over the (local) batch (reference :723-726)
+                Z_loss = esr_local.shift_l1(self.model.fake_H, self.image_mask, self.periodicity_pairs) + \
+                    (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.desired_STD) ** 2).mean()
             elif 'periodicity' in self.objective:
                 # one STD-preserving scalar over the whole (local) batch and all patches, added to every sample (reference :799-815)
                 Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean() + \
@@ -557,6 +615,11 @@ class Z_optimizer():
                 Z_loss = Z_loss.mean(0)
             if 'max' in self.objective:
                 Z_loss = -1 * Z_loss
+            if self.non_local_Z_optimization and self.objective != 'scribble':
+                # the region constraint's share of l1 over the GLOBAL batch, on the scribble kernels
+                H, W = self.model.fake_H.shape[2:]
+                constraint = esr_scribble.region_constraint(self.model.fake_H, self.constraint_spec,
+                                                            norm=self.global_batch * self.model.fake_H.size(1) * H * W)
             self.latest_Z_loss_values = [v.item() for v in Z_loss.reshape(-1)]
             # mean over the GLOBAL batch (reference :742): this shard contributes sum/B_global
             if loss is None:

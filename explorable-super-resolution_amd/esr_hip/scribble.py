@@ -11,6 +11,8 @@ data['scribble_mask'] (1 a drawn colour, 2 / 3 brighten / darken, 4..50 local-TV
       L_b = mean_{c,p} M1 |I_b - D| + sum_{d in (1,1), (1,0), (0,1), (-1,1)} mean_{c, p with p + d inside} [T(p) = T(p + d) > 0] |I_b(p) - I_b(p + d)|
       C   = sum_{b,c,p} (1 - lm) |I_b - I0| / constraint_norm          (F.l1_loss(I (1 - lm), I0 (1 - lm)) for the default B C H W)
   GPU: csrc/esr_scribble.hip (one read of x for all terms and any number of regions); CPU: the defining torch expression.
+* region_constraint(x, image_mask, initial, norm): the constraint C alone, for the other objectives that take it (the patch-magnitude and
+  periodicityPlus ones), on the same kernels with an empty label map.
 """
 import numpy as np
 import torch
@@ -212,6 +214,22 @@ class _Scribble(torch.autograd.Function):
         check(_lib.lib.esr_scribble_grad(xd.data_ptr(), B, Cc, H, W, D.data_ptr(), lab.data_ptr(), 0 if I0 is None else I0.data_ptr(),
                                          0 if I0 is None else I0.size(0), g.data_ptr(), g_con, dx.data_ptr(), 0, stream_ptr()), 'esr_scribble_grad')
         return dx, None, None
+
+
+def constraint_spec(image_mask, initial):
+    """the ScribbleSpec of the region constraint alone (an empty label map, the constrained set 1 - (image_mask > 0)), for the objectives that
+    share scribble's constraint; build it once per edit.  initial: the clamped initial output [1 or B, C, H, W]."""
+    m = _np(image_mask)
+    return ScribbleSpec(np.zeros(m.shape, dtype=np.int64), m, np.zeros((1, initial.size(1)) + m.shape, dtype=np.float32), constraint=True,
+                        initial=initial)
+
+
+def region_constraint(x, image_mask, initial=None, norm=None):
+    """sum_{b,c,p} (1 - lm) |clamp(x, 0, 1) - initial| / norm, lm = (image_mask > 0): F.l1_loss(I (1 - lm), initial (1 - lm)) for the default
+    norm B C H W (reference :385-390); a shard of a larger batch passes B_global C H W.  image_mask: the mask [H, W], or a constraint_spec
+    built from it (then `initial` is the spec's).  On the esr_scribble kernels."""
+    spec = image_mask if isinstance(image_mask, ScribbleSpec) else constraint_spec(image_mask, initial)
+    return scribble_loss(x, spec, constraint_norm=norm)[1]
 
 
 def scribble_loss(x, spec, constraint_norm=None):

@@ -494,6 +494,20 @@ int esr_scribble(const float* x, int B, int C, int H, int W, const float* desire
 int esr_scribble_grad(const float* x, int B, int C, int H, int W, const float* desired, const uint8_t* labels, const float* i0, int i0_batch, const float* g,
                       float g_con, float* dx, int accumulate, esr_stream_t stream);
 
+/* ---- patch-magnitude Z objective (csrc/esr_patchmag.hip; reference codes/Z_optimization.py:391-394, 450-455, 717-722) ----
+ * x: fp32 [B][C][H][W], read as the gray image v = mean_c clamp(x_c, 0, 1); corner_index: int32 [H-6][W-6], the ordinal p in [0, P) of the
+ * selected 7 x 7 window with that top-left corner, -1 (or anything outside [0, P)) where none is selected; desired: fp32 [P][49], one desired
+ * patch per window, its pixels row-major.  H, W >= 7, P >= 1.
+ * esr_patch_mag: partial[b][k] (doubles), k < esr_patch_mag_blocks(H, W): workgroup k's part of sum_p sum_{j < 49} (v(window p, j) -
+ *   desired[p][j])^2; the caller sums over k and divides by 49 P.  No atomics: two calls give the same bits.
+ * esr_patch_mag_grad: dx (+)= d/dx sum_b g[b] / (49 P) sum_{p, j} (v - desired)^2.  Gather form (a pixel walks the at most 49 corners whose
+ *   window covers it), no atomics, deterministic; pixels under no selected window get exactly 0. */
+int64_t esr_patch_mag_blocks(int H, int W);
+int esr_patch_mag(const float* x, int B, int C, int H, int W, const int32_t* corner_index, const float* desired, int P, double* partial,
+                  esr_stream_t stream);
+int esr_patch_mag_grad(const float* x, int B, int C, int H, int W, const int32_t* corner_index, const float* desired, int P, const float* g, float* dx,
+                       int accumulate, esr_stream_t stream);
+
 /* ---- random-alternatives Z objective (csrc/esr_pairmin.hip; reference codes/Z_optimization.py:683-701) ----
  * x: fp32 [Bg][C][H][W], the GLOBAL batch, read as I = clamp(x, 0, 1) when clamp01 and as x otherwise (feature tensors); [lo, hi): the rows of
  * this call; mask: [H][W] or NULL; init: [init_batch][C][H][W] with init_batch 1 (broadcast) or hi - lo, or NULL (then w is ignored).  Per

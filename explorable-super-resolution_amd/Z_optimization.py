@@ -48,6 +48,9 @@ without STD (the overlap-0.5 patch selection with its non-covered pixels), the l
 training mode (HR_unpadder), the region constraint (non_local_Z_optimization on a partial image mask) for any objective but 'scribble' and the
 six names above (the other local and periodicity ones refuse it, the whole-image ones ignore it), the '*_localSTD' histogram variants and the
 automatic histogram temperature.
+JPEG mode (jpeg_extractor given; models/DecompCNN_model.py): the model's fake_H holds DCT coefficients and its image is output_image (0...255),
+Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' in place of 'LR'.  Accepted there: 'l1', 'TV',
+'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', which read Output_Batch(within_0_1=True) only; every other name is refused.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective - with ONE exception: the random objectives compare
 every sample with every other, so each rank all-gathers the detached D of all ranks once per iteration, esr_hip.dist.all_gather_tensor, and
@@ -293,6 +296,8 @@ RANDOM_OBJECTIVES = ('random_l1', 'random_l1_limited', 'random_VGG')
 # objectives (reference :391-394, :450-455, :717-722) and periodicityPlus (:470-477, :723-726, :799-806).  Accepted by exact name only.
 MAG_OBJECTIVES = ('local_Mag_increase', 'local_Mag_decrease')
 PLUS_OBJECTIVES = tuple(pre + 'nonInt_periodicityPlus' + post for pre in ('local_STD_', '') for post in ('', '_1D'))
+# accepted with jpeg_extractor (JPEG mode): they read the model's Output_Batch(within_0_1=True) only, never fake_H
+JPEG_OBJECTIVES = ('l1', 'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease')
 
 
 class Z_optimizer():
@@ -303,7 +308,13 @@ class Z_optimizer():
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
-                 **unsupported):
+                 jpeg_extractor=None, **unsupported):
+        # JPEG mode (the explorable JPEG decoder, models/DecompCNN_model.py): the model's fake_H holds DCT coefficients [B, 64, h, w] and its image
+        # is output_image (0...255); Z lives on the block grid, Z_size = [H/8, W/8]; data carries 'Uncomp' or 'Comp' and 'QF' instead of 'LR'
+        self.jpeg_mode = jpeg_extractor is not None
+        if self.jpeg_mode and (objective not in JPEG_OBJECTIVES or HR_unpadder is not None):
+            raise NotImplementedError("Z objective '%s'%s in JPEG mode (jpeg_extractor given) is not part of this build: implemented there are %s" % (
+                objective, '' if HR_unpadder is None else ' with HR_unpadder (training)', list(JPEG_OBJECTIVES)))
         if 'localSTD' in objective:
             hist_objective_config(objective)            # raises, naming the variant
         if objective == 'scribble' and image_mask is None:
@@ -397,7 +408,7 @@ class Z_optimizer():
         if objective in PERIODICITY_OBJECTIVES or objective in PLUS_OBJECTIVES:
             H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
             self.periodicity_pairs = [esr_local.ShiftPair(p, H, W, interpolated='nonInt' in objective) for p in data['periodicity_points']]
-        if not self.model_training and 'fake_H' in model.__dict__:
+        if not self.model_training and ('fake_H' in model.__dict__ if not self.jpeg_mode else getattr(model, 'output_image', None) is not None):
             self.initial_output = model.Output_Batch(within_0_1=True).detach()
             # every sample's own initial STD (the reference's first_image_only flag is honoured by its 'local' objectives only,
             # Z_optimization.py:617-627): per-sample reference points, so sharding the batch over ranks needs no exchange
@@ -443,15 +454,19 @@ class Z_optimizer():
         self.HR_unpadder = HR_unpadder
         self.STD_PRESERVING_WEIGHT = 100 if 'TV' in objective else 20      # reference Z_optimization.py:508-509 (TV), :471 (others)
 
+    def _image(self):
+        """the model's output image before the clamp to [0, 1]: fake_H itself for the SR model, output_image / 255 in JPEG mode"""
+        return self.model.output_image / 255 if self.jpeg_mode else self.model.fake_H
+
     def Masked_STD(self, first_image_only=False):
         if self.local_STD:
             # the STD of every selected 7 x 7 window [P, B] (reference :616-627); first_image_only: image 0 only, [P, 1]
             x = self.model.fake_H[:1] if first_image_only else self.model.fake_H
             return esr_local.patch_std(x, self.patches)
         # whole-image objectives: the STD of EVERY sample, [1, B], whatever the flag says (as the reference, see __init__)
-        if self.model.fake_H.is_cuda:        # clamp, mask and the two moments in one pass over the batch (esr_img_stats)
+        if self._image().is_cuda:            # clamp, mask and the two moments in one pass over the batch (esr_img_stats)
             from esr_hip import zobj
-            return zobj.image_std(self.model.fake_H, self.image_mask, clamp01=True).view(1, -1)
+            return zobj.image_std(self._image(), self.image_mask, clamp01=True).view(1, -1)
         out = self.model.Output_Batch(within_0_1=True)
         return torch.std(out if self.image_mask is None else out * self.image_mask, dim=(1, 2, 3)).view(1, -1)
 
@@ -531,11 +546,13 @@ class Z_optimizer():
 
     def _local_data(self):
         d = dict(self.data)
-        lr = d['LR']
-        if lr.size(0) == self.global_batch and self.global_batch > 1:
-            d['LR'] = lr[self.shard[0]:self.shard[1]]
-        elif lr.size(0) == 1:
-            d['LR'] = lr.expand(self.shard[1] - self.shard[0], -1, -1, -1)
+        keys = [k for k in ('Uncomp', 'Comp', 'QF') if k in d] if self.jpeg_mode else ['LR']
+        for k in keys:
+            t = d[k]
+            if t.size(0) == self.global_batch and self.global_batch > 1:
+                d[k] = t[self.shard[0]:self.shard[1]]
+            elif t.size(0) == 1:
+                d[k] = t.expand(self.shard[1] - self.shard[0], *([-1] * (t.dim() - 1)))
         return d
 
     def optimize(self):
@@ -606,7 +623,7 @@ class Z_optimizer():
                     esr_local.shift_l1(self.model.fake_H, self.image_mask, self.periodicity_pairs)
             elif 'TV' in self.objective:
                 Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean(0) + \
-                    (TV_Loss(self.model.fake_H, self.image_mask, clamp01=True) if not self.model_training else
+                    (TV_Loss(self._image(), self.image_mask, clamp01=True) if not self.model_training else
                      TV_Loss(self.output_image if self.image_mask is None else self.output_image * self.image_mask))
             else:
                 Z_loss = self.Masked_STD()

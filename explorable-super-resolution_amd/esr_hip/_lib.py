@@ -244,6 +244,10 @@ _SIGS = {
     'esr_unpack_grad_nchw_norm': (C.c_int, [C.POINTER(ActView), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'esr_maxpool2x2': (C.c_int, [C.POINTER(ActView), C.POINTER(ActView), C.c_int, C.c_void_p]),
     'esr_maxpool2x2_grad': (C.c_int, [C.POINTER(ActView), C.POINTER(ActView), C.c_int, C.POINTER(ActView), C.c_int, C.c_void_p]),
+    'esr_jpeg_compress': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ActView), C.c_void_p]),
+    'esr_jpeg_extract': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'esr_jpeg_extract_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'esr_jpeg_compress_grad': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

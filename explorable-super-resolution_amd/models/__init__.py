@@ -2,9 +2,9 @@
 import importlib
 
 # opt['model'] -> (module, class).  'srgan' (codes/models/SRGAN_model.py) cannot run in the reference (undefined `need_HR`, :127-130); both
-# GAN names resolve to the live SRRaGAN wrapper here.  'dncnn' (explorable JPEG decoding) is outside the RRDB+CEM hot path.
-_WRAPPERS = {'srragan': ('SRRaGAN_model', 'SRRaGANModel'), 'srgan': ('SRRaGAN_model', 'SRRaGANModel')}
-_OUT_OF_SCOPE = {'dncnn': 'Model [dncnn] (explorable JPEG decoding) is outside the RRDB+CEM hot path'}
+# GAN names resolve to the live SRRaGAN wrapper here.  'dncnn' is explorable JPEG decoding (codes/models/DecompCNN_model.py), inference surface.
+_WRAPPERS = {'srragan': ('SRRaGAN_model', 'SRRaGANModel'), 'srgan': ('SRRaGAN_model', 'SRRaGANModel'), 'dncnn': ('DecompCNN_model', 'DecompCNNModel')}
+_OUT_OF_SCOPE = {}
 
 
 def create_model(opt, *kargs, **kwargs):

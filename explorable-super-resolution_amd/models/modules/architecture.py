@@ -18,6 +18,7 @@ import torch.nn as nn
 from . import block as B
 from esr_hip.engine import RRDBEngine
 from esr_hip import vgg as esr_vgg
+from esr_hip import dncnn as esr_dncnn
 
 
 class RRDBNet(nn.Module):
@@ -268,3 +269,101 @@ class VGGFeatureExtractor(nn.Module):
         if self.use_input_norm:
             x = (x - self.mean) / self.std
         return self.features(x)
+
+
+class DnCNN(nn.Module):
+    """Generator of the explorable JPEG decoder (reference architecture.py:109-214, generator form): Conv2d(latent + in_nc -> n_channels, bias) /
+    ReLU, depth - 2 times Conv2d(no bias) / BatchNorm2d(eps 1e-4, momentum 0.95) / LeakyReLU(0.01), Conv2d(-> out_nc, no bias), Sigmoid; the
+    input is [Z | quantised coefficients], Z re-concatenated in front of the features at the first conv ('first_layer') or at every conv
+    ('all_layers'); the output is quantised coefficients + (sigmoid - 0.5).  `dncnn` is the reference's ModuleList, so state_dict keys
+    (dncnn.0.weight, dncnn.3.running_mean, ...) and positional checkpoint loading are the reference's.
+
+    On the GPU in eval() the conv chain runs on the library's kernels (esr_hip/dncnn.py: forward and input gradient, BatchNorm folded, frozen
+    weights; set_precision picks 'split' — fp32-class, the default — or 'bf16').  CPU tensors and training mode run the stock modules."""
+
+    def __init__(self, n_channels, depth, kernel_size=3, in_nc=64, out_nc=64, norm_type='batch', act_type='leakyrelu', latent_input=None,
+                 num_latent_channels=None, discriminator=False, expected_input_size=None, chroma_generator=False, spectral_norm=False,
+                 pooling_no_FC=False, avoid_padding=None, output_layer=None):
+        super(DnCNN, self).__init__()
+        assert act_type == 'leakyrelu'
+        assert norm_type in ['batch', 'instance', 'layer', None]
+        assert output_layer in ['Sigmoid', 'ReLU', None]
+        if discriminator:
+            raise NotImplementedError('DnCNN(discriminator=True): the DnCNN critic belongs to training the JPEG model, which this build does not do')
+        if chroma_generator:
+            raise NotImplementedError('DnCNN(chroma_generator=True): this build runs the Y-channel (grey-scale) model only')
+        if norm_type in ('layer', 'instance'):
+            raise NotImplementedError("DnCNN(norm_type=%r): 'batch' (folded into the convs in eval mode) or None" % (norm_type,))
+        if avoid_padding:
+            raise NotImplementedError(
+                "DnCNN(avoid_padding=True), the padding-free form: not part of this build. With latent_input='all_layers' the reference's own forward "
+                'fails there (the latent is not cropped with the shrinking maps: "Sizes of tensors must match"), and the shipped training settings '
+                'use padding. define_G reads avoid_padding = not bool(network_G.padding): in the options file set network_G "padding": 1.')
+        if kernel_size != 3:
+            raise NotImplementedError('DnCNN(kernel_size=%r): 3' % (kernel_size,))
+        self.discriminator_net = False
+        self.chroma_generator = False
+        self.margins = 0
+        self.latent_input = latent_input
+        self.num_latent_channels = num_latent_channels
+        if latent_input not in ['all_layers', 'first_layer'] or num_latent_channels is None:
+            self.num_latent_channels = 0
+        lat_rest = self.num_latent_channels * (self.latent_input == 'all_layers')
+        esr_dncnn.check_shapes(n_channels, depth, in_nc, out_nc, self.num_latent_channels, lat_rest)
+        layers = [nn.Conv2d(in_nc + self.num_latent_channels, n_channels, kernel_size=3, padding=1, bias=True), nn.ReLU(inplace=True)]
+        for _ in range(1, depth - 1):
+            layers.append(nn.Conv2d(n_channels + lat_rest, n_channels, kernel_size=3, padding=1, bias=False))
+            if norm_type == 'batch':
+                layers.append(nn.BatchNorm2d(n_channels, eps=0.0001, momentum=0.95))
+            layers.append(nn.LeakyReLU(inplace=True))
+        layers.append(nn.Conv2d(n_channels + lat_rest, out_nc, kernel_size=3, padding=1, bias=False))
+        if output_layer == 'Sigmoid':
+            layers.append(nn.Sigmoid())
+        elif output_layer == 'ReLU':
+            layers.append(nn.ReLU())
+        self.output_layer = output_layer
+        self.dncnn = nn.ModuleList(layers)
+        self._engine = None
+        self._precision = 'split'
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = esr_dncnn.DnCNNEngine(self.dncnn, self.num_latent_channels, self.latent_input, precision=self._precision)
+        return self._engine
+
+    def set_precision(self, precision):
+        """'split' (default): bf16 hi+lo operands, fp32-class outputs and gradients; 'bf16': one plane, one MFMA per product."""
+        assert precision in ('split', 'bf16')
+        self._precision = precision
+        if self._engine is not None:
+            self._engine.set_precision(precision)
+
+    def on_kernels(self, x):
+        return x.is_cuda and not self.training
+
+    def pre_output(self, x):
+        """The last conv's output, before the output layer, for the input [Z | quantised coefficients] (HIP engine; GPU, eval mode)."""
+        return esr_dncnn.dncnn_forward(self.engine, x)
+
+    def _torch_chain(self, x, stop_before_output):
+        latent_input, x = torch.split(x, [self.num_latent_channels, x.size(1) - self.num_latent_channels], dim=1)
+        for i, module in enumerate(self.dncnn):
+            if stop_before_output and isinstance(module, (nn.Sigmoid, nn.ReLU)) and i == len(self.dncnn) - 1 and self.output_layer is not None:
+                break
+            if self.num_latent_channels > 0 and isinstance(module, nn.Conv2d) and (self.latent_input == 'all_layers' or i == 0):
+                x = torch.cat([latent_input, x], dim=1)
+            x = module(x)
+        return x
+
+    def forward(self, x):
+        quantized_coeffs = x[:, self.num_latent_channels:]
+        if self.on_kernels(x):
+            y = self.pre_output(x)
+            if self.output_layer == 'Sigmoid':
+                y = torch.sigmoid(y)
+            elif self.output_layer == 'ReLU':
+                y = torch.relu(y)
+        else:
+            y = self._torch_chain(x, False)
+        return quantized_coeffs + (y - 0.5)

@@ -80,7 +80,13 @@ def define_G(opt, CEM=None, num_latent_channels=None, **kwargs):
                             upsample_mode='upconv',
                             latent_input=(opt_net['latent_input'] + '_' + opt_net['latent_input_domain']) if opt_net['latent_input'] is not None else None,
                             num_latent_channels=num_latent_channels)
-    elif which_model in ('sr_resnet', 'DnCNN', 'MSRResNet'):
+    elif which_model == 'DnCNN':
+        if kwargs.get('chroma_mode', False):
+            raise NotImplementedError('Generator model [DnCNN] with chroma_mode: this build runs the Y-channel (grey-scale) model only')
+        netG = arch.DnCNN(n_channels=opt_net['nf'], depth=opt_net['nb'], in_nc=64, out_nc=64, norm_type=opt_net['norm_type'],
+                          latent_input=opt_net['latent_input'], num_latent_channels=num_latent_channels, chroma_generator=False,
+                          avoid_padding=not bool(opt_net['padding']), output_layer='Sigmoid')
+    elif which_model in ('sr_resnet', 'MSRResNet'):
         raise NotImplementedError('Generator model [{:s}] is outside the RRDB+CEM hot path of this build'.format(which_model))
     else:
         raise NotImplementedError('Generator model [{:s}] not recognized'.format(which_model))

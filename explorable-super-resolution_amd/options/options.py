@@ -1,6 +1,7 @@
 """Option files: JSON with `//` comments -> nested dict -> NoneDict, with the path / batch-size derivations the drivers rely on.
-Same entry points as the reference's codes/options/options.py (parse, save, dict_to_nonedict, NoneDict); the explorable-JPEG
-branches and the machine-specific dataset-root rewriting of the reference are not reproduced (outside the RRDB+CEM path).
+Same entry points as the reference's codes/options/options.py (parse, save, dict_to_nonedict, NoneDict).  parse(..., JPEG=True) resolves the
+explorable-JPEG files' ModelY dictionaries (Y-channel model; chroma=True is refused); the machine-specific dataset-root rewriting of the
+reference is not reproduced.
 """
 import json
 import os
@@ -64,10 +65,20 @@ def parse(opt_path, is_train=True, batch_size_multiplier=None, **kwargs):
 
 def parse_conf(opt_path, is_train=True, batch_size_multiplier=None, **kwargs):
     name = kwargs.get('name')
-    if kwargs.get('JPEG'):
-        raise NotImplementedError('explorable JPEG decoding options are outside the RRDB+CEM path')
+    JPEG_run = bool(kwargs.get('JPEG'))
+    if JPEG_run and kwargs.get('chroma'):
+        raise NotImplementedError('parse(JPEG=True, chroma=True): this build runs the Y-channel (grey-scale) JPEG model only')
     opt = json.loads(_strip_comments(opt_path), object_pairs_hook=OrderedDict)
     opt = dictionary_values_choice(opt, 'PhaseInit' if kwargs.get('initialization') else 'PhaseGAN')
+    if JPEG_run:                                     # reference options.py:68-85, Y-channel branch
+        opt = dictionary_values_choice(opt, 'ModelY')
+        opt['input_downsampling'] = 1
+        if opt['name'][:len('JPEG/')] != 'JPEG/':
+            opt['name'] = os.path.join('JPEG', opt['name'])
+        opt['scale'] = 8 * opt['input_downsampling']
+        opt['network_G'].setdefault('residual', 1)
+        if is_train and 'input_type' not in opt['network_D']:
+            opt['network_D']['input_type'] = 'DCT_premult' if opt['network_D']['DCT_D'] else 'image'
     scale = opt['scale']
     opt['timestamp'] = get_timestamp()
     opt['is_train'] = is_train
@@ -78,7 +89,7 @@ def parse_conf(opt_path, is_train=True, batch_size_multiplier=None, **kwargs):
             dataset['phase'] = phase
             dataset['scale'] = scale
             is_lmdb = False
-            for field in ('dataroot_HR', 'dataroot_LR'):
+            for field in ('dataroot_Uncomp' if JPEG_run else 'dataroot_HR', 'dataroot_LR'):
                 if dataset.get(field) is not None:
                     dataset[field] = os.path.expanduser(os.path.join(root, dataset[field]))
                     is_lmdb = is_lmdb or dataset[field].endswith('lmdb')
@@ -90,7 +101,7 @@ def parse_conf(opt_path, is_train=True, batch_size_multiplier=None, **kwargs):
     for key, path in opt['path'].items():
         if path:
             opt['path'][key] = os.path.expanduser(path)
-    if name is not None:
+    if not JPEG_run and name is not None:
         opt['name'] = os.path.join(name)
     experiments_root = os.path.join(opt['path']['root'], 'experiments', opt['name'])
     opt['path']['experiments_root'] = experiments_root

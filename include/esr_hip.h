@@ -628,6 +628,35 @@ typedef struct {
 int esr_run(const esr_cmd* cmds, int n, int* failed, esr_stream_t stream);
 int64_t esr_cmd_bytes(void);       /* sizeof(esr_cmd): lets a binding check its struct layout */
 
+/* ---- explorable JPEG decoding: the 8x8 block DCT consistency layer (codes/JPEG_module/JPEG.py, Y channel, block size 8) ----
+ * Images are fp32 [B][1][H][W] (0...255), coefficients fp32 [B][64][h][w] with h = H/8, w = W/8 and channel 8u + v = vertical frequency u,
+ * horizontal frequency v of the orthonormal DCT-II of the block at (i, j).  `qtab` is fp32 [B][64], row-major (u, v), one table per image
+ * (JPEG.Set_Q_Table, JPEG.py:74-86).  The reference evaluates each transform by broadcasting against a [B,8,8,h,w,8] temporary per axis
+ * (JPEG.py:108-120); here one launch per call moves each side once, in 16-byte accesses where the addresses allow (image and coefficient
+ * pointers 16-byte aligned, w a multiple of 4; any w works).  Images must be 16-byte aligned.  No atomics: two calls give the same bits.
+ * B and h up to 65535 (ESR_E_UNSUPPORTED beyond).
+ *
+ * esr_jpeg_compress — JPEG.forward with compress=True (JPEG.py:131-163): coef = DCT(x - 128) / qtab, torch.round (half to even) when
+ *   round != 0.  H, W multiples of 8 (ESR_E_ARG otherwise).  act_out (optional; then coef may be NULL): the same values written into
+ *   groups [0, 8) of the view in its format and planes (interior pixels only, as the conv kernels store), so that the generator's first conv
+ *   reads them without a second pass (esr_pack_nchw). */
+int esr_jpeg_compress(const float* x, int B, int H, int W, const float* qtab, int round, float* coef, const esr_act_view* act_out,
+                      esr_stream_t stream);
+/* esr_jpeg_extract — JPEG.forward with compress=False (JPEG.py:193-197) with the generator's tail in front of it
+ *   (codes/models/modules/architecture.py:206, 214 after nn.Sigmoid): c = coef when y == NULL, else c = coef + (sigmoid(y) - 0.5) with y the
+ *   last conv's fp32 [B][64][h][w] output and coef the quantised input; coef_out (optional) receives c;
+ *   img[b][0][8i + r][8j + s] = 128 + iDCT(c * qtab). */
+int esr_jpeg_extract(const float* coef, const float* y, int B, int h, int w, const float* qtab, float* coef_out, float* img,
+                     esr_stream_t stream);
+/* Adjoint of esr_jpeg_extract (autograd through JPEG.py:193-197 and the sigmoid): d_coef = qtab * DCT(d_img) — the transform is orthonormal,
+ *   so the adjoint of the inverse is the forward transform — and, with y, d_y = d_coef * s (1 - s), s = sigmoid(y).  Either output may be NULL
+ *   (not both); d_y needs y. */
+int esr_jpeg_extract_grad(const float* d_img, const float* y, int B, int h, int w, const float* qtab, float* d_coef, float* d_y,
+                          esr_stream_t stream);
+/* Adjoint of the non-quantising compressor (autograd through JPEG.py:131-156): d_x = iDCT(d_coef / qtab).  (With rounding the reference's
+ *   gradient is zero: no kernel.) */
+int esr_jpeg_compress_grad(const float* d_coef, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream);
+
 int esr_version(void);
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 // Backward-pass helpers that are not convolutions: elementwise / pooling ops on the channel-group activation layout and the
 // adjoints of the module-boundary packing (replicate padding, latent bilinear /sf).  HBM-bound streaming kernels: one 16-byte
-// pixel vector (8 channels) per thread, coalesced along W.
+// pixel vector (8 channels) per thread, coalesced along W.  They read and write the layout through the accessors of esr_common.h.
 //
 // Reference operations whose gradients these implement (autograd in the reference):
 //   nearest upsample            codes/models/modules/block.py:293-300 (Upsampler)          -> sum-pool s x s
@@ -12,88 +12,48 @@
 
 namespace {
 
-// 16-bit element of either plane format -> fp32 (fmt: ESR_FMT_BF16 / ESR_FMT_F16, uniform per view)
-__device__ __forceinline__ float el2f(uint32_t bits, int fmt) { return fmt == ESR_FMT_F16 ? h2f(bits) : bf2f(bits); }
-
-__device__ __forceinline__ void unpack8(const uint4* hi, const uint4* lo, long long o, float (&v)[8], int fmt) {
-    const uint4 h = hi[o];
-    const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = el2f(hw[e] & 0xFFFF, fmt); v[2 * e + 1] = el2f(hw[e] >> 16, fmt); }
-    if (lo) {
-        const uint4 l = lo[o];
-        const uint32_t lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[2 * e] += el2f(lw[e] & 0xFFFF, fmt); v[2 * e + 1] += el2f(lw[e] >> 16, fmt); }
-    }
-}
-
-__device__ __forceinline__ void pack8(uint4* hi, uint4* lo, long long o, const float (&v)[8], int fmt) {
-    uint32_t h[8], l[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (fmt == ESR_FMT_F16) { h[e] = f2h(v[e]); l[e] = f2h(v[e] - h2f(h[e])); }
-        else split_bf16(v[e], h[e], l[e]);
-    }
-    hi[o] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-    if (lo) lo[o] = make_uint4(l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16));
-}
-
 // out = alpha * A + beta * sumpool_s(Bv), optionally * leaky_relu'(mask).  A / mask / out share out's size; Bv is s x larger.
 __global__ void act_combine_kernel(DView A, float alpha, DView Bv, float beta, int s, DView M, float slope, DView out, int H, int W, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (b, cg, y, x) over the interior
     if (idx >= total) return;
-    const int x = (int)(idx % W);
-    long long t = idx / W;
-    const int y = (int)(t % H);
-    t /= H;
-    const int cg = (int)(t % out.ncg);
-    const int b = (int)(t / out.ncg);
-    const long long pix = (long long)(y + 1) * (W + 2) + (x + 1);
+    const ActPos q = act_pos(idx, out.ncg, H, W);
+    const int b = q.b, cg = q.cg, y = q.y, x = q.x;
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (A.hi) {
         float a8[8];
-        unpack8(A.hi, A.lo, b * A.bs + cg * A.cs + pix, a8, A.fmt);
+        load8(A.hi, A.lo, act_off(A.bs, A.cs, W, b, cg, y, x), A.fmt, a8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = alpha * a8[e];
     }
     if (Bv.hi) {
-        const int Wb = W * s + 2;
         for (int dy = 0; dy < s; ++dy)
             for (int dx = 0; dx < s; ++dx) {
                 float b8[8];
-                unpack8(Bv.hi, Bv.lo, b * Bv.bs + cg * Bv.cs + (long long)(y * s + dy + 1) * Wb + (x * s + dx + 1), b8, Bv.fmt);
+                load8(Bv.hi, Bv.lo, act_off(Bv.bs, Bv.cs, W * s, b, cg, y * s + dy, x * s + dx), Bv.fmt, b8);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaf(beta, b8[e], v[e]);
             }
     }
     if (M.hi) {
-        const uint4 h = M.hi[b * M.bs + cg * M.cs + pix];
-        const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
+        const uint4 h = M.hi[act_off(M.bs, M.cs, W, b, cg, y, x)];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const uint32_t bits = (e & 1) ? (hw[e >> 1] >> 16) : (hw[e >> 1] & 0xFFFF);
+            const uint32_t bits = elem16(h, e);
             if ((bits & 0x8000u) || !(bits & 0x7FFFu)) v[e] *= slope;   // stored activation <= 0
         }
     }
-    pack8((uint4*)out.hi, (uint4*)out.lo, b * out.bs + cg * out.cs + pix, v, out.fmt);
+    store8(mut(out.hi), mut(out.lo), act_off(out.bs, out.cs, W, b, cg, y, x), v, out.fmt);
 }
 
 // Adjoint of the conv kernel's pixel-shuffle store (esr_hip.h): dst[g*r^2 + s][y][x] = src[g][r*y + s/r][r*x + s%r]; one 16-byte vector per thread
 __global__ void pixel_unshuffle_kernel(DView src, int r, DView dst, int H, int W, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (b, dst group, y, x) over dst's interior
     if (idx >= total) return;
-    const int x = (int)(idx % W);
-    long long t = idx / W;
-    const int y = (int)(t % H);
-    t /= H;
-    const int cg = (int)(t % dst.ncg);
-    const int b = (int)(t / dst.ncg);
+    const ActPos q = act_pos(idx, dst.ncg, H, W);
+    const int b = q.b, cg = q.cg, y = q.y, x = q.x;
     const int g = cg / (r * r), sp = cg % (r * r);
-    const long long so = b * src.bs + g * src.cs + (long long)(r * y + sp / r + 1) * (r * W + 2) + (r * x + sp % r + 1);
-    const long long d_o = b * dst.bs + cg * dst.cs + (long long)(y + 1) * (W + 2) + (x + 1);
-    ((uint4*)dst.hi)[d_o] = src.hi[so];
-    if (dst.lo) ((uint4*)dst.lo)[d_o] = src.lo ? src.lo[so] : make_uint4(0, 0, 0, 0);
+    const long long so = act_off(src.bs, src.cs, r * W, b, g, r * y + sp / r, r * x + sp % r);
+    store_raw8(mut(dst.hi), mut(dst.lo), act_off(dst.bs, dst.cs, W, b, cg, y, x), load_raw8(src.hi, src.lo, so));
 }
 
 // Adjoint of esr_pack_nchw: act-layout gradient (interior (h+2pad)/down x (w+2pad)/down) -> fp32 NCHW gradient of the
@@ -105,23 +65,17 @@ __global__ void unpack_grad_kernel(DView G, float* __restrict__ dst, long long d
                                    int accumulate, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (b, channel group, y, x) of the un-padded source
     if (idx >= total) return;
-    const int x = (int)(idx % w);
-    long long t = idx / w;
-    const int y = (int)(t % h);
-    t /= h;
-    const int ncg = (nc + 7) >> 3;
-    const int cg = (int)(t % ncg);
-    const int b = (int)(t / ncg);
+    const ActPos q = act_pos(idx, (nc + 7) >> 3, h, w);
+    const int b = q.b, cg = q.cg, y = q.y, x = q.x;
     const int hp = h + 2 * pad, wp = w + 2 * pad;
     // padded-frame positions mapping onto (y, x)
     const int y_lo = y == 0 ? 0 : y + pad, y_hi = y == h - 1 ? hp - 1 : y + pad;
     const int x_lo = x == 0 ? 0 : x + pad, x_hi = x == w - 1 ? wp - 1 : x + pad;
     const int Hd = hp / down, Wd = wp / down;
-    const long long base = b * G.bs + cg * G.cs;
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto add_at = [&](int yy, int xx, float wgt) {   // acc += wgt * the 8 gradient channels at act-layout interior pixel (yy, xx)
         float g8[8];
-        unpack8(G.hi, G.lo, base + (long long)(yy + 1) * (Wd + 2) + (xx + 1), g8, G.fmt);
+        load8(G.hi, G.lo, act_off(G.bs, G.cs, Wd, b, cg, yy, xx), G.fmt, g8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(wgt, g8[e], acc[e]);
     };
@@ -198,12 +152,10 @@ __global__ void grad_absmax_kernel(DView v, long long plane, long long total, ui
         const long long p = idx % plane, t = idx / plane;
         const int cg = (int)(t % v.ncg), b = (int)(t / v.ncg);
         const uint4 h = v.hi[b * v.bs + cg * v.cs + p];
-        const uint32_t w[4] = {h.x, h.y, h.z, h.w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t a0 = w[e] & 0x7FFFu, a1 = (w[e] >> 16) & 0x7FFFu;      // |fp16| bit patterns order like the magnitudes
-            m = m > a0 ? m : a0;
-            m = m > a1 ? m : a1;
+        for (int e = 0; e < 8; ++e) {
+            const uint32_t a = elem16(h, e) & 0x7FFFu;      // |fp16| bit patterns order like the magnitudes
+            m = m > a ? m : a;
         }
     }
 #pragma unroll
@@ -241,16 +193,15 @@ __global__ void grad_scale_kernel(DView src, DView dst, long long plane, long lo
     const int cg = (int)(t % dst.ncg), b = (int)(t / dst.ncg);
     const long long si = b * src.bs + cg * src.cs + p, di = b * dst.bs + cg * dst.cs + p;
     const uint4* const sp[2] = {src.hi, src.lo};
-    uint4* const dp[2] = {(uint4*)dst.hi, (uint4*)dst.lo};
+    uint4* const dp[2] = {mut(dst.hi), mut(dst.lo)};
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl) {
         if (!sp[pl] || !dp[pl]) continue;
         const uint4 h = sp[pl][si];
-        const uint32_t w[4] = {h.x, h.y, h.z, h.w};
-        uint32_t o[4];
+        uint32_t o[8];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2h(h2f(w[e] & 0xFFFF) * f) | (f2h(h2f(w[e] >> 16) * f) << 16);
-        dp[pl][di] = make_uint4(o[0], o[1], o[2], o[3]);
+        for (int e = 0; e < 8; ++e) o[e] = f2h(h2f(elem16(h, e)) * f);
+        dp[pl][di] = pack16x8(o);
     }
 }
 

@@ -23,8 +23,6 @@ int g_cem_wave_target = 0;          // > 0 (instrumented build only): strips a l
 int g_cem_wave_rmin = 0;            // > 0 (instrumented build only): downscale strip height, output rows
 int g_cem_filt_rmin = 18;           // shortest LR-filter strip (a strip starts K - 1 rows early: 26 / 18 / 13 rows 25 / 21 / 24 us at configs[1])
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // Workgroup -> (tile column, tile row, image plane) for the tiled kernels.  Workgroups are dispatched in linear order (x fastest), round-robin
 // over the 8 XCDs, each with its own L2: XCD x sweeps a CONTIGUOUS run of the row-major (plane, tile row, tile column) order, so that the
 // window overlap of neighbouring tiles (1.45x of g for the x4 downscale) is served by the L2 that fetched it (round 4 counters: 0.299 GB

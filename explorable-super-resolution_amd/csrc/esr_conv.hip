@@ -837,19 +837,17 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, int dim0, int d
     const int cp = ks / 9, t = ks % 9;
     const int cg = 2 * cp + (lane >> 5);
     const int mch = mmap[m * 32 + (lane & 31)];
-    uint32_t hi[8], lo[8];
+    float v8[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int kch = cg < ncg_in ? kmap[cg * 8 + e] : -1;
         float v = 0.f;
         if (kch >= 0 && mch >= 0)
             v = transposed ? w[((long long)kch * dim1 + mch) * 9 + (8 - t)] : w[((long long)mch * dim1 + kch) * 9 + t];
-        if (f16) { hi[e] = f2h(v * scale); lo[e] = f2h(v * scale - h2f(hi[e])); }
-        else split_bf16(v * scale, hi[e], lo[e]);
+        v8[e] = v * scale;
     }
-    uint4* o = out + ((size_t)(ks * mtiles + m) * npl) * 64 + lane;
-    o[0] = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
-    if (npl == 2) o[64] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
+    uint4* o = out + ((size_t)(ks * mtiles + m) * npl) * 64 + lane;      // the lo plane of a tile follows its hi plane
+    store8(o, npl == 2 ? o + 64 : nullptr, 0, v8, f16 ? ESR_FMT_F16 : ESR_FMT_BF16);
 }
 
 // many weight tensors in one launch (a training step re-packs every layer after the optimiser's update): block b packs tile map[b].y of entry
@@ -888,16 +886,11 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackEntry
     for (int v = threadIdx.x; v < 9 * 64; v += 256) {
         const int t = v >> 6, lane = v & 63;
         const float* src = tile + (lane & 31) * PITCH + (lane >> 5) * 72 + t;
-        uint32_t hi[8], lo[8];
+        float x8[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float x = src[c * 9];
-            if (e.f16) { hi[c] = f2h(x * e.scale); lo[c] = f2h(x * e.scale - h2f(hi[c])); }
-            else split_bf16(x * e.scale, hi[c], lo[c]);
-        }
+        for (int c = 0; c < 8; ++c) x8[c] = src[c * 9] * e.scale;
         uint4* o = e.out + ((size_t)((cp * 9 + t) * e.mtiles + mt) * e.npl) * 64 + lane;
-        o[0] = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
-        if (e.npl == 2) o[64] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
+        store8(o, e.npl == 2 ? o + 64 : nullptr, 0, x8, e.f16 ? ESR_FMT_F16 : ESR_FMT_BF16);
     }
 }
 
@@ -1056,24 +1049,18 @@ int launch_epi(const ConvArgs& a, int epi, hipStream_t s) {
 __global__ void splitk_finish_kernel(const float* __restrict__ ws, int S, long long slab, DView out, int C, int H, int W, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    const int x = (int)(idx % W);
-    long long t = idx / W;
-    const int y = (int)(t % H);
-    t /= H;
-    const int ncg = C >> 3;
-    const int cg = (int)(t % ncg);
-    const int b = (int)(t / ncg);
-    uint32_t vh[8], vl[8];
+    const ActPos q = act_pos(idx, C >> 3, H, W);
+    const int b = q.b, cg = q.cg, y = q.y, x = q.x;
+    float v8[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float* p = ws + ((long long)(b * C + cg * 8 + e) * H + y) * W + x;
         float v = 0.f;
         for (int k = 0; k < S; ++k) v += p[k * slab];
-        split_bf16(v, vh[e], vl[e]);
+        v8[e] = v;
     }
-    const long long o = b * out.bs + cg * out.cs + (long long)(y + 1) * (W + 2) + (x + 1);
-    ((uint4*)out.hi)[o] = make_uint4(vh[0] | (vh[1] << 16), vh[2] | (vh[3] << 16), vh[4] | (vh[5] << 16), vh[6] | (vh[7] << 16));
-    if (out.lo) ((uint4*)out.lo)[o] = make_uint4(vl[0] | (vl[1] << 16), vl[2] | (vl[3] << 16), vl[4] | (vl[5] << 16), vl[6] | (vl[7] << 16));
+    // always bf16, not out.fmt: the host takes the split-K path for bf16 launches only (`plain`); the format is named here so that the choice shows
+    store8(mut(out.hi), mut(out.lo), act_off(out.bs, out.cs, W, b, cg, y, x), v8, ESR_FMT_BF16);
 }
 
 }  // namespace

@@ -31,37 +31,12 @@ static inline CView to_cview(const esr_act_view* v) {
 template <bool S2D>
 __device__ __forceinline__ long long voff(const CView& v, int b, int cg, int y, int x) {
     if (S2D) return b * v.bs + (long long)(16 * (cg >> 2) + 4 * (2 * (y & 1) + (x & 1)) + (cg & 3)) * v.cs + (long long)((y >> 1) + 1) * (v.W + 2) + ((x >> 1) + 1);
-    return b * v.bs + (long long)cg * v.cs + (long long)(y + 1) * (v.W + 2) + (x + 1);
+    return act_off(v.bs, v.cs, v.W, b, cg, y, x);
 }
-__device__ __forceinline__ void ld8(const CView& v, long long o, float* f) {
-    const uint4 h = v.hi[o];
-    const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
-    if (v.lo) {
-        const uint4 l = v.lo[o];
-        const uint32_t lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const uint32_t hb = (e & 1) ? (hw[e >> 1] >> 16) : (hw[e >> 1] & 0xFFFF), lb = (e & 1) ? (lw[e >> 1] >> 16) : (lw[e >> 1] & 0xFFFF);
-            f[e] = v.fmt == ESR_FMT_F16 ? h2f(hb) + h2f(lb) : bf2f(hb) + bf2f(lb);
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const uint32_t hb = (e & 1) ? (hw[e >> 1] >> 16) : (hw[e >> 1] & 0xFFFF);
-            f[e] = v.fmt == ESR_FMT_F16 ? h2f(hb) : bf2f(hb);
-        }
-    }
-}
-__device__ __forceinline__ void st8(const CView& v, long long o, const float* f) {
-    uint32_t vh[8], vl[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (v.fmt == ESR_FMT_F16) { vh[e] = f2h(f[e]); vl[e] = f2h(f[e] - h2f(vh[e])); }
-        else split_bf16(f[e], vh[e], vl[e]);
-    }
-    v.hi[o] = make_uint4(vh[0] | (vh[1] << 16), vh[2] | (vh[3] << 16), vh[4] | (vh[5] << 16), vh[6] | (vh[7] << 16));
-    if (v.lo) v.lo[o] = make_uint4(vl[0] | (vl[1] << 16), vl[2] | (vl[3] << 16), vl[4] | (vl[5] << 16), vl[6] | (vl[7] << 16));
-}
+// the shared accessors (the global ones of esr_common.h) on a CView
+__device__ __forceinline__ Raw8 load_raw8(const CView& v, long long o) { return ::load_raw8(v.hi, v.lo, o); }
+__device__ __forceinline__ void decode8(const CView& v, const Raw8& r, float (&f)[8]) { ::decode8(r, v.lo != nullptr, v.fmt, f); }
+__device__ __forceinline__ void store8(const CView& v, long long o, const float (&f)[8]) { ::store8(v.hi, v.lo, o, f, v.fmt); }
 
 // zero the border vectors adjacent to stored pixel (py, px) of the plane that offset `o` points into (py, px: 0-based interior coordinates of
 // the STORED plane of size Hs x Ws): the threads of the frame's neighbours cover the whole one-pixel border exactly once or twice
@@ -109,24 +84,6 @@ __device__ __forceinline__ BnStat bn_stat(const double* sums, long long gc, doub
     return o;
 }
 
-// raw 16-byte vectors of one pixel (hi [+ lo]) and their decoding: loads are issued for several pixels before the first is decoded
-struct Raw8 { uint4 h, l; };
-__device__ __forceinline__ Raw8 ldraw(const CView& v, long long o) {
-    Raw8 r;
-    r.h = v.hi[o];
-    r.l = v.lo ? v.lo[o] : make_uint4(0, 0, 0, 0);
-    return r;
-}
-__device__ __forceinline__ void dec8(const CView& v, const Raw8& r, float* f) {
-    const uint32_t hw[4] = {r.h.x, r.h.y, r.h.z, r.h.w}, lw[4] = {r.l.x, r.l.y, r.l.z, r.l.w};
-    const bool lo = v.lo != nullptr;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint32_t hb = (e & 1) ? (hw[e >> 1] >> 16) : (hw[e >> 1] & 0xFFFF), lb = (e & 1) ? (lw[e >> 1] >> 16) : (lw[e >> 1] & 0xFFFF);
-        f[e] = v.fmt == ESR_FMT_F16 ? h2f(hb) + (lo ? h2f(lb) : 0.f) : bf2f(hb) + (lo ? bf2f(lb) : 0.f);
-    }
-}
-
 // MODE 0: sum y, sum y^2                      (forward statistics)
 // MODE 1: sum dyb, sum dyb*xh                 (backward)
 // MODE 2: sum u, sum u*xh, sum u*dyb          (double backward)
@@ -165,14 +122,14 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const BnArgs a) {
     };
     auto add = [&](const Raw8& ry, const Raw8& rd, const Raw8& ru) {
         float fy[8], fd[8], fu[8];
-        dec8(a.y, ry, fy);
+        decode8(a.y, ry, fy);
         if (MODE == 0) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) { acc[0][e] += fy[e]; acc[1][e] += fy[e] * fy[e]; }
             return;
         }
-        dec8(a.dz, rd, fd);
-        if (MODE == 2) dec8(a.u, ru, fu);
+        decode8(a.dz, rd, fd);
+        if (MODE == 2) decode8(a.u, ru, fu);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float pre = sc[e] * fy[e] + sh[e];
@@ -187,18 +144,18 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const BnArgs a) {
         long long oy0, od0, ou0, oy1, od1, ou1;
         offs(p, oy0, od0, ou0);
         offs(p + step, oy1, od1, ou1);
-        Raw8 ry0 = ldraw(a.y, oy0), ry1 = ldraw(a.y, oy1), rd0{}, rd1{}, ru0{}, ru1{};
-        if (MODE >= 1) { rd0 = ldraw(a.dz, od0); rd1 = ldraw(a.dz, od1); }
-        if (MODE == 2) { ru0 = ldraw(a.u, ou0); ru1 = ldraw(a.u, ou1); }
+        Raw8 ry0 = load_raw8(a.y, oy0), ry1 = load_raw8(a.y, oy1), rd0{}, rd1{}, ru0{}, ru1{};
+        if (MODE >= 1) { rd0 = load_raw8(a.dz, od0); rd1 = load_raw8(a.dz, od1); }
+        if (MODE == 2) { ru0 = load_raw8(a.u, ou0); ru1 = load_raw8(a.u, ou1); }
         add(ry0, rd0, ru0);
         add(ry1, rd1, ru1);
     }
     if (p < a.npg) {
         long long oy0, od0, ou0;
         offs(p, oy0, od0, ou0);
-        Raw8 ry0 = ldraw(a.y, oy0), rd0{}, ru0{};
-        if (MODE >= 1) rd0 = ldraw(a.dz, od0);
-        if (MODE == 2) ru0 = ldraw(a.u, ou0);
+        Raw8 ry0 = load_raw8(a.y, oy0), rd0{}, ru0{};
+        if (MODE >= 1) rd0 = load_raw8(a.dz, od0);
+        if (MODE == 2) ru0 = load_raw8(a.u, ou0);
         add(ry0, rd0, ru0);
     }
     constexpr int RS = 256 + 16;                     // row pitch: the four rows a wave folds at once fall into disjoint bank windows
@@ -256,9 +213,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs a) {
         const int pc = live[i] ? p : 0;
         ys[i] = pc / a.W;
         xs[i] = pc - ys[i] * a.W;
-        ry[i] = ldraw(a.y, voff<false>(a.y, b, cg, ys[i], xs[i]));
-        if (MODE >= 1) rd[i] = ldraw(a.dz, voff<S2D>(a.dz, b, cg, ys[i], xs[i]));
-        if (MODE == 2) ru[i] = ldraw(a.u, voff<false>(a.u, b, cg, ys[i], xs[i]));
+        ry[i] = load_raw8(a.y, voff<false>(a.y, b, cg, ys[i], xs[i]));
+        if (MODE >= 1) rd[i] = load_raw8(a.dz, voff<S2D>(a.dz, b, cg, ys[i], xs[i]));
+        if (MODE == 2) ru[i] = load_raw8(a.u, voff<false>(a.u, b, cg, ys[i], xs[i]));
     }
     __shared__ float fin[FIN ? 16 : 1];
     if constexpr (FIN) {
@@ -318,9 +275,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs a) {
         if (!live[i]) continue;
         const int yy = ys[i], xx = xs[i];
         float fy[8], fd[8], fu[8], o0[8], o1[8];
-        dec8(a.y, ry[i], fy);
-        if (MODE >= 1) dec8(a.dz, rd[i], fd);
-        if (MODE == 2) dec8(a.u, ru[i], fu);
+        decode8(a.y, ry[i], fy);
+        if (MODE >= 1) decode8(a.dz, rd[i], fd);
+        if (MODE == 2) decode8(a.u, ru[i], fu);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const bool ok = okc[e];
@@ -343,12 +300,12 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs a) {
         // every result is the input of a conv (or weight-gradient) launch: write its zero border too
         const long long os = voff<S2D>(a.out0, b, cg, yy, xx), op = voff<false>(MODE == 2 ? a.out1 : a.out0, b, cg, yy, xx);
         if (MODE == 0 || MODE == 2) {
-            st8(a.out0, os, o0);
+            store8(a.out0, os, o0);
             if (S2D) zero_border(a.out0, os, yy >> 1, xx >> 1, a.H / 2, a.W / 2);
             else zero_border(a.out0, os, yy, xx, a.H, a.W);
         }
-        if (MODE == 1) { st8(a.out0, op, o0); zero_border(a.out0, op, yy, xx, a.H, a.W); }
-        if (MODE == 2) { st8(a.out1, op, o1); zero_border(a.out1, op, yy, xx, a.H, a.W); }
+        if (MODE == 1) { store8(a.out0, op, o0); zero_border(a.out0, op, yy, xx, a.H, a.W); }
+        if (MODE == 2) { store8(a.out1, op, o1); zero_border(a.out1, op, yy, xx, a.H, a.W); }
     }
 }
 

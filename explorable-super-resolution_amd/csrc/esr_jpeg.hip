@@ -116,16 +116,10 @@ __global__ __launch_bounds__(256) void dct_fwd_kernel(const float* __restrict__ 
         }
     }
     if (act_hi && j < nb) {  // thread (u, j): the eight v of one pixel vector of group u
-        uint32_t vh[8], vl[8];
+        float s[8];
 #pragma unroll
-        for (int v = 0; v < 8; ++v) {
-            const float s = XO[(hi5 * 8 + v) * OP + j];
-            if (act_fmt == ESR_FMT_F16) { vh[v] = f2h(s); vl[v] = f2h(s - h2f(vh[v])); }
-            else split_bf16(s, vh[v], vl[v]);
-        }
-        const long long o = b * act_bs + hi5 * act_cs + (long long)(i + 1) * (w + 2) + (j0 + j + 1);
-        act_hi[o] = make_uint4(vh[0] | (vh[1] << 16), vh[2] | (vh[3] << 16), vh[4] | (vh[5] << 16), vh[6] | (vh[7] << 16));
-        if (act_lo) act_lo[o] = make_uint4(vl[0] | (vl[1] << 16), vl[2] | (vl[3] << 16), vl[4] | (vl[5] << 16), vl[6] | (vl[7] << 16));
+        for (int v = 0; v < 8; ++v) s[v] = XO[(hi5 * 8 + v) * OP + j];
+        store8(act_hi, act_lo, act_off(act_bs, act_cs, w, b, hi5, i, j0 + j), s, act_fmt);
     }
 }
 

@@ -28,12 +28,6 @@ constexpr int LT_X = 64, LT_Y = 16;          // corner / pixel tile per workgrou
 constexpr int LS_X = LT_X + LP - 1, LS_Y = LT_Y + LP - 1;
 constexpr int L_THREADS = 256;
 
-__device__ __forceinline__ float gray(const float* __restrict__ img, int C, long long plane, long long off) {
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += fminf(fmaxf(img[c * plane + off], 0.f), 1.f);
-    return s / (float)C;
-}
-
 __global__ __launch_bounds__(L_THREADS) void patch_std_kernel(const float* __restrict__ x, int C, int H, int W, const uint8_t* __restrict__ corners,
                                                                 float* __restrict__ S, float* __restrict__ M) {
     __shared__ float v[LS_Y][LS_X];

@@ -2,25 +2,19 @@
 // ([B][CG][H+2][W+2][8] bf16 hi/lo planes with a zero border), with the CEM eval-mode replicate padding
 // (codes/CEM/CEMnet.py:286-295) and the latent bilinear /sf of RRDBNet.forward (codes/models/modules/architecture.py:284)
 // fused into the read.  HBM-bound streaming kernels: one 16-byte vector store per thread, coalesced along W.
+// The layout's arithmetic (offsets, index decomposition, encode / decode of a pixel vector) is esr_common.h's.
 #include "esr_common.h"
 
 namespace {
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ void pack_nchw_kernel(const float* __restrict__ src, long long sbs, int C, int h, int w, int c0, int nc, int pad, int down, uint4* hi,
                                  uint4* lo, long long bs, long long cs, int ncg, int Hd, int Wd, int fmt, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    const int Wp = Wd + 2, Hp = Hd + 2;
-    const int X = (int)(idx % Wp);
-    long long t = idx / Wp;
-    const int Y = (int)(t % Hp);
-    t /= Hp;
-    const int cg = (int)(t % ncg);
-    const int b = (int)(t / ncg);
-    uint32_t vh[8], vl[8];
-    const bool border = (X == 0) || (Y == 0) || (X == Wp - 1) || (Y == Hp - 1);
+    const ActPos q = act_pos(idx, ncg, Hd + 2, Wd + 2);   // over the padded frame
+    const int b = q.b, cg = q.cg, Y = q.y, X = q.x;
+    const bool border = frame_border(Y, X, Hd, Wd);
+    float v8[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int ch = cg * 8 + e;
@@ -42,37 +36,24 @@ __global__ void pack_nchw_kernel(const float* __restrict__ src, long long sbs, i
                 v = (1.f - ly) * ((1.f - lx) * p[r0 + q0] + lx * p[r0 + q1]) + ly * ((1.f - lx) * p[r1 + q0] + lx * p[r1 + q1]);
             }
         }
-        if (fmt == ESR_FMT_F16) { vh[e] = f2h(v); vl[e] = f2h(v - h2f(vh[e])); }
-        else split_bf16(v, vh[e], vl[e]);
+        v8[e] = v;
     }
-    const long long o = b * bs + cg * cs + (long long)Y * Wp + X;
-    hi[o] = make_uint4(vh[0] | (vh[1] << 16), vh[2] | (vh[3] << 16), vh[4] | (vh[5] << 16), vh[6] | (vh[7] << 16));
-    if (lo) lo[o] = make_uint4(vl[0] | (vl[1] << 16), vl[2] | (vl[3] << 16), vl[4] | (vl[5] << 16), vl[6] | (vl[7] << 16));
+    store8(hi, lo, act_off_frame(bs, cs, Wd, b, cg, Y, X), v8, fmt);
 }
 
 __global__ void unpack_nchw_kernel(const uint4* __restrict__ hi, const uint4* __restrict__ lo, long long bs, long long cs, int H, int W,
                                    int nc, float* __restrict__ dst, int fmt, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (b, cg, y, x)
     if (idx >= total) return;
-    const int ncg = (nc + 7) / 8;
-    const int x = (int)(idx % W);
-    long long t = idx / W;
-    const int y = (int)(t % H);
-    t /= H;
-    const int cg = (int)(t % ncg);
-    const int b = (int)(t / ncg);
-    const long long o = b * bs + cg * cs + (long long)(y + 1) * (W + 2) + (x + 1);
-    const uint4 h = hi[o];
-    const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
-    uint32_t lw[4] = {0, 0, 0, 0};
-    if (lo) { const uint4 l = lo[o]; lw[0] = l.x; lw[1] = l.y; lw[2] = l.z; lw[3] = l.w; }
+    const ActPos q = act_pos(idx, (nc + 7) / 8, H, W);
+    const int b = q.b, cg = q.cg, y = q.y, x = q.x;
+    float v8[8];
+    load8(hi, lo, act_off(bs, cs, W, b, cg, y, x), fmt, v8);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int ch = cg * 8 + e;
         if (ch >= nc) break;
-        const uint32_t hb = (e & 1) ? (hw[e >> 1] >> 16) : (hw[e >> 1] & 0xFFFF);
-        const uint32_t lb = (e & 1) ? (lw[e >> 1] >> 16) : (lw[e >> 1] & 0xFFFF);
-        dst[((long long)(b * nc + ch) * H + y) * W + x] = fmt == ESR_FMT_F16 ? h2f(hb) + h2f(lb) : bf2f(hb) + bf2f(lb);
+        dst[((long long)(b * nc + ch) * H + y) * W + x] = v8[e];
     }
 }
 

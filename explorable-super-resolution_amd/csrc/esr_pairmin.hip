@@ -28,7 +28,6 @@ constexpr size_t P_LDS_LIMIT = 160 * 1024;
 
 // the columns hold x as it is: the clamp is one v_med3 per read, and the backward finds its gate [0 <= x <= 1] next to the value
 __device__ __forceinline__ float rd(float v, bool clamp) { return clamp ? __builtin_amdgcn_fmed3f(v, 0.f, 1.f) : v; }
-__device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }      // torch's |.|' = 0 at 0
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -25,12 +25,6 @@ constexpr int MT_X = 64, MT_Y = 16;          // corner / pixel tile per workgrou
 constexpr int MS_X = MT_X + MP - 1, MS_Y = MT_Y + MP - 1;
 constexpr int M_THREADS = 256;
 
-__device__ __forceinline__ float gray(const float* __restrict__ img, int C, long long plane, long long off) {
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += fminf(fmaxf(img[c * plane + off], 0.f), 1.f);
-    return s / (float)C;
-}
-
 __global__ __launch_bounds__(M_THREADS) void patch_mag_kernel(const float* __restrict__ x, int C, int H, int W, const int32_t* __restrict__ index,
                                                                 const float* __restrict__ desired, int P, double* __restrict__ partial) {
     __shared__ float v[MS_Y][MS_X];

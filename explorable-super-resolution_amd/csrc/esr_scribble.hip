@@ -20,9 +20,6 @@ namespace {
 constexpr int S_THREADS = 256;
 constexpr uint8_t LAB_L1 = 0x80, LAB_CON = 0x40, LAB_TV = 0x3f;
 
-__device__ __forceinline__ float c01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-__device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }      // torch's |.|' = 0 at 0
-
 __global__ __launch_bounds__(S_THREADS) void scribble_kernel(const float* __restrict__ x, int C, int H, int W, const float* __restrict__ D,
                                                               const uint8_t* __restrict__ lab, const float* __restrict__ i0, int i0_batch,
                                                               double* __restrict__ partial) {
@@ -47,12 +44,12 @@ __global__ __launch_bounds__(S_THREADS) void scribble_kernel(const float* __rest
         float a[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < C; ++c) {
             const float* p = img + c * plane + o;
-            const float v = c01(*p);
+            const float v = clamp_unit(*p);
             if (l & LAB_L1) a[0] += fabsf(v - D[c * plane + o]);
-            if (m_dr) a[1] += fabsf(v - c01(p[W + 1]));
-            if (m_ur) a[1] += fabsf(v - c01(p[1 - W]));
-            if (m_d) a[2] += fabsf(v - c01(p[W]));
-            if (m_r) a[3] += fabsf(v - c01(p[1]));
+            if (m_dr) a[1] += fabsf(v - clamp_unit(p[W + 1]));
+            if (m_ur) a[1] += fabsf(v - clamp_unit(p[1 - W]));
+            if (m_d) a[2] += fabsf(v - clamp_unit(p[W]));
+            if (m_r) a[3] += fabsf(v - clamp_unit(p[1]));
             if (con) a[4] += fabsf(v - ref[c * plane + o]);
         }
 #pragma unroll
@@ -107,7 +104,7 @@ __global__ __launch_bounds__(S_THREADS) void scribble_grad_kernel(const float* _
     for (int c = 0; c < C; ++c) {
         const float* p = img + c * plane + o;
         const float raw = *p;
-        const float v = c01(raw);
+        const float v = clamp_unit(raw);
         float acc = 0.f;
         if (l & LAB_L1) acc += w_l1 * sgn(v - D[c * plane + o]);
         if (nb) {
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(S_THREADS) void scribble_grad_kernel(const float* _
             for (int dy = -1; dy <= 1; ++dy)
                 for (int dxx = -1; dxx <= 1; ++dxx) {
                     if (dy == 0 && dxx == 0) continue;
-                    if (nb >> k & 1u) acc += (dy == 0 ? w_h : (dxx == 0 ? w_v : w_d)) * sgn(v - c01(p[dy * W + dxx]));
+                    if (nb >> k & 1u) acc += (dy == 0 ? w_h : (dxx == 0 ? w_v : w_d)) * sgn(v - clamp_unit(p[dy * W + dxx]));
                     ++k;
                 }
         }

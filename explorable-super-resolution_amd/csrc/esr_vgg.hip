@@ -1,35 +1,21 @@
 // The VGG feature extractor's glue between the conv launches (codes/models/modules/architecture.py:658-705, torchvision's VGG `features`):
 // the input normalisation (x - mean) / std fused into the NCHW -> activation-layout pack, its adjoint fused into the gradient unpack, and the
 // 2x2 stride-2 max pool with its backward.  The convolutions themselves (and their ReLU, act_slope = 0) are esr_conv3x3 launches.
-// All four kernels are HBM-bound streaming kernels: one thread per 16-byte pixel vector (8 channels) of the destination.
+// All four kernels are HBM-bound streaming kernels: one thread per 16-byte pixel vector (8 channels) of the destination; they read and
+// write the layout through the accessors of esr_common.h.
 #include "esr_common.h"
 
 namespace {
-
-// element e (0..7) of a 16-byte vector of 16-bit values
-__device__ __forceinline__ uint32_t lane16(const uint4& v, int e) {
-    const uint32_t w = (e >> 1) == 0 ? v.x : (e >> 1) == 1 ? v.y : (e >> 1) == 2 ? v.z : v.w;
-    return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
-__device__ __forceinline__ float val16(uint32_t h, int fmt) { return fmt == ESR_FMT_F16 ? h2f(h) : bf2f(h); }
-__device__ __forceinline__ uint4 pack8(const uint32_t (&e)[8]) {
-    return make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
-}
 
 // fp32 NCHW [B][C][h][w] -> act view (h x w interior, zero border), v = (x - mean[c]) / std[c] (mean / std NULL: v = x)
 __global__ void pack_norm_kernel(const float* __restrict__ src, int C, int h, int w, const float* __restrict__ mean, const float* __restrict__ stdv,
                                  uint4* hi, uint4* lo, long long bs, long long cs, int ncg, int fmt, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    const int Wp = w + 2, Hp = h + 2;
-    const int X = (int)(idx % Wp);
-    long long t = idx / Wp;
-    const int Y = (int)(t % Hp);
-    t /= Hp;
-    const int cg = (int)(t % ncg);
-    const int b = (int)(t / ncg);
-    const bool border = X == 0 || Y == 0 || X == Wp - 1 || Y == Hp - 1;
-    uint32_t vh[8], vl[8];
+    const ActPos q = act_pos(idx, ncg, h + 2, w + 2);   // over the padded frame
+    const int b = q.b, cg = q.cg, Y = q.y, X = q.x;
+    const bool border = frame_border(Y, X, h, w);
+    float v8[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int ch = cg * 8 + e;
@@ -38,27 +24,18 @@ __global__ void pack_norm_kernel(const float* __restrict__ src, int C, int h, in
             v = src[(((long long)b * C + ch) * h + (Y - 1)) * w + (X - 1)];
             if (mean) v = (v - mean[ch]) / stdv[ch];
         }
-        if (fmt == ESR_FMT_F16) { vh[e] = f2h(v); vl[e] = f2h(v - h2f(vh[e])); }
-        else split_bf16(v, vh[e], vl[e]);
+        v8[e] = v;
     }
-    const long long o = b * bs + cg * cs + (long long)Y * Wp + X;
-    hi[o] = pack8(vh);
-    if (lo) lo[o] = pack8(vl);
+    store8(hi, lo, act_off_frame(bs, cs, w, b, cg, Y, X), v8, fmt);
 }
 
 // act-layout gradient (interior h x w) -> fp32 NCHW [B][C][h][w], divided by std[c] (std NULL: copied)
 __global__ void unpack_grad_norm_kernel(DView g, int C, int h, int w, const float* __restrict__ stdv, float* __restrict__ dst, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per output element (b, c, y, x)
     if (idx >= total) return;
-    const int x = (int)(idx % w);
-    long long t = idx / w;
-    const int y = (int)(t % h);
-    t /= h;
-    const int c = (int)(t % C);
-    const int b = (int)(t / C);
-    const long long o = b * g.bs + (c >> 3) * g.cs + (long long)(y + 1) * (w + 2) + (x + 1);
-    float v = val16(lane16(g.hi[o], c & 7), g.fmt);
-    if (g.lo) v += val16(lane16(g.lo[o], c & 7), g.fmt);
+    const Idx4 q = split_index(idx, C, h, w);
+    const int b = q.i0, c = q.i1, y = q.i2, x = q.i3;
+    const float v = decode1(load_raw8(g.hi, g.lo, act_off(g.bs, g.cs, w, b, c >> 3, y, x)), g.lo != nullptr, g.fmt, c & 7);
     dst[idx] = stdv ? v / stdv[c] : v;
 }
 
@@ -69,20 +46,19 @@ __device__ __forceinline__ int window_argmax(const uint4 (&wh)[4], const uint4 (
     int arg = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        float v = val16(lane16(wh[k], e), fmt);
-        if (has_lo) v += val16(lane16(wl[k], e), fmt);
+        const float v = decode1(Raw8{wh[k], wl[k]}, has_lo, fmt, e);
         if (v > best || __builtin_isnan(v)) { best = v; arg = k; }
     }
     return arg;
 }
 
 __device__ __forceinline__ void load_window(const DView& x, int Win, int b, int cg, int oy, int ox, uint4 (&wh)[4], uint4 (&wl)[4]) {
-    const long long base = b * x.bs + cg * x.cs + (long long)(2 * oy + 1) * (Win + 2) + (2 * ox + 1);
+    const long long base = act_off(x.bs, x.cs, Win, b, cg, 2 * oy, 2 * ox);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const long long o = base + (long long)(k >> 1) * (Win + 2) + (k & 1);
-        wh[k] = x.hi[o];
-        wl[k] = x.lo ? x.lo[o] : make_uint4(0, 0, 0, 0);
+        const Raw8 r = load_raw8(x.hi, x.lo, base + (long long)(k >> 1) * (Win + 2) + (k & 1));
+        wh[k] = r.h;
+        wl[k] = r.l;
     }
 }
 
@@ -91,19 +67,11 @@ __device__ __forceinline__ void load_window(const DView& x, int Win, int b, int 
 __global__ void maxpool_kernel(DView x, int Win, DView y, int Ho, int Wo, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    const int Wp = Wo + 2, Hp = Ho + 2;
-    const int X = (int)(idx % Wp);
-    long long t = idx / Wp;
-    const int Y = (int)(t % Hp);
-    t /= Hp;
-    const int cg = (int)(t % y.ncg);
-    const int b = (int)(t / y.ncg);
-    const long long o = b * y.bs + cg * y.cs + (long long)Y * Wp + X;
-    uint4* const yh = (uint4*)y.hi;
-    uint4* const yl = (uint4*)y.lo;
-    if (X == 0 || Y == 0 || X == Wp - 1 || Y == Hp - 1) {
-        yh[o] = make_uint4(0, 0, 0, 0);
-        if (yl) yl[o] = make_uint4(0, 0, 0, 0);
+    const ActPos q = act_pos(idx, y.ncg, Ho + 2, Wo + 2);   // over y's padded frame
+    const int b = q.b, cg = q.cg, Y = q.y, X = q.x;
+    const long long o = act_off_frame(y.bs, y.cs, Wo, b, cg, Y, X);
+    if (frame_border(Y, X, Ho, Wo)) {
+        store_raw8(mut(y.hi), mut(y.lo), o, Raw8{});
         return;
     }
     uint4 wh[4], wl[4];
@@ -112,11 +80,10 @@ __global__ void maxpool_kernel(DView x, int Win, DView y, int Ho, int Wo, long l
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int k = window_argmax(wh, wl, x.lo != nullptr, x.fmt, e);
-        oh[e] = lane16(wh[k], e);
-        ol[e] = lane16(wl[k], e);
+        oh[e] = elem16(wh[k], e);
+        ol[e] = elem16(wl[k], e);
     }
-    yh[o] = pack8(oh);
-    if (yl) yl[o] = pack8(ol);
+    store_raw8(mut(y.hi), mut(y.lo), o, Raw8{pack16x8(oh), pack16x8(ol)});
 }
 
 // dx (H x W, zero border) = dy scattered to the argmax of every window of x (recomputed from x), zero elsewhere — including the last row /
@@ -124,42 +91,27 @@ __global__ void maxpool_kernel(DView x, int Win, DView y, int Ho, int Wo, long l
 __global__ void maxpool_grad_kernel(DView x, DView dy, int Ho, int Wo, DView dx, int H, int W, int relu_mask, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    const int Wp = W + 2, Hp = H + 2;
-    const int X = (int)(idx % Wp);
-    long long t = idx / Wp;
-    const int Y = (int)(t % Hp);
-    t /= Hp;
-    const int cg = (int)(t % dx.ncg);
-    const int b = (int)(t / dx.ncg);
-    const long long o = b * dx.bs + cg * dx.cs + (long long)Y * Wp + X;
-    uint4* const gh = (uint4*)dx.hi;
-    uint4* const gl = (uint4*)dx.lo;
+    const ActPos q = act_pos(idx, dx.ncg, H + 2, W + 2);   // over dx's padded frame
+    const int b = q.b, cg = q.cg, Y = q.y, X = q.x;
+    const long long o = act_off_frame(dx.bs, dx.cs, W, b, cg, Y, X);
     const int yy = Y - 1, xx = X - 1;
     if (yy < 0 || xx < 0 || yy >= 2 * Ho || xx >= 2 * Wo) {
-        gh[o] = make_uint4(0, 0, 0, 0);
-        if (gl) gl[o] = make_uint4(0, 0, 0, 0);
+        store_raw8(mut(dx.hi), mut(dx.lo), o, Raw8{});
         return;
     }
     const int oy = yy >> 1, ox = xx >> 1, self = ((yy & 1) << 1) | (xx & 1);
     uint4 wh[4], wl[4];
     load_window(x, W, b, cg, oy, ox, wh, wl);
-    const long long od = b * dy.bs + cg * dy.cs + (long long)(oy + 1) * (Wo + 2) + (ox + 1);
-    const uint4 dh = dy.hi[od];
-    const uint4 dl = dy.lo ? dy.lo[od] : make_uint4(0, 0, 0, 0);
+    const Raw8 d = load_raw8(dy.hi, dy.lo, act_off(dy.bs, dy.cs, Wo, b, cg, oy, ox));
     uint32_t oh[8], ol[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         bool pass = window_argmax(wh, wl, x.lo != nullptr, x.fmt, e) == self;
-        if (relu_mask) {
-            float v = val16(lane16(wh[self], e), x.fmt);
-            if (x.lo) v += val16(lane16(wl[self], e), x.fmt);
-            pass = pass && v > 0.f;
-        }
-        oh[e] = pass ? lane16(dh, e) : 0u;
-        ol[e] = pass ? lane16(dl, e) : 0u;
+        if (relu_mask) pass = pass && decode1(Raw8{wh[self], wl[self]}, x.lo != nullptr, x.fmt, e) > 0.f;
+        oh[e] = pass ? elem16(d.h, e) : 0u;
+        ol[e] = pass ? elem16(d.l, e) : 0u;
     }
-    gh[o] = pack8(oh);
-    if (gl) gl[o] = pack8(ol);
+    store_raw8(mut(dx.hi), mut(dx.lo), o, Raw8{pack16x8(oh), pack16x8(ol)});
 }
 
 inline unsigned blocks_of(long long total) { return (unsigned)((total + 255) / 256); }

@@ -160,7 +160,6 @@ __global__ __launch_bounds__(IS_THREADS) void img_stats_grad_kernel(const float*
     const int yy = (int)(t % H), c = (int)(t / H);
     const float c0 = coef[b * 3], c1 = coef[b * 3 + 1], c2 = coef[b * 3 + 2];
     auto V = [&](int y, int x_) { return is_val(img, mask, clamp01, H, W, c, y, x_); };
-    auto sgn = [](float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); };
     const float v = V(yy, xx);
     float g;
     if (KIND == 0) g = c0 * v + c1;

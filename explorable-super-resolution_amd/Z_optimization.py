@@ -64,6 +64,7 @@ import math
 import numpy as np
 import torch
 
+from esr_hip import _image as esr_image
 from esr_hip import dist as esr_dist
 from esr_hip import local as esr_local
 from esr_hip import pairmin as esr_pairmin
@@ -136,8 +137,7 @@ class SoftHistogramLoss(torch.nn.Module):
                 self.Feed_Desired_Hist_Im([im[0] if im.dim() == 4 else im for im in desired_hist_image][:1])
             return
         # the KDE / dictionary forms
-        self.image_mask = None if input_im_HR_mask is None else (input_im_HR_mask.detach().cpu().numpy() if torch.is_tensor(input_im_HR_mask)
-                                                                 else np.asarray(input_im_HR_mask))
+        self.image_mask = None if input_im_HR_mask is None else esr_image.to_numpy(input_im_HR_mask)
         self._patch_index = {}
         self.bins = None
         if not self.KDE:           # dictionary of gray levels: the bin centres, float32 values as the reference's linspace
@@ -197,7 +197,7 @@ class SoftHistogramLoss(torch.nn.Module):
             pts = []
             for im, m in zip(desired_hist_image, masks):
                 im = im[0] if im.dim() == 4 else im
-                m = None if m is None else (m.detach().cpu().numpy() if torch.is_tensor(m) else np.asarray(m))
+                m = None if m is None else esr_image.to_numpy(m)
                 pts.append(self._points(im.float().mean(0, keepdim=True), m, overlap)[0])
             pts = torch.cat(pts, 0).contiguous()                                       # [N_desired, D]
             self.bins = pts[kde.dedup_keep(pts, self.bin_width / 2)].contiguous()
@@ -302,7 +302,7 @@ JPEG_OBJECTIVES = ('l1', 'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrea
 
 class Z_optimizer():
     MIN_LR = 1e-5
-    PATCH_SIZE_4_STD = 7
+    PATCH_SIZE_4_STD = esr_image.PATCH
     SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES) + \
         list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble'] + list(RANDOM_OBJECTIVES) + list(MAG_OBJECTIVES) + list(PLUS_OBJECTIVES)
 
@@ -401,12 +401,13 @@ class Z_optimizer():
         assert (initial_LR is not None) or (existing_optimizer is not None), 'Should either supply optimizer from previous iterations or initial LR for new optimizer'
         self.image_mask = None if image_mask is None else torch.from_numpy(np.asarray(image_mask, dtype=np.float32)).to(self.device)
         self.local_STD = objective.startswith('local_') and objective not in MAG_OBJECTIVES
+        periodic = objective in PERIODICITY_OBJECTIVES or objective in PLUS_OBJECTIVES
+        if self.local_STD or periodic:
+            H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
         if self.local_STD:
             # every 7 x 7 window inside the opened image mask (ReturnPatchExtractionMat with overlap 1, :391-398); no mask: the whole output
-            H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
             self.patches = esr_local.PatchSet(image_mask, H, W)
-        if objective in PERIODICITY_OBJECTIVES or objective in PLUS_OBJECTIVES:
-            H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
+        if periodic:
             self.periodicity_pairs = [esr_local.ShiftPair(p, H, W, interpolated='nonInt' in objective) for p in data['periodicity_points']]
         if not self.model_training and ('fake_H' in model.__dict__ if not self.jpeg_mode else getattr(model, 'output_image', None) is not None):
             self.initial_output = model.Output_Batch(within_0_1=True).detach()
@@ -427,9 +428,7 @@ class Z_optimizer():
             self.desired_im = data['desired'].to(self.device)
         if self.random and 'limited' in objective:           # reference :546-548
             self.initial_image = 1 * model.output_image.detach()
-            if self.initial_image.size(0) not in (1, local_bs):
-                raise ValueError("Z objective '%s': the model's output_image has batch %d, the Z search %d on this rank (1 broadcasts)" %
-                                 (objective, self.initial_image.size(0), local_bs))
+            self._check_initial_batch(self.initial_image, 'output_image')
             self.rmse_weight = float(data['rmse_weight'])
         if objective == 'scribble':
             self._set_scribble(image_mask, data)
@@ -470,14 +469,19 @@ class Z_optimizer():
         out = self.model.Output_Batch(within_0_1=True)
         return torch.std(out if self.image_mask is None else out * self.image_mask, dim=(1, 2, 3)).view(1, -1)
 
+    def _check_initial_batch(self, initial, what='output'):
+        """the initial batch an objective starts from (the model's `what`) has one image for all samples or one per sample of this rank"""
+        local_bs = self.shard[1] - self.shard[0]
+        if initial.size(0) not in (1, local_bs):
+            raise ValueError("Z objective '%s': the model's %s has batch %d, the Z search %d on this rank (1 broadcasts)" %
+                             (self.objective, what, initial.size(0), local_bs))
+
     def _set_scribble(self, image_mask, data):
         """labels, desired image and constraint of the scribble objective (reference :401-448, :385-390), built once"""
         if 'fake_H' not in self.model.__dict__ or self.model.fake_H is None:
             raise ValueError("Z objective 'scribble' needs the model's current output (its brightened pixels and the region constraint start from it)")
-        local_bs = self.shard[1] - self.shard[0]
         initial = self.initial_output
-        if initial.size(0) not in (1, local_bs):
-            raise ValueError("Z objective 'scribble': the model's output has batch %d, the Z search %d on this rank (1 broadcasts)" % (initial.size(0), local_bs))
+        self._check_initial_batch(initial)
         # every rank must edit towards the same image: rank 0's brightened pixels (one broadcast, here only)
         desired = esr_scribble.desired_image(data['desired'], data['scribble_mask'], initial[0], data.get('brightness_factor'))
         desired = esr_dist.broadcast_tensor(torch.from_numpy(desired).to(self.device))
@@ -506,10 +510,7 @@ class Z_optimizer():
             self.desired_STD = self.initial_STD + inc                           # PLUS_MEANS_STD_INCREASE (reference :472, :476-477)
             self.constraining_loss_weight = 0.1                                 # the default (reference :390)
         if self.non_local_Z_optimization:
-            local_bs = self.shard[1] - self.shard[0]
-            if initial.size(0) not in (1, local_bs):
-                raise ValueError("Z objective '%s': the model's output has batch %d, the Z search %d on this rank (1 broadcasts)" %
-                                 (self.objective, initial.size(0), local_bs))
+            self._check_initial_batch(initial)
             self.constraint_spec = esr_scribble.constraint_spec(image_mask, initial)
 
     def _set_desired_VGG(self, desired):

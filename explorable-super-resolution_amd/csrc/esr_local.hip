@@ -11,6 +11,7 @@
 //     dv(y, x) = sum over the corners whose window covers (y, x) of a[p] (v(y, x) - mean[p])
 // (the v Box7^T(a) - Box7^T(a mean) of the adjoint, evaluated per term so that nearly flat windows do not cancel), dx_c = dv / C [0 <= x_c <= 1].
 // A workgroup owns a 16 x 64 pixel tile and stages a and mean of the 22 x 70 corners covering it in LDS: no atomics, bit-reproducible.
+// The tiling of both directions is Patch7 of csrc/esr_image.h (shared with csrc/esr_patchmag.hip); the kernels here hold the arithmetic only.
 //
 // Shifted L1 (periodicity).  For one period point and its two signs s = +, -: separable bilinear samplers (grid_sample, zero padding) given as
 // per-output-column taps (base_x[s][j], frac_x[s][j]) and per-output-row taps (base_y[s][i], frac_y[s][i]), weights (1 - frac, frac) on
@@ -19,33 +20,20 @@
 // as one double per (image, output row); the caller sums the rows and divides by C ny nx.  The backward forms G = g_b M sign(GS+ - GS-) on the
 // output grid, then the adjoint Wy+^T G Wx+ - Wy-^T G Wx- in gather form: every source pixel walks the output rows / columns whose taps
 // touch it, from per-source contributor ranges built by the caller (the samplers are monotone, so each range is contiguous).  No atomics.
-#include "esr_common.h"
+#include "esr_image.h"
 
 namespace {
 
-constexpr int LP = 7;                        // patch side (the reference's PATCH_SIZE_4_STD)
-constexpr int LT_X = 64, LT_Y = 16;          // corner / pixel tile per workgroup
-constexpr int LS_X = LT_X + LP - 1, LS_Y = LT_Y + LP - 1;
-constexpr int L_THREADS = 256;
+using PT = Patch7;
+constexpr int LP = PT::SIDE;                 // patch side (the reference's PATCH_SIZE_4_STD)
+constexpr int L_THREADS = PT::NT;
 
 __global__ __launch_bounds__(L_THREADS) void patch_std_kernel(const float* __restrict__ x, int C, int H, int W, const uint8_t* __restrict__ corners,
                                                                 float* __restrict__ S, float* __restrict__ M) {
-    __shared__ float v[LS_Y][LS_X];
-    const int b = blockIdx.z, cy0 = blockIdx.y * LT_Y, cx0 = blockIdx.x * LT_X;
-    const int Hc = H - LP + 1, Wc = W - LP + 1;
-    const long long plane = (long long)H * W;
-    const float* img = x + (long long)b * C * plane;
-    for (int t = threadIdx.x; t < LS_Y * LS_X; t += L_THREADS) {
-        const int ty = t / LS_X, tx = t % LS_X, y = cy0 + ty, xx = cx0 + tx;
-        v[ty][tx] = (y < H && xx < W) ? gray(img, C, plane, (long long)y * W + xx) : 0.f;
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % LT_X;
-    const int cx = cx0 + tx;
-    if (cx >= Wc) return;
-    for (int ty = threadIdx.x / LT_X; ty < LT_Y; ty += L_THREADS / LT_X) {
-        const int cy = cy0 + ty;
-        if (cy >= Hc) break;
+    __shared__ float v[PT::SY][PT::SX];
+    PT::load_gray(v, x, C, H, W);
+    const int b = blockIdx.z, Hc = H - LP + 1, Wc = W - LP + 1;
+    PT::for_corners(H, W, [&](int cy, int cx, int ty, int tx) {
         const long long o = ((long long)b * Hc + cy) * Wc + cx;
         float s = 0.f, m = 0.f;
         if (corners[(long long)cy * Wc + cx]) {
@@ -69,20 +57,18 @@ __global__ __launch_bounds__(L_THREADS) void patch_std_kernel(const float* __res
         }
         S[o] = s;
         M[o] = m;
-    }
+    });
 }
 
 __global__ __launch_bounds__(L_THREADS) void patch_std_grad_kernel(const float* __restrict__ x, int C, int H, int W, const uint8_t* __restrict__ corners,
                                                                      const float* __restrict__ S, const float* __restrict__ M, const float* __restrict__ dS,
                                                                      float* __restrict__ dx, int accumulate) {
-    __shared__ float a[LS_Y][LS_X], m[LS_Y][LS_X];
-    const int b = blockIdx.z, y0 = blockIdx.y * LT_Y, x0 = blockIdx.x * LT_X;
-    const int Hc = H - LP + 1, Wc = W - LP + 1;
+    __shared__ float a[PT::SY][PT::SX], m[PT::SY][PT::SX];
+    const int b = blockIdx.z, Hc = H - LP + 1, Wc = W - LP + 1;
     const long long plane = (long long)H * W;
-    for (int t = threadIdx.x; t < LS_Y * LS_X; t += L_THREADS) {
-        const int ty = t / LS_X, tx = t % LS_X, cy = y0 - (LP - 1) + ty, cx = x0 - (LP - 1) + tx;
+    PT::stage_corners(H, W, [&](int ty, int tx, int cy, int cx, bool inside) {
         float av = 0.f, mv = 0.f;
-        if (cy >= 0 && cx >= 0 && cy < Hc && cx < Wc && corners[(long long)cy * Wc + cx]) {
+        if (inside && corners[(long long)cy * Wc + cx]) {
             const long long o = ((long long)b * Hc + cy) * Wc + cx;
             const float s = S[o];
             if (s > 0.f) {
@@ -92,16 +78,10 @@ __global__ __launch_bounds__(L_THREADS) void patch_std_grad_kernel(const float* 
         }
         a[ty][tx] = av;
         m[ty][tx] = mv;
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % LT_X;
-    const int xx = x0 + tx;
-    if (xx >= W) return;
+    });
     const float* img = x + (long long)b * C * plane;
     float* out = dx + (long long)b * C * plane;
-    for (int ty = threadIdx.x / LT_X; ty < LT_Y; ty += L_THREADS / LT_X) {
-        const int y = y0 + ty;
-        if (y >= H) break;
+    PT::for_pixels(H, W, [&](int y, int xx, int ty, int tx) {
         const long long off = (long long)y * W + xx;
         const float v = gray(img, C, plane, off);
         float acc = 0.f;
@@ -109,14 +89,8 @@ __global__ __launch_bounds__(L_THREADS) void patch_std_grad_kernel(const float* 
         for (int dy = 0; dy < LP; ++dy)
 #pragma unroll
             for (int dxx = 0; dxx < LP; ++dxx) acc += a[ty + dy][tx + dxx] * (v - m[ty + dy][tx + dxx]);
-        const float g = acc / (float)C;
-        for (int c = 0; c < C; ++c) {
-            const float raw = img[c * plane + off];
-            const float gc = (raw >= 0.f && raw <= 1.f) ? g : 0.f;      // torch.clamp's gradient: 1 inside and at the bounds
-            float* o = out + c * plane + off;
-            *o = accumulate ? *o + gc : gc;
-        }
-    }
+        gated_store_pixel(out, img, C, plane, off, acc / (float)C, accumulate);
+    });
 }
 
 // ---- shifted L1 ----
@@ -127,7 +101,7 @@ struct Taps {
 __device__ __forceinline__ float pix(const float* __restrict__ p, int H, int W, int y, int x, int clamp01) {
     if (y < 0 || y >= H || x < 0 || x >= W) return 0.f;
     const float v = p[(long long)y * W + x];
-    return clamp01 ? fminf(fmaxf(v, 0.f), 1.f) : v;
+    return clamp01 ? clamp_unit(v) : v;
 }
 
 __device__ __forceinline__ float bilin(const float* __restrict__ p, int H, int W, int y0, float fy, int x0, float fx, int clamp01) {
@@ -156,14 +130,9 @@ __global__ __launch_bounds__(L_THREADS) void shift_l1_kernel(const float* __rest
         }
         acc += (double)(Mw * s);
     }
-    __shared__ double red[L_THREADS];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = L_THREADS / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(long long)b * ny + i] = red[0];
+    __shared__ double red[1][L_THREADS];
+    block_tree_sum(red, {acc});
+    if (threadIdx.x == 0) partial[(long long)b * ny + i] = red[0][0];
 }
 
 // G[b][c][i][j] = g[b] M(i, j) sign(GS+ - GS-)   (torch's |.|' = 0 at 0)
@@ -223,23 +192,17 @@ __global__ __launch_bounds__(L_THREADS) void shift_l1_adj_kernel(const float* __
             acc += s == 0 ? as : -as;
         }
         const long long off = ((long long)b * C + c) * plane + (long long)y * W + xx;
-        const float raw = x[off];
-        const float gc = (raw >= 0.f && raw <= 1.f) ? acc : 0.f;
-        dx[off] = accumulate ? dx[off] + gc : gc;
+        gated_store(dx + off, x[off], acc, accumulate);
     }
 }
-
-bool grid_ok(int B, int H, int W) { return B <= 65535 && H <= 65535 && W <= 65535; }
 
 }  // namespace
 
 extern "C" int esr_patch_std(const float* x, int B, int C, int H, int W, const uint8_t* corners, float* S, float* mean, esr_stream_t stream) {
     if (!x || !corners || !S || !mean || B <= 0 || C <= 0 || H < LP || W < LP) return ESR_E_ARG;
     if (!grid_ok(B, H, W)) return ESR_E_UNSUPPORTED;
-    const int Hc = H - LP + 1, Wc = W - LP + 1;
-    const dim3 grid((unsigned)((Wc + LT_X - 1) / LT_X), (unsigned)((Hc + LT_Y - 1) / LT_Y), (unsigned)B);
     ESR_CLEAR_ERR();
-    hipLaunchKernelGGL(patch_std_kernel, grid, dim3(L_THREADS), 0, (hipStream_t)stream, x, C, H, W, corners, S, mean);
+    hipLaunchKernelGGL(patch_std_kernel, PT::corner_grid(B, H, W), dim3(L_THREADS), 0, (hipStream_t)stream, x, C, H, W, corners, S, mean);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
@@ -248,9 +211,8 @@ extern "C" int esr_patch_std_grad(const float* x, int B, int C, int H, int W, co
                                   float* dx, int accumulate, esr_stream_t stream) {
     if (!x || !corners || !S || !mean || !dS || !dx || B <= 0 || C <= 0 || H < LP || W < LP) return ESR_E_ARG;
     if (!grid_ok(B, H, W)) return ESR_E_UNSUPPORTED;
-    const dim3 grid((unsigned)((W + LT_X - 1) / LT_X), (unsigned)((H + LT_Y - 1) / LT_Y), (unsigned)B);
     ESR_CLEAR_ERR();
-    hipLaunchKernelGGL(patch_std_grad_kernel, grid, dim3(L_THREADS), 0, (hipStream_t)stream, x, C, H, W, corners, S, mean, dS, dx, accumulate);
+    hipLaunchKernelGGL(patch_std_grad_kernel, PT::pixel_grid(B, H, W), dim3(L_THREADS), 0, (hipStream_t)stream, x, C, H, W, corners, S, mean, dS, dx, accumulate);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }

@@ -17,7 +17,7 @@
 //   element adds every row's two terms into its own column of a second LDS array and then writes its own outputs: no scatter to memory, no atomics.
 // Batches whose columns do not fit in 160 KiB of LDS (about 300 rows forward; Bg + hi - lo > 320 backward) take the same code with the columns
 // in global memory (`work`, and dx itself as the accumulator): any Bg >= 1 runs.
-#include "esr_common.h"
+#include "esr_image.h"
 
 namespace {
 
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(P_THREADS) void pairmin_grad_kernel(PairArgs p, flo
             for (int j = 0; j < 8; ++j) {
                 if (b0 + j >= nl) break;
                 if (init) g[j] -= p.w * sgn(rd(raw[j], p.clamp01 != 0) - i0[j]);
-                if (p.clamp01 && !(raw[j] >= 0.f && raw[j] <= 1.f)) g[j] = 0.f;       // torch.clamp's gradient: 1 inside and at the bounds
+                if (p.clamp01 && !clamp_gate(raw[j])) g[j] = 0.f;
                 dx[(long long)(b0 + j) * p.n + e] = m * g[j];
             }
         }

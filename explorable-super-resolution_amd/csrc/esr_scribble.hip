@@ -13,7 +13,7 @@
 // LDS reduction; the caller sums the rows).  No atomics, bit-reproducible.
 // Backward, gather form: pixel q collects its own L1 and constraint terms and the 8 pair terms in which it is the first or the second element;
 // both give + w sign(v(q) - v(n)) for the neighbour n, w the offset class's weight.  No atomics.
-#include "esr_common.h"
+#include "esr_image.h"
 
 namespace {
 
@@ -56,15 +56,7 @@ __global__ __launch_bounds__(S_THREADS) void scribble_kernel(const float* __rest
         for (int k = 0; k < 5; ++k) s[k] += (double)a[k];
     }
     __shared__ double red[5][S_THREADS];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) red[k][threadIdx.x] = s[k];
-    __syncthreads();
-    for (int w = S_THREADS / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-#pragma unroll
-            for (int k = 0; k < 5; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum(red, s);
     if (threadIdx.x < 5) partial[((long long)b * H + y) * 5 + threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -117,13 +109,9 @@ __global__ __launch_bounds__(S_THREADS) void scribble_grad_kernel(const float* _
                 }
         }
         if (con) acc += g_con * sgn(v - ref[c * plane + o]);
-        const float gc = (raw >= 0.f && raw <= 1.f) ? acc : 0.f;      // torch.clamp's gradient: 1 inside and at the bounds
-        float* q = out + c * plane + o;
-        *q = accumulate ? *q + gc : gc;
+        gated_store(out + c * plane + o, raw, acc, accumulate);
     }
 }
-
-bool grid_ok(int B, int H, int W) { return B <= 65535 && H <= 65535 && W <= 65535; }
 
 }  // namespace
 

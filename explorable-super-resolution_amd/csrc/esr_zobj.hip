@@ -6,7 +6,7 @@
 // workgroup owns one BIN per thread and streams a slab of pixels through LDS: every thread accumulates its bin in a double register — no n x K
 // tensor, no atomics; per-slab partial histograms are folded by the caller (K doubles per slab).  The backward is the transposed loop: one
 // PIXEL per thread, the K upstream gradients in LDS.
-#include "esr_common.h"
+#include "esr_image.h"
 
 namespace {
 
@@ -102,7 +102,7 @@ constexpr int IS_THREADS = 256, IS_PER_THREAD = 8;
 
 __device__ __forceinline__ float is_val(const float* __restrict__ img, const float* __restrict__ mask, int clamp01, int H, int W, int c, int y, int x) {
     float v = img[((long long)c * H + y) * W + x];
-    if (clamp01) v = fminf(fmaxf(v, 0.f), 1.f);
+    if (clamp01) v = clamp_unit(v);
     if (mask) v *= mask[(long long)y * W + x];
     return v;
 }
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(IS_THREADS) void img_stats_grad_kernel(const float*
         if (yy > 0 && xx + 1 < W) g += Bf(yy - 1, xx);
     }
     const float raw = img[((long long)c * H + yy) * W + xx];
-    if (clamp01 && !(raw >= 0.f && raw <= 1.f)) g = 0.f;          // torch.clamp's gradient: 1 inside and AT the bounds ((x >= min) & (x <= max)), 0 outside (NaN: 0)
+    if (clamp01 && !clamp_gate(raw)) g = 0.f;
     if (mask) g *= mask[(long long)yy * W + xx];
     float* o = dx + (long long)b * n + i;
     *o = accumulate ? *o + g : g;

@@ -16,11 +16,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._image import PATCH, DeviceCopies, detach_f32, mask_on, to_numpy
 from ._lib import check
 from .act import stream_ptr
 from .kde import _box_sum, binary_opening_square
-
-PATCH = 7            # the reference's PATCH_SIZE_4_STD
 
 
 def patch_corners(mask, H=None, W=None):
@@ -29,7 +28,7 @@ def patch_corners(mask, H=None, W=None):
     if mask is None:
         m = np.ones((H, W), dtype=bool)
     else:
-        m = (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)) != 0
+        m = to_numpy(mask) != 0
     if m.shape[0] < PATCH or m.shape[1] < PATCH:
         raise ValueError('local STD: a %d x %d image holds no %d x %d patch' % (m.shape[0], m.shape[1], PATCH, PATCH))
     c = (_box_sum(binary_opening_square(m, PATCH), PATCH) == PATCH * PATCH).astype(np.uint8)
@@ -61,9 +60,7 @@ def _patch_std_cpu(x, flat_idx):
 class _PatchStd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, corners, flat_idx):
-        xd = x.detach()
-        if xd.dtype != torch.float32 or not xd.is_contiguous():
-            xd = xd.float().contiguous()
+        xd = detach_f32(x)
         B, Cc, H, W = xd.shape
         S = torch.empty(B, H - PATCH + 1, W - PATCH + 1, dtype=torch.float32, device=xd.device)
         M = torch.empty_like(S)
@@ -83,24 +80,21 @@ class _PatchStd(torch.autograd.Function):
         return dx, None, None
 
 
-class PatchSet:
+class PatchSet(DeviceCopies):
     """a corner map with its device copies, built once per (mask, image size) and reused every iteration"""
 
     def __init__(self, mask, H, W, corners=None):
         self.corners = patch_corners(mask, H, W) if corners is None else np.asarray(corners, dtype=np.uint8)
         self.H, self.W = self.corners.shape[0] + PATCH - 1, self.corners.shape[1] + PATCH - 1
         self.flat_idx = torch.from_numpy(np.flatnonzero(self.corners).astype(np.int64))
-        self._dev = {}
+        self.forget_devices()
 
     @property
     def P(self):
         return int(self.flat_idx.numel())
 
-    def on(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = (torch.from_numpy(self.corners).to(device), self.flat_idx.to(device))
-        return self._dev[key]
+    def _to_device(self, device):
+        return torch.from_numpy(self.corners).to(device), self.flat_idx.to(device)
 
 
 def patch_std(x, patches):
@@ -151,7 +145,7 @@ def _ranges(base, n_src):
     return np.stack([np.clip(lo, 0, len(base)), np.clip(hi, 0, len(base))], 1).astype(np.int32)
 
 
-class ShiftPair:
+class ShiftPair(DeviceCopies):
     """The two samplers of one period point: sign + and sign -, each separable (taps per output column and per output row)."""
 
     def __init__(self, point, H, W, interpolated):
@@ -185,14 +179,11 @@ class ShiftPair:
         self.frac_y = np.stack(fy).astype(np.float32)
         self.ranges_x = np.stack([_ranges(b, W) for b in self.base_x])
         self.ranges_y = np.stack([_ranges(b, H) for b in self.base_y])
-        self._dev = {}
+        self.forget_devices()
 
-    def on(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in
-                                   (self.base_x, self.frac_x, self.base_y, self.frac_y, self.ranges_x, self.ranges_y))
-        return self._dev[key]
+    def _to_device(self, device):
+        return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in
+                     (self.base_x, self.frac_x, self.base_y, self.frac_y, self.ranges_x, self.ranges_y))
 
     def grids(self, device, dtype=torch.float32):
         """the reference's [1, ny, nx, 2] grid_sample grids for the signs +, - (non-integer form)"""
@@ -220,11 +211,9 @@ def _shift_l1_cpu(x, mask, pairs):
 class _ShiftL1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, pairs):
-        xd = x.detach()
-        if xd.dtype != torch.float32 or not xd.is_contiguous():
-            xd = xd.float().contiguous()
+        xd = detach_f32(x)
         B, Cc, H, W = xd.shape
-        md = mask.detach().to(device=xd.device, dtype=torch.float32).expand(H, W).contiguous()
+        md = mask_on(mask, xd.device, H, W)
         loss = torch.zeros(B, dtype=torch.float64, device=xd.device)
         for pr in pairs:
             bx, fx, by, fy, _, _ = pr.on(xd.device)

@@ -15,6 +15,7 @@ index there.  CPU: the defining torch expression (torch.min's own choice on ties
 import torch
 
 from . import _lib
+from ._image import as_f32, detach_f32, ptr
 from ._lib import check
 from .act import stream_ptr
 
@@ -66,10 +67,6 @@ def _scratch(xa, lo, hi, grad):
     return torch.empty(int(n), dtype=torch.float32, device=xa.device) if n else None
 
 
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
 class _PairMin(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_local, x_all, lo, clamp01, mask, init, w):
@@ -78,8 +75,8 @@ class _PairMin(torch.autograd.Function):
         work = _scratch(x_all, lo, lo + Bl, 0)
         blocks = int(_lib.lib.esr_pairmin_blocks(C, H, W))
         partial = torch.empty(Bl, blocks, dtype=torch.float64, device=x_all.device)
-        check(_lib.lib.esr_pairmin(x_all.data_ptr(), Bg, C, H, W, lo, lo + Bl, int(clamp01), _ptr(mask), _ptr(init), 0 if init is None else init.size(0),
-                                   float(w), _ptr(work), partial.data_ptr(), stream_ptr()), 'esr_pairmin')
+        check(_lib.lib.esr_pairmin(x_all.data_ptr(), Bg, C, H, W, lo, lo + Bl, int(clamp01), ptr(mask), ptr(init), 0 if init is None else init.size(0),
+                                   float(w), ptr(work), partial.data_ptr(), stream_ptr()), 'esr_pairmin')
         Z = -partial.sum(1) / (C * H * W)
         ctx.save_for_backward(x_all, mask, init)
         ctx.args = (lo, Bl, bool(clamp01), float(w))
@@ -93,8 +90,8 @@ class _PairMin(torch.autograd.Function):
         work = _scratch(x_all, lo, lo + Bl, 1)
         dx = torch.empty(Bl, C, H, W, dtype=torch.float32, device=x_all.device)
         scale = -(0.0 if gS is None else float(gS)) / (float(C) * H * W * Bg)
-        check(_lib.lib.esr_pairmin_grad(x_all.data_ptr(), Bg, C, H, W, lo, lo + Bl, int(clamp01), _ptr(mask), _ptr(init), 0 if init is None else init.size(0),
-                                        w, scale, _ptr(work), dx.data_ptr(), stream_ptr()), 'esr_pairmin_grad')
+        check(_lib.lib.esr_pairmin_grad(x_all.data_ptr(), Bg, C, H, W, lo, lo + Bl, int(clamp01), ptr(mask), ptr(init), 0 if init is None else init.size(0),
+                                        w, scale, ptr(work), dx.data_ptr(), stream_ptr()), 'esr_pairmin_grad')
         return dx, None, None, None, None, None, None
 
 
@@ -103,15 +100,13 @@ def random_share(x_local, x_all=None, lo=0, clamp01=True, mask=None, init=None, 
     x_local [B_local, C, H, W]: this rank's rows, attached to the graph; x_all [Bg, C, H, W]: every rank's rows, detached, in rank order, holding
     x_local's values at [lo, lo + B_local) - None when the local rows are the whole batch.  mask [H, W] or None; init [1 or B_local, C, H, W]
     with its weight w (the '*_limited' term) or None."""
-    xl = x_local if (x_local.dtype == torch.float32 and x_local.is_contiguous()) else x_local.float().contiguous()
-    xa = xl.detach() if x_all is None else x_all.detach()
-    if xa.dtype != torch.float32 or not xa.is_contiguous():
-        xa = xa.float().contiguous()
+    xl = as_f32(x_local)
+    xa = detach_f32(xl if x_all is None else x_all)
     _check(xl, xa, lo, mask, init)
     if mask is not None:
-        mask = mask.detach().float().contiguous()
+        mask = detach_f32(mask)
     if init is not None:
-        init = init.detach().float().contiguous()
+        init = detach_f32(init)
     if not xl.is_cuda:
         return _share_cpu(xl, xa, lo, clamp01, mask, init, float(w))
     Z, share = _PairMin.apply(xl, xa, lo, clamp01, mask, init, float(w))

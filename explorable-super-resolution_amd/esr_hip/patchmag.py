@@ -13,11 +13,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._image import PATCH, DeviceCopies, detach_f32, to_numpy
 from ._lib import check
 from .act import stream_ptr
 from .kde import patch_extraction_indexes
 
-PATCH = 7            # the reference's PATCH_SIZE_4_STD
 OVERLAP = 0.5        # desired_overlap of the 'local' names without 'STD' (reference :392)
 STD_FLOOR = 1 / 255
 
@@ -32,7 +32,7 @@ def desired_patches(initial_first, patch_indexes, increment, sign):
     return ((Q - m) / s * (s + increment * (1 if sign > 0 else -1)) + m).contiguous()
 
 
-class MagSpec:
+class MagSpec(DeviceCopies):
     """the patch set and the desired patches of one edit, built once and reused every iteration (device copies cached).
     image_mask None: the whole H x W image.  initial_first: [C, H, W], image 0 of the clamped initial output.  ValueError when no patch fits."""
 
@@ -40,7 +40,7 @@ class MagSpec:
         if image_mask is None:
             m = np.ones((H, W), dtype=np.float32)
         else:
-            m = image_mask.detach().cpu().numpy() if torch.is_tensor(image_mask) else np.asarray(image_mask)
+            m = to_numpy(image_mask)
         self.H, self.W = m.shape
         if (H is not None and H != self.H) or (W is not None and W != self.W):
             raise ValueError('patch magnitude: image mask %s for a %s x %s image' % (m.shape, H, W))
@@ -55,7 +55,7 @@ class MagSpec:
         self.corner_index[y0, x0] = np.arange(self.P, dtype=np.int32)
         self.increment, self.sign = float(increment), (1 if sign > 0 else -1)
         self.desired = desired_patches(initial_first, self.patches, increment, sign)
-        self._dev = {}
+        self.forget_devices()
 
     @property
     def P(self):
@@ -66,15 +66,11 @@ class MagSpec:
         if tuple(desired.shape) != (PATCH * PATCH, self.P):
             raise ValueError('patch magnitude: desired patches %s, expected [49, %d]' % (tuple(desired.shape), self.P))
         self.desired = desired.detach().float().cpu().contiguous()
-        self._dev = {}
+        self.forget_devices()
 
-    def on(self, device):
-        """(corner_index [H-6, W-6] int32, desired [P, 49], patch indexes [P, 49] int64) on `device`"""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = (torch.from_numpy(self.corner_index).to(device), self.desired.t().contiguous().to(device),
-                              torch.from_numpy(self.patches).to(device))
-        return self._dev[key]
+    def _to_device(self, device):
+        """on(device): (corner_index [H-6, W-6] int32, desired [P, 49], patch indexes [P, 49] int64)"""
+        return torch.from_numpy(self.corner_index).to(device), self.desired.t().contiguous().to(device), torch.from_numpy(self.patches).to(device)
 
 
 def _patch_mag_cpu(x, spec):
@@ -87,9 +83,7 @@ def _patch_mag_cpu(x, spec):
 class _PatchMag(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, spec):
-        xd = x.detach()
-        if xd.dtype != torch.float32 or not xd.is_contiguous():
-            xd = xd.float().contiguous()
+        xd = detach_f32(x)
         B, Cc, H, W = xd.shape
         index, desired, _ = spec.on(xd.device)
         partial = torch.empty(B, int(_lib.lib.esr_patch_mag_blocks(H, W)), dtype=torch.float64, device=xd.device)

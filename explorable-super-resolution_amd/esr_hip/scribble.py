@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._image import DeviceCopies, detach_f32, ptr, to_numpy
 from ._lib import check
 from .act import stream_ptr
 
@@ -26,10 +27,6 @@ SMOOTHING_MARGIN = 1            # the reference's 3 x 3 smoothing of the brightn
 NON_EDIT_MARGINS = 24           # the region constraint's always-editable interior, E[24:-24, 24:-24]
 DILATION = 16                   # dilate(image_mask, ones(16, 16))
 TV_OFFSETS = ((1, 1), (1, 0), (0, 1), (-1, 1))       # (dy, dx): p pairs with p + d (Return_Translated_SubImage with shifts -d, utils/util.py:260-273)
-
-
-def _np(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
 # ------------------------------------------------------------------------------------------------ one-off host preparation
@@ -83,10 +80,10 @@ def desired_image(desired, scribble_mask, initial_first, brightness_factor=None)
     """D [1, C, H, W] float32: data['desired'] with the pixels s in {2, 3} replaced by the brightened initial image 0 (initial_first [C, H, W],
     already clamped to [0, 1]); brightness_factor is read only where those labels occur"""
     s = np.asarray(scribble_mask)
-    D = _np(desired).astype(np.float32).reshape(1, -1, s.shape[0], s.shape[1]).copy()
+    D = to_numpy(desired).astype(np.float32).reshape(1, -1, s.shape[0], s.shape[1]).copy()
     sel = (s == 2) | (s == 3)
     if sel.any():
-        hsv = rgb2hsv(np.clip(255 * _np(initial_first).astype(np.float32).transpose(1, 2, 0), 0, 255))
+        hsv = rgb2hsv(np.clip(255 * to_numpy(initial_first).astype(np.float32).transpose(1, 2, 0), 0, 255))
         hsv[..., 2] = hsv[..., 2] * brightness_multiplier(s, brightness_factor)
         rgb = (hsv2rgb(hsv) / 255).transpose(2, 0, 1).astype(np.float32)
         D[0][:, sel] = rgb[:, sel]
@@ -131,7 +128,7 @@ def rebuilt_z_mask(image_mask):
     return np.minimum(1, E + dilate16(m)).astype(np.float32)
 
 
-class ScribbleSpec:
+class ScribbleSpec(DeviceCopies):
     """labels, the desired image and the constraint's reference output, built once per edit and reused every iteration.
     desired: [1, C, H, W] (desired_image's result); initial: the initial output [1 or B, C, H, W] (clamped), needed when `constraint`."""
 
@@ -139,19 +136,15 @@ class ScribbleSpec:
         self.labels = label_map(scribble_mask, image_mask, constraint)
         self.H, self.W = self.labels.shape
         self.constraint = bool(constraint)
-        self.desired = torch.as_tensor(_np(desired), dtype=torch.float32).reshape(1, -1, self.H, self.W).contiguous()
+        self.desired = torch.as_tensor(to_numpy(desired), dtype=torch.float32).reshape(1, -1, self.H, self.W).contiguous()
         if self.constraint and initial is None:
             raise ValueError('scribble: the region constraint needs the initial output')
-        self.initial = initial.detach().float().contiguous() if (self.constraint and initial is not None) else None
+        self.initial = detach_f32(initial) if (self.constraint and initial is not None) else None
         self.regions = int((self.labels & LAB_TV).max())
-        self._dev = {}
+        self.forget_devices()
 
-    def on(self, device):
-        key = str(device)
-        if key not in self._dev:
-            i0 = None if self.initial is None else self.initial.to(device)
-            self._dev[key] = (torch.from_numpy(self.labels).to(device), self.desired.to(device), i0)
-        return self._dev[key]
+    def _to_device(self, device):
+        return torch.from_numpy(self.labels).to(device), self.desired.to(device), None if self.initial is None else self.initial.to(device)
 
     def masks(self, device, dtype=torch.float32):
         """(M1, T, constraint mask) as [H, W] tensors: the L1 set, the TV region ids, 1 - lm (zeros without the constraint)"""
@@ -186,13 +179,11 @@ def _scribble_cpu(x, spec, norm):
 class _Scribble(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, spec, norm):
-        xd = x.detach()
-        if xd.dtype != torch.float32 or not xd.is_contiguous():
-            xd = xd.float().contiguous()
+        xd = detach_f32(x)
         B, Cc, H, W = xd.shape
         lab, D, I0 = spec.on(xd.device)
         partial = torch.empty(B, H, 5, dtype=torch.float64, device=xd.device)
-        check(_lib.lib.esr_scribble(xd.data_ptr(), B, Cc, H, W, D.data_ptr(), lab.data_ptr(), 0 if I0 is None else I0.data_ptr(),
+        check(_lib.lib.esr_scribble(xd.data_ptr(), B, Cc, H, W, D.data_ptr(), lab.data_ptr(), ptr(I0),
                                     0 if I0 is None else I0.size(0), partial.data_ptr(), stream_ptr()), 'esr_scribble')
         s = partial.sum(1)                                   # [B, 5]: l1, diagonal, vertical, horizontal pairs, constraint
         L = s[:, 0] / (Cc * H * W)
@@ -211,7 +202,7 @@ class _Scribble(torch.autograd.Function):
         g = (torch.zeros(B, device=xd.device) if gL is None else gL.detach()).float().contiguous()
         g_con = 0.0 if (gC is None or I0 is None) else float(gC) / ctx.norm
         dx = torch.empty_like(xd)
-        check(_lib.lib.esr_scribble_grad(xd.data_ptr(), B, Cc, H, W, D.data_ptr(), lab.data_ptr(), 0 if I0 is None else I0.data_ptr(),
+        check(_lib.lib.esr_scribble_grad(xd.data_ptr(), B, Cc, H, W, D.data_ptr(), lab.data_ptr(), ptr(I0),
                                          0 if I0 is None else I0.size(0), g.data_ptr(), g_con, dx.data_ptr(), 0, stream_ptr()), 'esr_scribble_grad')
         return dx, None, None
 
@@ -219,7 +210,7 @@ class _Scribble(torch.autograd.Function):
 def constraint_spec(image_mask, initial):
     """the ScribbleSpec of the region constraint alone (an empty label map, the constrained set 1 - (image_mask > 0)), for the objectives that
     share scribble's constraint; build it once per edit.  initial: the clamped initial output [1 or B, C, H, W]."""
-    m = _np(image_mask)
+    m = to_numpy(image_mask)
     return ScribbleSpec(np.zeros(m.shape, dtype=np.int64), m, np.zeros((1, initial.size(1)) + m.shape, dtype=np.float32), constraint=True,
                         initial=initial)
 

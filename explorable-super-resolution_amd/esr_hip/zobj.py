@@ -1,10 +1,9 @@
 """Host wrappers of the Z-objective kernels (csrc/esr_zobj.hip): the soft histogram behind the reference's SoftHistogramLoss
 (codes/Z_optimization.py:170-209), as a differentiable torch function."""
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._image import detach_f32, mask_on, ptr
 from ._lib import check
 from .act import require_gpu, stream_ptr
 
@@ -35,9 +34,7 @@ class _SoftHist(torch.autograd.Function):
 def soft_histogram(values, bins, lo, hi, temperature, eps=1e-7):
     """h[k] = mean_i exp(-(d(v_i, c_k) + eps)^2 / temperature), c_k = linspace(lo, hi, bins), distance wrapped with period hi.
     values: any shape (flattened), on the GPU; returns [bins] float64; differentiable w.r.t. values."""
-    shape_grad = values
-    out = _SoftHist.apply(values.reshape(-1), int(bins), float(lo), float(hi), float(temperature), float(eps))
-    return out
+    return _SoftHist.apply(values.reshape(-1), int(bins), float(lo), float(hi), float(temperature), float(eps))
 
 
 # ------------------------------------------------------------------------------------------------ per-image statistics (esr_img_stats)
@@ -48,15 +45,11 @@ class _ImgStat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, clamp01, kind):
         require_gpu(x, 'image batch')
-        xd = x.detach()
-        if xd.dtype != torch.float32 or not xd.is_contiguous():
-            xd = xd.float().contiguous()
+        xd = detach_f32(x)
         B, Cc, H, W = xd.shape
-        m = None
-        if mask is not None:
-            m = mask.detach().to(device=xd.device, dtype=torch.float32).expand(H, W).contiguous()
+        m = None if mask is None else mask_on(mask, xd.device, H, W)
         sums = torch.zeros(B, 3, dtype=torch.float64, device=xd.device)
-        check(_lib.lib.esr_img_stats(xd.data_ptr(), B, Cc, H, W, m.data_ptr() if m is not None else None, 1 if clamp01 else 0, kind, sums.data_ptr(), stream_ptr()),
+        check(_lib.lib.esr_img_stats(xd.data_ptr(), B, Cc, H, W, ptr(m), 1 if clamp01 else 0, kind, sums.data_ptr(), stream_ptr()),
               'esr_img_stats')
         ctx.save_for_backward(xd, m, sums)
         ctx.clamp01, ctx.kind = clamp01, kind
@@ -88,7 +81,7 @@ class _ImgStat(torch.autograd.Function):
             coef[:, 0], coef[:, 1], coef[:, 2] = 2 * g[0] / nn_, 2 * g[1] / nn_, g[2] / nn_
         coef = coef.float().contiguous()
         dx = torch.empty_like(xd)
-        check(_lib.lib.esr_img_stats_grad(xd.data_ptr(), B, Cc, H, W, m.data_ptr() if m is not None else None, 1 if ctx.clamp01 else 0, ctx.kind, coef.data_ptr(),
+        check(_lib.lib.esr_img_stats_grad(xd.data_ptr(), B, Cc, H, W, ptr(m), 1 if ctx.clamp01 else 0, ctx.kind, coef.data_ptr(),
                                           dx.data_ptr(), 0, stream_ptr()), 'esr_img_stats_grad')
         return dx, None, None, None
 

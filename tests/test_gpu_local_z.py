@@ -96,6 +96,39 @@ def test_patch_std_matches_float64_at_512x384():
     assert float((g - g64).abs().max()) <= 1e-5 * float(g64.abs().max())
 
 
+@pytest.mark.parametrize('H,W,P', [(7, 7, 1), (22, 70, 1024), (23, 71, 1105)])
+def test_patch_std_matches_float64_at_the_tile_frame_edges(H, W, P):
+    """the smallest shapes at which the shared 16 x 64 corner-tile frame can go wrong, full mask: one corner in a tile that is almost all padding;
+    Hc x Wc = 16 x 64, exactly one full tile; 17 x 65, a 2 x 2 grid whose last row and column of tiles hold one corner each.  The bounds of
+    test_patch_std_matches_float64_at_512x384 (these inputs have no flat windows, so both sides of its split need not occur)."""
+    from esr_hip import local
+    ps = local.PatchSet(None, H, W)
+    assert ps.P == P
+    x = seeded_uniform((2, 3, H, W), 1508, -0.1, 1.1).to(DEV).requires_grad_(True)
+    S = local.patch_std(x, ps)
+    x64 = x.detach().double().requires_grad_(True)
+    S64 = std64(x64, ps)
+    assert S.shape == S64.shape == (P, 2)
+    s, r = S.detach().double(), S64.detach()
+    big = r > 1e-3
+    print('patch_std %d x %d: P %d, %d of %d STDs above 1e-3, worst rel %.2e' % (H, W, P, int(big.sum()), big.numel(),
+                                                                               float(((s - r).abs() / r)[big].max()) if big.any() else 0.0))
+    if big.any():
+        assert float(((s - r).abs() / r)[big].max()) <= 1e-5
+    if (~big).any():
+        assert float((s - r).abs()[~big].max()) <= 1e-7
+    cot = seeded_uniform(tuple(S.shape), 1509, -1.0, 1.0).to(DEV)
+    (S * cot).sum().backward()
+    (S64 * cot.double()).sum().backward()
+    g, g64 = x.grad.double(), x64.grad
+    print('   grad err / max|grad| %.2e' % (float((g - g64).abs().max()) / float(g64.abs().max())))
+    assert torch.isfinite(x.grad).all()
+    assert float((g - g64).abs().max()) <= 1e-5 * float(g64.abs().max())
+    again = x.detach().clone().requires_grad_(True)
+    (local.patch_std(again, ps) * cot).sum().backward()
+    assert torch.equal(x.grad, again.grad)
+
+
 def test_flat_patch_gradient_is_zero_and_finite():
     from esr_hip import local
     x = torch.full((1, 3, 16, 16), 0.3, device=DEV)

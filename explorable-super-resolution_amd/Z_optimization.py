@@ -50,7 +50,9 @@ six names above (the other local and periodicity ones refuse it, the whole-image
 automatic histogram temperature.
 JPEG mode (jpeg_extractor given; models/DecompCNN_model.py): the model's fake_H holds DCT coefficients and its image is output_image (0...255),
 Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' in place of 'LR'.  Accepted there: 'l1', 'TV',
-'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', which read Output_Batch(within_0_1=True) only; every other name is refused.
+'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', which read Output_Batch(within_0_1=True) only; every other name is refused.  On a colour
+model (chroma_mode) Z_size is still the Y grid, the objectives see the RGB output, Z's gradient runs through both generators, and a model fed
+with the Y coefficients as 'Comp' gets data['uncompressed_chroma'] ([B, 2, H, W] Cb, Cr) passed to model.test.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective - with ONE exception: the random objectives compare
 every sample with every other, so each rank all-gathers the detached D of all ranks once per iteration, esr_hip.dist.all_gather_tensor, and
@@ -454,8 +456,9 @@ class Z_optimizer():
         self.STD_PRESERVING_WEIGHT = 100 if 'TV' in objective else 20      # reference Z_optimization.py:508-509 (TV), :471 (others)
 
     def _image(self):
-        """the model's output image before the clamp to [0, 1]: fake_H itself for the SR model, output_image / 255 in JPEG mode"""
-        return self.model.output_image / 255 if self.jpeg_mode else self.model.fake_H
+        """the model's output image before the clamp to [0, 1]: fake_H itself for the SR model; in JPEG mode output_image / 255, converted to
+        RGB for the colour model"""
+        return self.model.Output_Image_0_1() if self.jpeg_mode else self.model.fake_H
 
     def Masked_STD(self, first_image_only=False):
         if self.local_STD:
@@ -535,19 +538,26 @@ class Z_optimizer():
         if 'VGG' in self.objective and not self.random:
             self._set_desired_VGG(data['desired'])
 
+    def _generator_parameters(self):
+        """netG's and, on a colour JPEG model, the Y generator's that Z's gradient also runs through"""
+        params = list(self.model.netG.parameters())
+        if self.jpeg_mode and getattr(self.model, 'netG_Y', None) is not None:
+            params += list(self.model.netG_Y.parameters())
+        return params
+
     def Manage_Model_Grad_Requirements(self, verify_disabled):
         if verify_disabled:
             self.original_requires_grad_status = []
-            for p in self.model.netG.parameters():
+            for p in self._generator_parameters():
                 self.original_requires_grad_status.append(p.requires_grad)
                 p.requires_grad = False
         else:
-            for i, p in enumerate(self.model.netG.parameters()):
+            for i, p in enumerate(self._generator_parameters()):
                 p.requires_grad = self.original_requires_grad_status[i]
 
     def _local_data(self):
         d = dict(self.data)
-        keys = [k for k in ('Uncomp', 'Comp', 'QF') if k in d] if self.jpeg_mode else ['LR']
+        keys = [k for k in ('Uncomp', 'Comp', 'QF', 'uncompressed_chroma') if k in d] if self.jpeg_mode else ['LR']
         for k in keys:
             t = d[k]
             if t.size(0) == self.global_batch and self.global_batch > 1:
@@ -577,12 +587,16 @@ class Z_optimizer():
             data['Z'] = self.Z_model()
             if USE_MIN_LOSS_Z:
                 per_iter_pre_tanh_Z.append(1 * self.Z_model.PreTanhZ())
-            self.model.feed_data(data, need_GT=False)
+            # JPEG mode: a colour model fed with 'Uncomp' runs its Y generator here, with gradients (reference :678, detach_Y False outside training)
+            self.model.feed_data(data, need_GT=False, **({'detach_Y': False} if self.jpeg_mode else {}))
             # drop the previous iteration's output first: its graph holds the generator's saved-activation buffers, and a forward that finds
             # them busy allocates a second full set (2 x 90 GB at the configs[3] shape)
             self.output_image = Z_loss = loss = None
             self.model.fake_H = self.model.output_image = None
-            self.model.test(prevent_grads_calc=False)
+            if self.jpeg_mode and data.get('uncompressed_chroma') is not None:      # colour model fed with Y coefficients (reference :679)
+                self.model.test(prevent_grads_calc=False, uncompressed_chroma=data['uncompressed_chroma'])
+            else:
+                self.model.test(prevent_grads_calc=False)
             self.output_image = self.model.Output_Batch(within_0_1=True)
             if self.model_training:
                 self.output_image = self.HR_unpadder(self.output_image)

@@ -5,7 +5,8 @@ after the middle ones, nothing after the last.  Forward and input gradient, froz
 
   * activations live in the conv kernels' layout ([planes][B][CG][h+2][w+2][8] bf16, zero border; hi+lo planes in 'split')
   * every layer is ONE esr_conv3x3 launch: layer 0 act_slope = 0 (nn.ReLU), middle layers act_slope = 0.01 (nn.LeakyReLU()'s default),
-    the last layer identity, stored as fp32 NCHW (out_nchw): the PRE-sigmoid output y — the sigmoid, the "- 0.5", the addition to the
+    the last layer identity, stored as fp32 NCHW (out_nchw; one launch per 64 output channels — the chroma generator has 128): the
+    PRE-sigmoid output y — the sigmoid, the "- 0.5", the addition to the
     quantised coefficients and the inverse DCT are one esr_jpeg_extract launch (esr_hip/jpeg.py)
   * eval-mode BatchNorm (eps 1e-4) is folded into the conv before packing: rows scaled by weight / sqrt(running_var + eps), bias
     = bn.bias - running_mean * that scale
@@ -161,7 +162,17 @@ class DnCNNEngine:
         n = len(self.layers)
         for k, ly in enumerate(self.layers):
             if k == n - 1:
-                A.conv3x3(ly.fwd, view_of(t), B, h, w, ly.cout, out_nchw=y, act_slope=1.0, use_bias=ly.b is not None, reverse=False)
+                if ly.cout <= 64:
+                    A.conv3x3(ly.fwd, view_of(t), B, h, w, ly.cout, out_nchw=y, act_slope=1.0, use_bias=ly.b is not None, reverse=False)
+                    break
+                # more than 64 output channels (the chroma generator's 128): an fp32 NCHW store covers one 64-row slice of the pack per
+                # launch (esr_conv3x3: output slices exist for the activation layout only), each into its own tensor, copied into place
+                if ly.b is not None:
+                    raise EsrError('DnCNN: a last conv of %d > 64 channels with a bias' % ly.cout)
+                for s, part in enumerate(ly.fwd.parts):
+                    ys = torch.empty(B, 64, h, w, dtype=torch.float32, device=dev)
+                    A.conv3x3(part, view_of(t), B, h, w, 64, out_nchw=ys, act_slope=1.0, use_bias=False, reverse=False)
+                    y[:, 64 * s:64 * (s + 1)] = ys
                 break
             nxt = self.layers[k + 1]
             zg = nxt.lat // 8

@@ -1,6 +1,7 @@
-"""Host side of the JPEG consistency layer (reference codes/JPEG_module/JPEG.py, Y channel, block size 8): the 8x8 block DCT between an image
-[B, 1, H, W] (0...255) and its coefficient planes [B, 64, H/8, W/8] (channel 8u + v), the per-image quantisation table, and the generator's
-sigmoid tail (codes/models/modules/architecture.py:206, 214).
+"""Host side of the JPEG consistency layer (reference codes/JPEG_module/JPEG.py): for the Y channel (block size 8) the 8x8 block DCT between an
+image [B, 1, H, W] (0...255) and its coefficient planes [B, 64, H/8, W/8] (channel 8u + v), the per-image quantisation table, and the generator's
+sigmoid tail (codes/models/modules/architecture.py:206, 214); for the colour model (chroma_mode, block size 16) the 16x16 transform of a YCbCr
+image, compress16 / extract16 at the end of this file.
 
 * compress(x, qtab, quantize) -> coefficients = DCT(x - 128) / qtab, torch.round when quantize (whose gradient is zero, as the reference's).
 * extract(coef, qtab, y=None) -> (c, image): c = coef when y is None, else coef + sigmoid(y) - 0.5; image = 128 + iDCT(c * qtab).
@@ -175,3 +176,178 @@ def compress_into(x, qtab, quantize, act_view, want_coef=True):
     check(_lib.lib.esr_jpeg_compress(xd.data_ptr(), B, H, W, q.data_ptr(), 1 if quantize else 0, None if coef is None else coef.data_ptr(),
                                      C.byref(act_view), stream_ptr()), 'esr_jpeg_compress')
     return coef
+
+
+# ================================================================================================ the colour model: 16x16 blocks
+# (reference JPEG.py with chroma_mode=True, block_size=16, FACTORIZE_CHROMA_HIGH_FREQS).  Image [B, 3, H, W] YCbCr 0...255, h = H/16, w = W/16.
+# An image plane keeps K = 16 frequencies per axis (256 channels, 16u + v) or K = 8 (64 channels, 8u + v: the chroma down-sampling).
+# qtab is the padded table [B, 3, 16, 16, 1, 1] (JPEG.padded_Q_table), any shape with B * 768 or 768 entries.
+#   compress16(x, qtab, mode): mode False -> [B, 768, h, w] (Y | Cb | Cr, K = 16, unrounded); 'downsample_only' -> [B, 384, h, w]
+#       (Y K = 16 | Cb | Cr K = 8, unrounded); True -> the same with Cb and Cr rounded (zero gradient there); Y is never rounded.
+#   extract16(coef, qtab, y=None) -> (c, image): by the channel count 128 (Cb, Cr low -> [B, 2, H, W]), 512 (Cb, Cr full -> [B, 2, H, W]) or
+#       384 (Y | Cb, Cr low -> [B, 3, H, W], + 128 on Y).  With y [B, 128, h, w], the chroma generator's last conv output, coef is the
+#       generator's 384 input coefficients (or their last 128): c = coef[:, -128:] + sigmoid(y) - 0.5, image [B, 2, H, W].
+MODES16 = {False: 0, 'downsample_only': 1, True: 2}          # ESR_JPEG16_ALL / _DOWNSAMPLE / _QUANTIZE
+
+
+def dct_matrix16(dtype=torch.float32, device='cpu'):
+    """D[k, n] = a(k) cos((2n + 1) k pi / 32), a(0) = 1/4, a(k > 0) = sqrt(1/8): orthonormal.  Computed in float64."""
+    k = torch.arange(16, dtype=torch.float64).view(16, 1)
+    n = torch.arange(16, dtype=torch.float64).view(1, 16)
+    D = torch.cos((2 * n + 1) * k * math.pi / 32) * math.sqrt(0.125)
+    D[0] = 0.25
+    return D.to(dtype=dtype, device=device)
+
+
+def _qtab16_for(qtab, B, device):
+    q = qtab.detach().reshape(-1, 3, 256).to(device=device, dtype=torch.float32)
+    if q.size(0) != B:
+        if q.size(0) != 1:
+            raise ValueError('JPEG: %d quantisation tables for %d images' % (q.size(0), B))
+        q = q.expand(B, 3, 256)
+    return q.contiguous()
+
+
+def _mode16(mode):
+    if not any(mode is m for m in (True, False)) and mode != 'downsample_only':
+        raise ValueError("JPEG compress16: mode True, False or 'downsample_only', got %r" % (mode,))
+    return MODES16[mode]
+
+
+def _planes16(form):
+    """(image planes, K per plane) of an extractor form"""
+    return {128: (2, (8, 8)), 512: (2, (16, 16)), 384: (3, (16, 8, 8))}[form]
+
+
+def _compress16_cpu(x, qtab, mode):
+    B, _, H, W = x.shape
+    h, w = H // 16, W // 16
+    D = dct_matrix16(x.dtype, x.device)
+    blocks = x.reshape(B, 3, h, 16, w, 16) - torch.tensor([128., 0., 0.], dtype=x.dtype, device=x.device).view(1, 3, 1, 1, 1, 1)
+    out = torch.einsum('ur,bcirjs,vs->bcuvij', D, blocks, D) / qtab.view(B, 3, 16, 16, 1, 1).to(x.dtype)
+    if mode == 0:
+        return out.reshape(B, 768, h, w)
+    chroma = out[:, 1:, :8, :8]
+    if mode == 2:
+        chroma = torch.round(chroma)
+    return torch.cat([out[:, 0].reshape(B, 256, h, w), chroma.reshape(B, 128, h, w)], 1)
+
+
+def _extract16_cpu(coef, qtab, y):
+    B, C, h, w = coef.shape
+    if y is not None:
+        coef = coef[:, C - 128:] + (torch.sigmoid(y) - 0.5)
+    form = coef.size(1)
+    n, Ks = _planes16(form)
+    D = dct_matrix16(coef.dtype, coef.device)
+    planes, c0 = [], 0
+    for K in Ks:
+        p = coef[:, c0:c0 + K * K].reshape(B, 1, K, K, h, w)
+        planes.append(p if K == 16 else torch.nn.functional.pad(p, [0, 0, 0, 0, 0, 8, 0, 8]))
+        c0 += K * K
+    full = torch.cat(planes, 1) * qtab.view(B, 3, 16, 16, 1, 1)[:, 3 - n:].to(coef.dtype)
+    img = torch.einsum('ur,bcuvij,vs->bcirjs', D, full, D).reshape(B, n, 16 * h, 16 * w)
+    if n == 3:
+        img = img + torch.tensor([128., 0., 0.], dtype=img.dtype, device=img.device).view(1, 3, 1, 1)
+    return coef, img
+
+
+class _Compress16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, qtab, mode):
+        xd = _f32c(x)
+        B, _, H, W = xd.shape
+        coef = torch.empty(B, 768 if mode == 0 else 384, H // 16, W // 16, dtype=torch.float32, device=xd.device)
+        check(_lib.lib.esr_jpeg16_compress(xd.data_ptr(), B, H, W, qtab.data_ptr(), mode, coef.data_ptr(), stream_ptr()), 'esr_jpeg16_compress')
+        ctx.mode, ctx.qtab = mode, qtab
+        return coef
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_coef):
+        B, _, h, w = d_coef.shape
+        g = _f32c(d_coef)
+        # the rounded Cb, Cr planes of the quantising mode: zero gradient (torch.round, JPEG.py:148); the kernel then writes the Y plane only
+        dx = (torch.zeros if ctx.mode == 2 else torch.empty)(B, 3, 16 * h, 16 * w, dtype=torch.float32, device=g.device)
+        check(_lib.lib.esr_jpeg16_compress_grad(g.data_ptr(), ctx.mode, B, h, w, ctx.qtab.data_ptr(), dx.data_ptr(), stream_ptr()),
+              'esr_jpeg16_compress_grad')
+        return dx, None, None
+
+
+def _extract16_launch(coef, y, qtab, want_c):
+    B, C, h, w = coef.shape
+    form = 128 if y is not None else C
+    img = torch.empty(B, _planes16(form)[0], 16 * h, 16 * w, dtype=torch.float32, device=coef.device)
+    c = torch.empty(B, 128, h, w, dtype=torch.float32, device=coef.device) if want_c else None
+    check(_lib.lib.esr_jpeg16_extract(coef.data_ptr(), C, C - form, None if y is None else y.data_ptr(), form, B, h, w, qtab.data_ptr(),
+                                      None if c is None else c.data_ptr(), img.data_ptr(), stream_ptr()), 'esr_jpeg16_extract')
+    return c, img
+
+
+class _Extract16(torch.autograd.Function):
+    """(coef, y | None, qtab) -> (c, image).  Backward: one esr_jpeg16_extract_grad launch for the image's gradient; a gradient arriving at c
+    itself is added with torch ops.  With y, coef may be the generator's whole 384-channel input: its leading channels get zero."""
+
+    @staticmethod
+    def forward(ctx, coef, y, qtab):
+        cd, yd = _f32c(coef), (None if y is None else _f32c(y))
+        c, img = _extract16_launch(cd, yd, qtab, want_c=yd is not None)
+        ctx.qtab, ctx.y, ctx.C = qtab, yd, cd.size(1)
+        ctx.set_materialize_grads(False)
+        return (cd.clone() if c is None else c), img          # (an output of its own: a Function does not hand an input back)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_c, d_img):
+        y, need_coef, need_y = ctx.y, ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.y is not None
+        form = 128 if y is not None else ctx.C
+        d_coef = d_y = None
+        if d_img is not None:
+            g = _f32c(d_img)
+            B, h, w = g.size(0), g.size(2) // 16, g.size(3) // 16
+            d_coef = torch.empty(B, form, h, w, dtype=torch.float32, device=g.device) if (need_coef or d_c is not None) else None
+            d_y = torch.empty(B, 128, h, w, dtype=torch.float32, device=g.device) if need_y else None
+            if d_coef is not None or d_y is not None:
+                check(_lib.lib.esr_jpeg16_extract_grad(g.data_ptr(), None if d_y is None else y.data_ptr(), form, B, h, w, ctx.qtab.data_ptr(),
+                                                       None if d_coef is None else d_coef.data_ptr(), None if d_y is None else d_y.data_ptr(),
+                                                       stream_ptr()), 'esr_jpeg16_extract_grad')
+        if d_c is not None:
+            d_c = d_c.detach().float()
+            d_coef = d_c if d_coef is None else d_coef + d_c
+            if need_y:
+                s = torch.sigmoid(y)
+                d_y = d_c * s * (1 - s) + (0 if d_y is None else d_y)
+        if need_coef and d_coef is not None and d_coef.size(1) != ctx.C:
+            d_coef = torch.nn.functional.pad(d_coef, [0, 0, 0, 0, ctx.C - d_coef.size(1), 0])
+        return (d_coef if need_coef else None), (d_y if need_y else None), None
+
+
+def _check_image16(x):
+    if x.dim() != 4 or x.size(1) != 3 or x.size(2) % 16 or x.size(3) % 16 or x.size(2) == 0 or x.size(3) == 0:
+        raise ValueError('JPEG compress16: a [B, 3, H, W] image with H and W multiples of 16, got %s' % (tuple(x.shape),))
+
+
+def compress16(x, qtab, mode):
+    """[B, 3, H, W] YCbCr -> [B, 768 | 384, H/16, W/16] (JPEG.py:131-154)"""
+    _check_image16(x)
+    m = _mode16(mode)
+    q = _qtab16_for(qtab, x.size(0), x.device)
+    if not x.is_cuda:
+        return _compress16_cpu(x, q, m)
+    return _Compress16.apply(x, q, m)
+
+
+def extract16(coef, qtab, y=None):
+    """(c, image) (JPEG.py:165-201; with y the chroma generator's tail, architecture.py:206-212, in front)"""
+    if coef.dim() != 4 or coef.numel() == 0 or coef.size(1) not in ((128, 384) if y is not None else (128, 384, 512)):
+        raise Exception('Unexpected input size')                # (the reference's words, JPEG.py:185)
+    if y is not None and (y.dim() != 4 or y.size(1) != 128 or y.shape[2:] != coef.shape[2:] or y.size(0) != coef.size(0) or y.device != coef.device):
+        raise ValueError('JPEG extract16: generator output %s on %s for coefficients %s on %s' % (tuple(y.shape), y.device, tuple(coef.shape), coef.device))
+    q = _qtab16_for(qtab, coef.size(0), coef.device)
+    if not coef.is_cuda:
+        return _extract16_cpu(coef, q, y)
+    if torch.is_grad_enabled() and (coef.requires_grad or (y is not None and y.requires_grad)):
+        return _Extract16.apply(coef, y, q)
+    cd, yd = _f32c(coef), (None if y is None else _f32c(y))
+    c, img = _extract16_launch(cd, yd, q, want_c=yd is not None)
+    return (cd if c is None else c), img

@@ -1,16 +1,23 @@
 """DecompCNNModel — the explorable JPEG decoder's model wrapper (reference codes/models/DecompCNN_model.py), inference surface: feed_data /
-test / Output_Batch / GetLatent / load with the reference's names, for the Y-channel (grey-scale) model.  Training (is_train), the chroma
-model and Enforce_pair_Consistency are not part of this build.
+test / Output_Batch / GetLatent / load with the reference's names, for the Y-channel (grey-scale) model and, with chroma_mode=True, the colour
+model that contains it.  Training (is_train) and Enforce_pair_Consistency are not part of this build.
 
+Y model (8x8 blocks):
     compressed coefficients = JPEG['compressor'](image)            [B, 64, H/8, W/8], quantised with the image's QF table
     fake_H       = netG([Z | coefficients])                        the generator's coefficients: within +-0.5 of the quantised ones (Sigmoid - 0.5),
                                                                    so re-compressing the output gives the input back
     output_image = JPEG['extractor'](fake_H)                       [B, 1, H, W], 0...255
-On the GPU test() runs the DnCNN engine up to the last conv and ONE esr_jpeg_extract launch that applies the sigmoid tail, produces fake_H and
-the image (esr_hip/jpeg.py); on the CPU it is the composition of the three modules."""
+Colour model (16x16 blocks, 4:2:0: Cb and Cr keep their low 8x8 frequencies):
+    y_channel_input = clamp(JPEG['extractor_Y'](netG_Y([Z | Y coefficients])), 0, 255)          the Y model, on the 8x8 grid
+    var_Comp     = JPEG['compressor']([y_channel_input | Cb | Cr])  [B, 384, H/16, W/16]: Y's 256 coefficients unrounded | Cb, Cr low, rounded
+    fake_H       = netG([Z resized to the 16x16 grid | var_Comp])   [B, 128, H/16, W/16]
+    output_image = [y_channel_input | JPEG['extractor'](fake_H)]    [B, 3, H, W] YCbCr; Output_Batch(True) converts to RGB
+On the GPU each generator runs on the DnCNN engine up to its last conv, and ONE esr_jpeg_extract / esr_jpeg16_extract launch applies the
+sigmoid tail and produces fake_H and the image (esr_hip/jpeg.py); on the CPU it is the composition of the modules."""
 import os
 import re
 from collections import OrderedDict
+from copy import deepcopy
 
 import numpy as np
 import torch
@@ -22,32 +29,63 @@ from .base_model import BaseModel
 from .modules.loss import Latent_channels_desc_2_num_channels
 
 
+def Tensor_YCbCR2RGB(image):
+    """[B, 3, H, W] YCbCr in 0...1 -> RGB (reference utils/util.py:328-330).  ITU-R BT.601 studio-range YCbCr (Y 16...235, Cb, Cr 16...240) to
+    full-range RGB: R = 255/219 (Y - 16) + 255/224 * 1.402 (Cr - 128), and so on, in the rounded form the reference carries (its matrix is per
+    unit of an 8-bit value, hence the factor 255)."""
+    mat = 255 * np.array([[0.00456621, 0.00456621, 0.00456621], [0, -0.00153632, 0.00791071], [0.00625893, -0.00318811, 0]]).transpose()
+    mat = torch.from_numpy(mat).view(1, 3, 3, 1, 1).to(device=image.device, dtype=image.dtype)
+    offset = torch.tensor([-222.921, 135.576, -276.836], device=image.device, dtype=image.dtype).view(1, 3, 1, 1) / 255
+    return (mat * image.unsqueeze(1)).sum(2) + offset
+
+
 class DecompCNNModel(BaseModel):
     def __init__(self, opt, accumulation_steps_per_batch=None, init_Fnet=None, init_Dnet=None, chroma_mode=False, **kwargs):
         super(DecompCNNModel, self).__init__(opt)
         if self.is_train:
             raise NotImplementedError('DecompCNNModel with is_train: this build runs the explorable JPEG decoder for inference and the Z search only')
-        if chroma_mode:
-            raise NotImplementedError('DecompCNNModel(chroma_mode=True): this build runs the Y-channel (grey-scale) model only')
+        if chroma_mode and opt['scale'] != 16:
+            raise NotImplementedError("DecompCNNModel(chroma_mode=True) with opt['scale'] = %r: the colour model works on 16x16 blocks; parse the "
+                                      'options with parse(..., JPEG=True, chroma=True)' % (opt['scale'],))
+        if not chroma_mode and opt['scale'] != 8:
+            raise NotImplementedError("DecompCNNModel with opt['scale'] = %r: options parsed with chroma=True build the colour model, "
+                                      'DecompCNNModel(opt, chroma_mode=True)' % (opt['scale'],))
         self.log_path = opt['path']['log']
         self.latent_input = opt['network_G']['latent_input'] if opt['network_G']['latent_input'] != 'None' else None
         if self.latent_input is not None:
             self.Z_size_factor = 1
-        self.chroma_mode = False
+        self.chroma_mode = bool(chroma_mode)
         self.cri_latent = None
         self.num_latent_channels = Latent_channels_desc_2_num_channels(opt['network_G']['latent_channels'])
         if self.latent_input is not None:
             assert isinstance(opt['network_G']['latent_channels'], int)
         self.step = 0
-        self.JPEG = {'compressor': JPEG(compress=True, chroma_mode=False, downsample_or_quantize=True, block_size=self.opt['scale']),
-                     'extractor': JPEG(compress=False, chroma_mode=False, block_size=self.opt['scale']),
-                     'non_quantized_compressor': JPEG(compress=True, downsample_or_quantize=False, chroma_mode=False, block_size=8)}
-        self.netG = networks.define_G(opt, num_latent_channels=self.num_latent_channels, chroma_mode=False).to(self.device)
+        cm = self.chroma_mode
+        self.JPEG = {'compressor': JPEG(compress=True, chroma_mode=cm, downsample_or_quantize=True, block_size=self.opt['scale']),
+                     'extractor': JPEG(compress=False, chroma_mode=cm, block_size=self.opt['scale'])}
+        self.netG = networks.define_G(opt, num_latent_channels=self.num_latent_channels, chroma_mode=cm,
+                                      no_high_freq_chroma_reconstruction=True).to(self.device)
         self.netG.eval()
+        if cm:                                   # the colour model contains the Y model (reference :63-71, USE_Y_GENERATOR_4_CHROMA)
+            netG_Y_opt = deepcopy(opt)
+            for key, value in (netG_Y_opt['network_G_Y'] or {}).items():
+                netG_Y_opt['network_G'][key] = value
+            self.netG_Y = networks.define_G(netG_Y_opt, num_latent_channels=self.num_latent_channels, chroma_mode=False).to(self.device)
+            self.netG_Y.eval()
+            self.JPEG['compressor_Y'] = JPEG(compress=True, chroma_mode=False, downsample_or_quantize=True, block_size=8)
+            self.JPEG['extractor_Y'] = JPEG(compress=False, chroma_mode=False, block_size=8)
+        self.JPEG['non_quantized_compressor' + ('_Y' if cm else '')] = JPEG(compress=True, downsample_or_quantize=False, chroma_mode=False, block_size=8)
+        if cm:                                   # (reference :114-117 with NO_HIGH_FREQ_CHROMA_RECONSTRUCTION)
+            self.JPEG['non_quantized_compressor'] = JPEG(compress=True, downsample_or_quantize='downsample_only', chroma_mode=True,
+                                                         block_size=self.opt['scale'])
         self.load()
 
     # ------------------------------------------------------------------ input
-    def feed_data(self, data, need_GT=False, **kwargs):
+    def feed_data(self, data, need_GT=False, detach_Y=True, **kwargs):
+        """data: 'QF' and either 'Uncomp' (an image: [B, 1, H, W], or [B, 3, H, W] YCbCr for the colour model, whose Y model then runs here —
+        with gradients when detach_Y is False) or 'Comp' (coefficients; for the colour model the Y channel's [B, 64, H/8, W/8], followed by
+        test(uncompressed_chroma=[B, 2, H, W])); optionally 'Z' on the Y grid [H/8, W/8].  The caller's tensors are left as they are (the
+        reference writes the generated Y channel into data['Uncomp'])."""
         self.QF = data['QF']
         for module in self.JPEG.values():
             module.Set_Q_Table(self.QF)
@@ -70,7 +108,12 @@ class DecompCNNModel(BaseModel):
         if 'Comp' in data.keys():
             self.Prepare_Input(data['Comp'].to(self.device), latent_input=cur_Z, compressed_input=True)
         else:
-            self.Prepare_Input(data['Uncomp'].to(self.device), latent_input=cur_Z)
+            uncomp = data['Uncomp'].to(self.device)
+            if self.chroma_mode and uncomp.size(1) == 3:                     # (reference :374-384)
+                self.Prepare_Input(uncomp[:, :1], cur_Z)
+                self.test_Y(detach=detach_Y, prevent_grads_calc=detach_Y)
+                uncomp = torch.cat([self.y_channel_input, uncomp[:, 1:].to(self.y_channel_input.dtype)], 1)
+            self.Prepare_Input(uncomp, latent_input=cur_Z)
         if need_GT:
             self.var_Uncomp = data['Uncomp'].to(self.device)
 
@@ -78,13 +121,19 @@ class DecompCNNModel(BaseModel):
         if compressed_input:
             self.var_Comp = im_input
         else:
-            if im_input.size(1) != 1:
-                raise NotImplementedError('DecompCNNModel: a %d-channel image; this build runs the Y-channel (grey-scale) model only' % im_input.size(1))
-            self.var_Comp = self.JPEG['compressor'](im_input)
+            if im_input.size(1) not in ((1, 3) if self.chroma_mode else (1,)):      # (the colour model also takes its Y channel alone)
+                raise ValueError('DecompCNNModel: a %d-channel image for the %s model' % (im_input.size(1), 'colour' if self.chroma_mode else 'Y-channel'))
+            if self.chroma_mode and im_input.size(1) == 1:
+                self.var_Comp = self.JPEG['compressor_Y'](im_input)
+            else:
+                self.var_Comp = self.JPEG['compressor'](im_input)
         if latent_input is not None and latent_input.numel() > 0:
-            if self.var_Comp.size()[2:] != latent_input.size()[2:]:
-                raise ValueError('Z of size %s for %s blocks' % (tuple(latent_input.shape[2:]), tuple(self.var_Comp.shape[2:])))
             latent_input = latent_input.to(device=self.var_Comp.device, dtype=self.var_Comp.dtype)
+            if self.var_Comp.size()[2:] != latent_input.size()[2:]:
+                # Z lives on the Y grid; the chroma generator's blocks are twice as large (reference :282-284)
+                if not self.chroma_mode or [2 * v for v in self.var_Comp.shape[2:]] != list(latent_input.shape[2:]):
+                    raise ValueError('Z of size %s for %s blocks' % (tuple(latent_input.shape[2:]), tuple(self.var_Comp.shape[2:])))
+                latent_input = torch.nn.functional.interpolate(latent_input, size=self.var_Comp.shape[2:], mode='bilinear', align_corners=True)
             if latent_input.size(0) != self.var_Comp.size(0):
                 latent_input = latent_input.expand(self.var_Comp.size(0), -1, -1, -1)
             self.model_input = torch.cat([latent_input, self.var_Comp], dim=1)
@@ -99,18 +148,45 @@ class DecompCNNModel(BaseModel):
         return inconsostent_output
 
     def Enforce_pair_Consistency(self, compressed_im, desired_im):
-        raise NotImplementedError('Enforce_pair_Consistency belongs to the chroma model, which this build does not run')
+        raise NotImplementedError("Enforce_pair_Consistency: the reference's own version reads JPEG['compressor_Y_non_quantized'] and "
+                                  "JPEG['compressor_non_quantized'], keys its model never defines (only its GUI adds them); not part of this build")
 
-    def test_(self):
-        self.netG.eval()
-        G = self.netG
+    def _generate(self, G, extractor, chroma):
+        """(generator's coefficients, their image) for the current model_input / var_Comp"""
         if getattr(G, 'output_layer', None) == 'Sigmoid' and G.on_kernels(self.model_input):
             # the generator's tail (sigmoid - 0.5 + quantised coefficients) and the extractor in one launch
             y = G.pre_output(self.model_input)
-            self.fake_H, self.output_image = esr_jpeg.extract(self.var_Comp, self.JPEG['extractor']._table_on(self.var_Comp.device), y)
+            return (esr_jpeg.extract16 if chroma else esr_jpeg.extract)(self.var_Comp, extractor._table_on(self.var_Comp.device), y)
+        fake = self.Enforce_Consistency(self.var_Comp, G(self.model_input))
+        return fake, extractor(fake)
+
+    def test_Y(self, prevent_grads_calc=True, **kwargs):
+        if prevent_grads_calc:
+            with torch.no_grad():
+                self.test_Y_(**kwargs)
         else:
-            self.fake_H = self.Enforce_Consistency(self.var_Comp, G(self.model_input))
-            self.output_image = self.JPEG['extractor'](self.fake_H)
+            self.test_Y_(**kwargs)
+
+    def test_Y_(self, detach=False):
+        """the Y model on the current model_input = [Z | Y coefficients] (reference :711-715)"""
+        self.netG_Y.eval()
+        self.y_channel_input = torch.clamp(self._generate(self.netG_Y, self.JPEG['extractor_Y'], False)[1], 0, 255)
+        if detach:
+            self.y_channel_input = self.y_channel_input.detach()
+
+    def test_(self, uncompressed_chroma=None, detach_Y=False, chroma_Z=None):
+        self.netG.eval()
+        if uncompressed_chroma is not None:          # colour model fed with the Y coefficients (reference :720-724)
+            if not self.chroma_mode:
+                raise ValueError('DecompCNNModel.test(uncompressed_chroma=...) belongs to the colour model (chroma_mode=True)')
+            self.test_Y(detach=detach_Y, prevent_grads_calc=False)   # (whether to keep gradients was decided by test())
+            uncompressed_chroma = uncompressed_chroma.to(device=self.y_channel_input.device, dtype=self.y_channel_input.dtype)
+            if uncompressed_chroma.size(0) != self.y_channel_input.size(0):
+                uncompressed_chroma = uncompressed_chroma.repeat([self.y_channel_input.size(0)] + [1] * (uncompressed_chroma.ndimension() - 1))
+            self.Prepare_Input(torch.cat([self.y_channel_input, uncompressed_chroma], 1), self.GetLatent() if chroma_Z is None else chroma_Z)
+        self.fake_H, self.output_image = self._generate(self.netG, self.JPEG['extractor'], self.chroma_mode)
+        if self.chroma_mode:
+            self.output_image = torch.cat([self.y_channel_input, self.output_image], 1)
 
     def test(self, prevent_grads_calc=True, **kwargs):
         if prevent_grads_calc:
@@ -119,13 +195,25 @@ class DecompCNNModel(BaseModel):
         else:
             self.test_(**kwargs)
 
+    def Output_Image_0_1(self):
+        """the output before the clamp to [0, 1], as Output_Batch(within_0_1=True) clamps it: RGB for the colour model"""
+        if self.output_image.size(1) == 3:
+            return Tensor_YCbCR2RGB(self.output_image / 255)
+        return self.output_image / 255
+
     def Output_Batch(self, within_0_1):
         if within_0_1:
-            return torch.clamp(self.output_image / 255, 0, 1)
+            return torch.clamp(self.Output_Image_0_1(), 0, 1)
         return self.output_image
 
     def Return_Compressed(self, uncompressed):
-        assert uncompressed.size(1) != 3, 'Got a color image when model is not supporting it'
+        chroma_input = uncompressed.size(1) == 3
+        assert self.chroma_mode or not chroma_input, 'Got a color image when model is not supporting it'
+        if self.chroma_mode:
+            Y_channel = self.JPEG['extractor_Y'](self.JPEG['compressor_Y'](uncompressed[:, :1]))
+            if not chroma_input:
+                return Y_channel
+            return self.JPEG['extractor'](self.JPEG['compressor'](torch.cat([Y_channel, uncompressed[:, 1:]], 1)))
         return self.JPEG['extractor'](self.JPEG['compressor'](uncompressed))
 
     def get_current_visuals(self, need_Uncomp=True, entire_batch=False):
@@ -142,7 +230,11 @@ class DecompCNNModel(BaseModel):
         print('Number of parameters in G: {:,d}'.format(n))
 
     def load(self, max_step=None, resume_train=None):
-        """The newest '<step>_G.pth' under path.models (up to max_step) when there is one, else path.pretrained_model_G (reference :1007-1045)."""
+        """The newest '<step>_G.pth' under path.models (up to max_step) when there is one, else path.pretrained_model_G (reference :1007-1045);
+        the colour model's netG_Y from path.Y_channel_model_G (:1049-1051)."""
+        if self.chroma_mode and self.opt['path']['Y_channel_model_G'] is not None:
+            print('loading model for G of channel Y [{:s}] ...'.format(self.opt['path']['Y_channel_model_G']))
+            self.load_network(self.opt['path']['Y_channel_model_G'], self.netG_Y)
         models_dir = self.opt['path']['models']
         step_of = lambda name: int(re.search(r'(\d)+(?=_G.pth)', name).group(0))
         own = sorted((n for n in (os.listdir(models_dir) if models_dir and os.path.isdir(models_dir) else []) if re.search(r'\d+_G\.pth$', n)), key=step_of)

@@ -2,7 +2,8 @@
 import importlib
 
 # opt['model'] -> (module, class).  'srgan' (codes/models/SRGAN_model.py) cannot run in the reference (undefined `need_HR`, :127-130); both
-# GAN names resolve to the live SRRaGAN wrapper here.  'dncnn' is explorable JPEG decoding (codes/models/DecompCNN_model.py), inference surface.
+# GAN names resolve to the live SRRaGAN wrapper here.  'dncnn' is explorable JPEG decoding (codes/models/DecompCNN_model.py), inference surface;
+# create_model(opt, chroma_mode=True) builds its colour model.
 _WRAPPERS = {'srragan': ('SRRaGAN_model', 'SRRaGANModel'), 'srgan': ('SRRaGAN_model', 'SRRaGANModel'), 'dncnn': ('DecompCNN_model', 'DecompCNNModel')}
 _OUT_OF_SCOPE = {}
 

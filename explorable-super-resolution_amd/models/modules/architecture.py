@@ -278,6 +278,9 @@ class DnCNN(nn.Module):
     ('all_layers'); the output is quantised coefficients + (sigmoid - 0.5).  `dncnn` is the reference's ModuleList, so state_dict keys
     (dncnn.0.weight, dncnn.3.running_mean, ...) and positional checkpoint loading are the reference's.
 
+    chroma_generator=True (in_nc 384, out_nc 128; :207-212): the input coefficients are Y's 256 | the quantised low 8x8 of Cb | of Cr on the 16x16
+    block grid, the output is those last 128 + (sigmoid - 0.5): the chroma planes' low frequencies, the only ones the colour model reconstructs.
+
     On the GPU in eval() the conv chain runs on the library's kernels (esr_hip/dncnn.py: forward and input gradient, BatchNorm folded, frozen
     weights; set_precision picks 'split' — fp32-class, the default — or 'bf16').  CPU tensors and training mode run the stock modules."""
 
@@ -290,8 +293,9 @@ class DnCNN(nn.Module):
         assert output_layer in ['Sigmoid', 'ReLU', None]
         if discriminator:
             raise NotImplementedError('DnCNN(discriminator=True): the DnCNN critic belongs to training the JPEG model, which this build does not do')
-        if chroma_generator:
-            raise NotImplementedError('DnCNN(chroma_generator=True): this build runs the Y-channel (grey-scale) model only')
+        if chroma_generator and not (in_nc - 256 == out_nc == 128):
+            raise NotImplementedError('DnCNN(chroma_generator=True, in_nc=%r, out_nc=%r): the chroma generator reads Y\'s 256 coefficients and the 2 x 64 '
+                                      'low chroma ones and estimates the latter: in_nc = 384, out_nc = 128 (define_G with chroma_mode)' % (in_nc, out_nc))
         if norm_type in ('layer', 'instance'):
             raise NotImplementedError("DnCNN(norm_type=%r): 'batch' (folded into the convs in eval mode) or None" % (norm_type,))
         if avoid_padding:
@@ -302,7 +306,7 @@ class DnCNN(nn.Module):
         if kernel_size != 3:
             raise NotImplementedError('DnCNN(kernel_size=%r): 3' % (kernel_size,))
         self.discriminator_net = False
-        self.chroma_generator = False
+        self.chroma_generator = bool(chroma_generator)
         self.margins = 0
         self.latent_input = latent_input
         self.num_latent_channels = num_latent_channels
@@ -357,7 +361,7 @@ class DnCNN(nn.Module):
         return x
 
     def forward(self, x):
-        quantized_coeffs = x[:, self.num_latent_channels:]
+        quantized_coeffs = x[:, self.num_latent_channels + (256 if self.chroma_generator else 0):]
         if self.on_kernels(x):
             y = self.pre_output(x)
             if self.output_layer == 'Sigmoid':

@@ -81,11 +81,14 @@ def define_G(opt, CEM=None, num_latent_channels=None, **kwargs):
                             latent_input=(opt_net['latent_input'] + '_' + opt_net['latent_input_domain']) if opt_net['latent_input'] is not None else None,
                             num_latent_channels=num_latent_channels)
     elif which_model == 'DnCNN':
-        if kwargs.get('chroma_mode', False):
-            raise NotImplementedError('Generator model [DnCNN] with chroma_mode: this build runs the Y-channel (grey-scale) model only')
-        netG = arch.DnCNN(n_channels=opt_net['nf'], depth=opt_net['nb'], in_nc=64, out_nc=64, norm_type=opt_net['norm_type'],
-                          latent_input=opt_net['latent_input'], num_latent_channels=num_latent_channels, chroma_generator=False,
-                          avoid_padding=not bool(opt_net['padding']), output_layer='Sigmoid')
+        chroma_mode = bool(kwargs.get('chroma_mode', False))
+        if chroma_mode and not kwargs.get('no_high_freq_chroma_reconstruction', True):
+            raise NotImplementedError('Generator model [DnCNN] with no_high_freq_chroma_reconstruction=False (a 2 x 256-channel chroma output): the '
+                                      'reference\'s model fixes it to True, and so does this build')
+        in_nc = opt['scale'] ** 2 + 2 * 64 if chroma_mode else 64               # (reference networks.py:103-106)
+        netG = arch.DnCNN(n_channels=opt_net['nf'], depth=opt_net['nb'], in_nc=in_nc, out_nc=2 * 64 if chroma_mode else 64,
+                          norm_type=opt_net['norm_type'], latent_input=opt_net['latent_input'], num_latent_channels=num_latent_channels,
+                          chroma_generator=chroma_mode, avoid_padding=not bool(opt_net['padding']), output_layer='Sigmoid')
     elif which_model in ('sr_resnet', 'MSRResNet'):
         raise NotImplementedError('Generator model [{:s}] is outside the RRDB+CEM hot path of this build'.format(which_model))
     else:

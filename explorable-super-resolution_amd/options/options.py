@@ -1,7 +1,7 @@
 """Option files: JSON with `//` comments -> nested dict -> NoneDict, with the path / batch-size derivations the drivers rely on.
 Same entry points as the reference's codes/options/options.py (parse, save, dict_to_nonedict, NoneDict).  parse(..., JPEG=True) resolves the
-explorable-JPEG files' ModelY dictionaries (Y-channel model; chroma=True is refused); the machine-specific dataset-root rewriting of the
-reference is not reproduced.
+explorable-JPEG files' ModelY dictionaries, and with chroma=True their ModelChroma ones (the colour model: scale 16, the '_chroma' dataset
+modes, the 'chroma_' name prefix); the machine-specific dataset-root rewriting of the reference is not reproduced.
 """
 import json
 import os
@@ -63,16 +63,37 @@ def parse(opt_path, is_train=True, batch_size_multiplier=None, **kwargs):
     return opt
 
 
+def _check_chroma_generator(netG):
+    """The chroma generator's first conv reads latent_channels + 384 channels on the conv kernels, which take up to 64 or a multiple of 64
+    channels starting on a group of 8 (esr_hip/dncnn.py: check_shapes): refused where the options are read, by name."""
+    if netG.get('latent_input', 'None') in ('None', None):
+        return
+    L = netG.get('latent_channels')
+    if not isinstance(L, int) or L % 64:
+        raise NotImplementedError('parse(JPEG=True, chroma=True): network_G latent_channels = %r for ModelChroma. The chroma generator\'s first conv '
+                                  'reads latent_channels + 384 channels and the conv kernels take a multiple of 64 there: latent_channels 0 '
+                                  '(latent_input "None"), 64 (the shipped setting), 128, ...' % (L,))
+
+
 def parse_conf(opt_path, is_train=True, batch_size_multiplier=None, **kwargs):
     name = kwargs.get('name')
     JPEG_run = bool(kwargs.get('JPEG'))
-    if JPEG_run and kwargs.get('chroma'):
-        raise NotImplementedError('parse(JPEG=True, chroma=True): this build runs the Y-channel (grey-scale) JPEG model only')
+    JPEG_chroma = JPEG_run and bool(kwargs.get('chroma'))
     opt = json.loads(_strip_comments(opt_path), object_pairs_hook=OrderedDict)
     opt = dictionary_values_choice(opt, 'PhaseInit' if kwargs.get('initialization') else 'PhaseGAN')
-    if JPEG_run:                                     # reference options.py:68-85, Y-channel branch
-        opt = dictionary_values_choice(opt, 'ModelY')
+    if JPEG_run:                                     # reference options.py:68-85
+        opt = dictionary_values_choice(opt, 'ModelChroma' if JPEG_chroma else 'ModelY')
         opt['input_downsampling'] = 1
+        if JPEG_chroma:
+            _check_chroma_generator(opt['network_G'])
+            opt['input_downsampling'] = 2            # 4:2:0: the chroma planes at half the resolution
+            for dataset in opt.get('datasets', {}).values():
+                if dataset['mode'][-len('_chroma'):] != '_chroma':
+                    dataset['mode'] += '_chroma'
+                dataset['input_downsampling'] = opt['input_downsampling']
+            parts = opt['name'].split('/')
+            if parts[-1][:len('chroma_')] != 'chroma_':
+                opt['name'] = os.path.join('/'.join(parts[:-1]), 'chroma_' + parts[-1])
         if opt['name'][:len('JPEG/')] != 'JPEG/':
             opt['name'] = os.path.join('JPEG', opt['name'])
         opt['scale'] = 8 * opt['input_downsampling']

@@ -657,6 +657,38 @@ int esr_jpeg_extract_grad(const float* d_img, const float* y, int B, int h, int 
  *   gradient is zero: no kernel.) */
 int esr_jpeg_compress_grad(const float* d_coef, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream);
 
+/* ---- the colour model of the explorable JPEG decoder: the 16x16 block DCT of 4:2:0 chroma (codes/JPEG_module/JPEG.py, chroma_mode, block 16) ----
+ * Images are fp32 [B][C][H][W] (YCbCr, 0...255), h = H/16, w = W/16.  Every image plane keeps K = 16 frequencies per axis (256 channels,
+ * channel 16u + v) or K = 8 (64 channels, channel 8u + v, u, v < 8: dropping the rest is the chroma down-sampling; on the way back the missing
+ * frequencies are zero).  `qtab` is fp32 [B][3][256]: per image the luminance table and twice the chrominance table, each edge-padded to 16x16
+ * (JPEG.padded_Q_table), row-major (u, v); a K = 8 plane reads entries 16u + v.  Y is shifted by 128, Cb and Cr by 0.  One launch per call; one
+ * workgroup owns 16 image rows x 16 blocks of one plane; 16-byte accesses on both sides where the addresses allow (pointers 16-byte aligned, w
+ * a multiple of 4; any w works).  Images must be 16-byte aligned.  No atomics: two calls give the same bits.  B * planes and h up to 65535
+ * (ESR_E_UNSUPPORTED beyond).
+ *
+ * esr_jpeg16_compress — JPEG.forward, compress=True, chroma_mode (JPEG.py:131-154) on a three-plane image; H, W multiples of 16.  mode:
+ *   ESR_JPEG16_ALL         downsample_or_quantize=False: coef [B][768][h][w] = Y, Cb, Cr with K = 16 each, nothing rounded
+ *   ESR_JPEG16_DOWNSAMPLE  'downsample_only': coef [B][384][h][w] = Y (K = 16) | Cb (K = 8) | Cr (K = 8), nothing rounded
+ *   ESR_JPEG16_QUANTIZE    True: the same 384 channels with Cb and Cr rounded half to even (Y is never rounded, JPEG.py:144-148) */
+#define ESR_JPEG16_ALL 0
+#define ESR_JPEG16_DOWNSAMPLE 1
+#define ESR_JPEG16_QUANTIZE 2
+int esr_jpeg16_compress(const float* x, int B, int H, int W, const float* qtab, int mode, float* coef, esr_stream_t stream);
+/* esr_jpeg16_extract — JPEG.forward, compress=False, chroma_mode (JPEG.py:165-201).  `form` is the reference's dispatch on the channel count:
+ *   128 = Cb, Cr (K = 8) -> img [B][2][H][W];  512 = Cb, Cr (K = 16) -> [B][2][H][W];  384 = Y (K = 16) | Cb | Cr (K = 8) -> [B][3][H][W], +128 on Y.
+ *   The `form` channels are read at channel coef_c0 of a tensor of coef_C channels (a slice of a wider tensor needs no copy).  With y (form 128
+ *   only): the chroma generator's tail (architecture.py:206-212) in front, c = coef + (sigmoid(y) - 0.5) with y the last conv's fp32
+ *   [B][128][h][w] output; coef_out (optional, with y) receives c as [B][128][h][w]. */
+int esr_jpeg16_extract(const float* coef, int coef_C, int coef_c0, const float* y, int form, int B, int h, int w, const float* qtab,
+                       float* coef_out, float* img, esr_stream_t stream);
+/* Adjoint of esr_jpeg16_extract: d_coef [B][form][h][w] = qtab * DCT16(d_img) restricted to the kept frequencies and, with y (form 128),
+ *   d_y = d_coef * s (1 - s), s = sigmoid(y).  Either output may be NULL (not both); d_y needs y. */
+int esr_jpeg16_extract_grad(const float* d_img, const float* y, int form, int B, int h, int w, const float* qtab, float* d_coef, float* d_y,
+                            esr_stream_t stream);
+/* Adjoint of esr_jpeg16_compress: d_x [B][3][H][W] = iDCT16(d_coef / qtab) over the channels of `mode`.  ESR_JPEG16_QUANTIZE: only the Y plane
+ *   is written (the rounded Cb and Cr planes have zero gradient, as torch.round's: the caller passes d_x zero-filled). */
+int esr_jpeg16_compress_grad(const float* d_coef, int mode, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream);
+
 int esr_version(void);
 
 #ifdef __cplusplus

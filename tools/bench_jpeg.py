@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""What the JPEG consistency layer and the DnCNN generator cost (csrc/esr_jpeg.hip, esr_hip/jpeg.py, esr_hip/dncnn.py): prints JSON lines.
+"""What the JPEG consistency layer and the DnCNN generator cost (csrc/esr_jpeg.hip, csrc/esr_jpeg16.hip, esr_hip/jpeg.py, esr_hip/dncnn.py):
+prints JSON lines.
 
     python tools/bench_jpeg.py [--steps 20] [--warmup 5]
 
@@ -7,6 +8,10 @@
     compress, extract and extract-grad kernels, each against the reference's formulation in torch ops on the same GPU (a broadcast against
     the cosine grid, a sum and a permute per axis, JPEG.py:108-120 — restated below), with the bytes a call must move (read the input once,
     write the output once: 8 bytes per element) over its time as a fraction of the 8 TB/s HBM peak (about 6.3 TB/s is achievable by a copy);
+(i') the colour model's 16-point kernels at 16 x 3 x 256 x 256 and 1 x 3 x 2048 x 2048 next to them: the quantising and the all-coefficient
+    compressor, the 384-channel extractor, the 128-channel extractor with the chroma generator's tail, and extractor forward + gradient, each
+    against the defining einsum expression of esr_hip/jpeg.py in torch ops on the same GPU; bytes moved = the planes read plus the planes
+    written (a K = 8 chroma plane is a quarter of a K = 16 one on the coefficient side);
 (ii) the DnCNN(n_channels=320, depth=10, latent 64, 'all_layers') generator at 16 x 32 x 32 blocks: forward, and forward + input gradient,
     on the library's kernels ('split') against the same module on stock torch (MIOpen) on the same GPU.
 Each pair is measured twice, interleaved; the second pass is free of one-off set-up."""
@@ -103,6 +108,32 @@ def main():
                                             ('extract fwd + grad', extract_grad_kernel, extract_grad_torch)):
                 tk, tt = timed(kernel, a.steps, a.warmup), timed(torch_ops, a.steps, a.warmup)
                 moved = nbytes * (2 if 'grad' in name else 1)
+                print(json.dumps({'pass': rep, 'op': name, 'shape': list(shape), 'kernel_us': round(tk * 1e6, 1), 'torch_ops_us': round(tt * 1e6, 1),
+                                  'torch_over_kernel': round(tt / tk, 2), 'kernel_GBps': round(moved / tk / 1e9, 1),
+                                  'fraction_of_hbm_peak': round(moved / tk / HBM_PEAK, 3), 'max_abs_diff_compress_extract': check}), flush=True)
+        for shape in ((16, 3, 256, 256), (1, 3, 2048, 2048)):
+            B, _, H, W = shape
+            n = B * H * W                                                                   # pixels of one plane
+            x = torch.floor(torch.rand(shape, generator=gen) * 256).to(dev)
+            q = torch.randint(1, 100, (B, 3, 256), generator=gen).float().to(dev)
+            cq, ca = J.compress16(x, q, True), J.compress16(x, q, False)
+            y = (torch.rand(B, 128, H // 16, W // 16, generator=gen) * 6 - 3).to(dev)
+            d_img = torch.rand(shape, generator=gen).to(dev)
+            check = (float((J._compress16_cpu(x, q, 0) - ca).abs().max()), float((J._extract16_cpu(cq, q, None)[1] - J.extract16(cq, q)[1]).abs().max()))
+
+            def grad_of(fn):
+                def run():
+                    c = cq.detach().requires_grad_(True)
+                    fn(c, q, None)[1].backward(d_img)
+                return run
+            rows = (('compress16 (quantising: Y | Cb, Cr low)', lambda: J.compress16(x, q, True), lambda: J._compress16_cpu(x, q, 2), 4 * (3 * n + 1.5 * n)),
+                    ('compress16 (all 3 x 256)', lambda: J.compress16(x, q, False), lambda: J._compress16_cpu(x, q, 0), 4 * (3 * n + 3 * n)),
+                    ('extract16 (384 -> YCbCr)', lambda: J.extract16(cq, q), lambda: J._extract16_cpu(cq, q, None), 4 * (1.5 * n + 3 * n)),
+                    ('extract16 (128 + generator tail -> Cb, Cr)', lambda: J.extract16(cq, q, y), lambda: J._extract16_cpu(cq, q, y),
+                     4 * (0.5 * n + 0.5 * n + 0.5 * n + 2 * n)),
+                    ('extract16 (384) fwd + grad', grad_of(J.extract16), grad_of(J._extract16_cpu), 2 * 4 * (1.5 * n + 3 * n)))
+            for name, kernel, torch_ops, moved in rows:
+                tk, tt = timed(kernel, a.steps, a.warmup), timed(torch_ops, a.steps, a.warmup)
                 print(json.dumps({'pass': rep, 'op': name, 'shape': list(shape), 'kernel_us': round(tk * 1e6, 1), 'torch_ops_us': round(tt * 1e6, 1),
                                   'torch_over_kernel': round(tt / tk, 2), 'kernel_GBps': round(moved / tk / 1e9, 1),
                                   'fraction_of_hbm_peak': round(moved / tk / HBM_PEAK, 3), 'max_abs_diff_compress_extract': check}), flush=True)

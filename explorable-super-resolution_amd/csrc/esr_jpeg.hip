@@ -12,7 +12,7 @@
 // give the same bits.
 #include <math.h>
 
-#include "esr_common.h"
+#include "esr_dct.h"
 
 namespace {
 
@@ -36,8 +36,6 @@ const DctTab& dct_tab() {
     }();
     return tab;
 }
-
-__device__ __forceinline__ float sigmoidf(float y) { return 1.f / (1.f + expf(-y)); }
 
 // image -> coefficients:  c = DCT(img - shift) (/ or *) qtab, optionally rounded half to even
 //   coef (optional): fp32 planes;  act (optional): the same values in the conv kernels' activation layout, groups [0, 8) of the view
@@ -95,24 +93,7 @@ __global__ __launch_bounds__(256) void dct_fwd_kernel(const float* __restrict__ 
             const int c = k / (TB / 4), jq = k % (TB / 4), jj = j0 + 4 * jq;
             if (jj >= w) continue;
             const long long o = (((long long)b * 64 + c) * h + i) * w + jj;
-            const float4 v = *(const float4*)(XO + c * OP + 4 * jq);
-            if (vec) {
-                if (coef) *(float4*)(coef + o) = v;
-                if (dy) {
-                    const float4 yy = *(const float4*)(y + o);
-                    const float s0 = sigmoidf(yy.x), s1 = sigmoidf(yy.y), s2 = sigmoidf(yy.z), s3 = sigmoidf(yy.w);
-                    *(float4*)(dy + o) = make_float4(v.x * (s0 * (1.f - s0)), v.y * (s1 * (1.f - s1)), v.z * (s2 * (1.f - s2)), v.w * (s3 * (1.f - s3)));
-                }
-            } else {
-                const float e[4] = {v.x, v.y, v.z, v.w};
-                for (int n = 0; n < 4 && jj + n < w; ++n) {
-                    if (coef) coef[o + n] = e[n];
-                    if (dy) {
-                        const float s = sigmoidf(y[o + n]);
-                        dy[o + n] = e[n] * (s * (1.f - s));
-                    }
-                }
-            }
+            coef_store4(*(const float4*)(XO + c * OP + 4 * jq), coef, y, dy, o, o, vec, w - jj);
         }
     }
     if (act_hi && j < nb) {  // thread (u, j): the eight v of one pixel vector of group u
@@ -133,29 +114,12 @@ __global__ __launch_bounds__(256) void dct_inv_kernel(const float* __restrict__ 
     const int nb = min(TB, w - j0);
     for (int k = tid; k < 64 * (TB / 4); k += 256) {
         const int c = k / (TB / 4), jq = k % (TB / 4), jj = j0 + 4 * jq;
-        float e[4] = {0.f, 0.f, 0.f, 0.f};
-        if (jj < w) {
-            const long long o = (((long long)b * 64 + c) * h + i) * w + jj;
-            if (vec) {
-                const float4 v = *(const float4*)(coef + o);
-                e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
-                if (y) {
-                    const float4 yy = *(const float4*)(y + o);
-                    e[0] += sigmoidf(yy.x) - 0.5f; e[1] += sigmoidf(yy.y) - 0.5f; e[2] += sigmoidf(yy.z) - 0.5f; e[3] += sigmoidf(yy.w) - 0.5f;
-                }
-                if (coef_out) *(float4*)(coef_out + o) = make_float4(e[0], e[1], e[2], e[3]);
-            } else {
-                for (int n = 0; n < 4 && jj + n < w; ++n) {
-                    e[n] = coef[o + n];
-                    if (y) e[n] += sigmoidf(y[o + n]) - 0.5f;
-                    if (coef_out) coef_out[o + n] = e[n];
-                }
-            }
+        if (jj >= w) {   // beyond the row: blocks that are transformed and never stored
+            *(float4*)(XO + c * OP + 4 * jq) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
         }
-        const float q = qtab[b * 64 + c];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) e[n] = divide ? e[n] / q : e[n] * q;
-        *(float4*)(XO + c * OP + 4 * jq) = make_float4(e[0], e[1], e[2], e[3]);
+        const long long o = (((long long)b * 64 + c) * h + i) * w + jj;
+        *(float4*)(XO + c * OP + 4 * jq) = coef_load4(coef, y, coef_out, o, o, vec, w - jj, qtab + b * 64 + c, divide);
     }
     __syncthreads();
     const int hi5 = tid >> 5, j = tid & 31;
@@ -195,9 +159,6 @@ __global__ __launch_bounds__(256) void dct_inv_kernel(const float* __restrict__ 
     }
 }
 
-inline bool grid_ok(int B, int h, int w) { return B > 0 && h > 0 && w > 0; }
-inline bool grid_fits(int B, int h) { return B <= 65535 && h <= 65535; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline dim3 grid_of(int B, int h, int w) { return dim3((unsigned)((w + TB - 1) / TB), (unsigned)h, (unsigned)B); }
 
 }  // namespace
@@ -208,10 +169,10 @@ extern "C" int esr_jpeg_compress(const float* x, int B, int H, int W, const floa
     const int h = H / 8, w = W / 8;
     const bool act = act_out && act_out->hi;
     if (act && (act_out->ncg < 8 || act_out->H != h || act_out->W != w || (act_out->fmt != ESR_FMT_BF16 && act_out->fmt != ESR_FMT_F16))) return ESR_E_ARG;
-    if (!grid_fits(B, h)) return ESR_E_UNSUPPORTED;
+    if (!grid_fits(B, 1, h)) return ESR_E_UNSUPPORTED;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct_fwd_kernel, grid_of(B, h, w), dim3(256), 0, (hipStream_t)stream, x, h, w, qtab, dct_tab(), 128.f, 1, round ? 1 : 0,
-                       (w % 4 == 0 && al16(coef)) ? 1 : 0, coef, (const float*)nullptr, (float*)nullptr, act ? (uint4*)act_out->hi : nullptr,
+                       coef_vec(w, coef), coef, (const float*)nullptr, (float*)nullptr, act ? (uint4*)act_out->hi : nullptr,
                        act ? (uint4*)act_out->lo : nullptr, act ? (long long)act_out->batch_stride : 0ll, act ? (long long)act_out->cg_stride : 0ll,
                        act ? act_out->fmt : 0);
     ESR_CHECK_LAUNCH();
@@ -220,33 +181,33 @@ extern "C" int esr_jpeg_compress(const float* x, int B, int H, int W, const floa
 
 extern "C" int esr_jpeg_extract(const float* coef, const float* y, int B, int h, int w, const float* qtab, float* coef_out, float* img,
                                 esr_stream_t stream) {
-    if (!coef || !qtab || !img || !grid_ok(B, h, w) || !al16(img)) return ESR_E_ARG;
-    if (!grid_fits(B, h)) return ESR_E_UNSUPPORTED;
+    if (!coef || !qtab || !img || !dims_positive(B, h, w) || !al16(img)) return ESR_E_ARG;
+    if (!grid_fits(B, 1, h)) return ESR_E_UNSUPPORTED;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct_inv_kernel, grid_of(B, h, w), dim3(256), 0, (hipStream_t)stream, coef, y, h, w, qtab, dct_tab(), 128.f, 0,
-                       (w % 4 == 0 && al16(coef) && al16(y) && al16(coef_out)) ? 1 : 0, coef_out, img);
+                       coef_vec(w, coef, y, coef_out), coef_out, img);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
 
 extern "C" int esr_jpeg_extract_grad(const float* d_img, const float* y, int B, int h, int w, const float* qtab, float* d_coef, float* d_y,
                                      esr_stream_t stream) {
-    if (!d_img || !qtab || (!d_coef && !d_y) || (d_y && !y) || !grid_ok(B, h, w) || !al16(d_img)) return ESR_E_ARG;
-    if (!grid_fits(B, h)) return ESR_E_UNSUPPORTED;
+    if (!d_img || !qtab || (!d_coef && !d_y) || (d_y && !y) || !dims_positive(B, h, w) || !al16(d_img)) return ESR_E_ARG;
+    if (!grid_fits(B, 1, h)) return ESR_E_UNSUPPORTED;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct_fwd_kernel, grid_of(B, h, w), dim3(256), 0, (hipStream_t)stream, d_img, h, w, qtab, dct_tab(), 0.f, 0, 0,
-                       (w % 4 == 0 && al16(d_coef) && al16(y) && al16(d_y)) ? 1 : 0, d_coef, d_y ? y : (const float*)nullptr, d_y, (uint4*)nullptr,
+                       coef_vec(w, d_coef, y, d_y), d_coef, d_y ? y : (const float*)nullptr, d_y, (uint4*)nullptr,
                        (uint4*)nullptr, 0ll, 0ll, 0);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
 
 extern "C" int esr_jpeg_compress_grad(const float* d_coef, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream) {
-    if (!d_coef || !qtab || !d_x || !grid_ok(B, h, w) || !al16(d_x)) return ESR_E_ARG;
-    if (!grid_fits(B, h)) return ESR_E_UNSUPPORTED;
+    if (!d_coef || !qtab || !d_x || !dims_positive(B, h, w) || !al16(d_x)) return ESR_E_ARG;
+    if (!grid_fits(B, 1, h)) return ESR_E_UNSUPPORTED;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct_inv_kernel, grid_of(B, h, w), dim3(256), 0, (hipStream_t)stream, d_coef, (const float*)nullptr, h, w, qtab, dct_tab(),
-                       0.f, 1, (w % 4 == 0 && al16(d_coef)) ? 1 : 0, (float*)nullptr, d_x);
+                       0.f, 1, coef_vec(w, d_coef), (float*)nullptr, d_x);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }

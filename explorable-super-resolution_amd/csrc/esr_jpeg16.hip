@@ -16,7 +16,7 @@
 // calls give the same bits.
 #include <math.h>
 
-#include "esr_common.h"
+#include "esr_dct.h"
 
 namespace {
 
@@ -52,8 +52,6 @@ struct Planes {
     int y_off[3];     // first channel in y / dy / coef_out, tensors of y_C channels
     int img_C, c_C, y_C;
 };
-
-__device__ __forceinline__ float sigmoidf(float y) { return 1.f / (1.f + expf(-y)); }
 
 // out[k] = sum_n c(k, n) x[n], k < K, by the even/odd split
 template <int K>
@@ -172,24 +170,7 @@ __global__ __launch_bounds__(256) void dct16_fwd_kernel(const float* __restrict_
         if (jj >= w) continue;
         const long long o = (((long long)b * pl.c_C + pl.c_off[p] + c) * h + i) * w + jj;
         const long long oy = (((long long)b * pl.y_C + pl.y_off[p] + c) * h + i) * w + jj;
-        const float4 v = *(const float4*)(XO + c * OP + 4 * jq);
-        if (vec) {
-            if (coef) *(float4*)(coef + o) = v;
-            if (dy) {
-                const float4 yy = *(const float4*)(y + oy);
-                const float s0 = sigmoidf(yy.x), s1 = sigmoidf(yy.y), s2 = sigmoidf(yy.z), s3 = sigmoidf(yy.w);
-                *(float4*)(dy + oy) = make_float4(v.x * (s0 * (1.f - s0)), v.y * (s1 * (1.f - s1)), v.z * (s2 * (1.f - s2)), v.w * (s3 * (1.f - s3)));
-            }
-        } else {
-            const float e[4] = {v.x, v.y, v.z, v.w};
-            for (int n = 0; n < 4 && jj + n < w; ++n) {
-                if (coef) coef[o + n] = e[n];
-                if (dy) {
-                    const float s = sigmoidf(y[oy + n]);
-                    dy[oy + n] = e[n] * (s * (1.f - s));
-                }
-            }
-        }
+        coef_store4(*(const float4*)(XO + c * OP + 4 * jq), coef, y, dy, o, oy, vec, w - jj);
     }
 }
 
@@ -206,30 +187,13 @@ __global__ __launch_bounds__(256) void dct16_inv_kernel(const float* __restrict_
     const float* qt = qtab + ((long long)b * 3 + pl.tab[p]) * 256;
     for (int k = tid; k < K * K * (TB / 4); k += 256) {
         const int c = k / (TB / 4), jq = k % (TB / 4), jj = j0 + 4 * jq;
-        float e[4] = {0.f, 0.f, 0.f, 0.f};
-        if (jj < w) {
-            const long long o = (((long long)b * pl.c_C + pl.c_off[p] + c) * h + i) * w + jj;
-            const long long oy = (((long long)b * pl.y_C + pl.y_off[p] + c) * h + i) * w + jj;
-            if (vec) {
-                const float4 v = *(const float4*)(coef + o);
-                e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
-                if (y) {
-                    const float4 yy = *(const float4*)(y + oy);
-                    e[0] += sigmoidf(yy.x) - 0.5f; e[1] += sigmoidf(yy.y) - 0.5f; e[2] += sigmoidf(yy.z) - 0.5f; e[3] += sigmoidf(yy.w) - 0.5f;
-                }
-                if (coef_out) *(float4*)(coef_out + oy) = make_float4(e[0], e[1], e[2], e[3]);
-            } else {
-                for (int n = 0; n < 4 && jj + n < w; ++n) {
-                    e[n] = coef[o + n];
-                    if (y) e[n] += sigmoidf(y[oy + n]) - 0.5f;
-                    if (coef_out) coef_out[oy + n] = e[n];
-                }
-            }
+        if (jj >= w) {   // beyond the row: blocks that are transformed and never stored
+            *(float4*)(XO + c * OP + 4 * jq) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
         }
-        const float q = qt[16 * (c / K) + c % K];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) e[n] = divide ? e[n] / q : e[n] * q;
-        *(float4*)(XO + c * OP + 4 * jq) = make_float4(e[0], e[1], e[2], e[3]);
+        const long long o = (((long long)b * pl.c_C + pl.c_off[p] + c) * h + i) * w + jj;
+        const long long oy = (((long long)b * pl.y_C + pl.y_off[p] + c) * h + i) * w + jj;
+        *(float4*)(XO + c * OP + 4 * jq) = coef_load4(coef, y, coef_out, o, oy, vec, w - jj, qt + 16 * (c / K) + c % K, divide);
     }
     __syncthreads();
     if (K == 16) inv_tile<16>(tab, XO, T, pl.shift[p]);
@@ -242,9 +206,6 @@ __global__ __launch_bounds__(256) void dct16_inv_kernel(const float* __restrict_
     }
 }
 
-inline bool grid_ok(int B, int h, int w) { return B > 0 && h > 0 && w > 0; }
-inline bool grid_fits(int B, int n, int h) { return (long long)B * n <= 65535 && h <= 65535; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline dim3 grid_of(int B, int n, int h, int w) { return dim3((unsigned)((w + TB - 1) / TB), (unsigned)h, (unsigned)(B * n)); }
 
 // the compressor's three modes (ESR_JPEG16_*): planes Y, Cb, Cr of a three-plane image
@@ -293,7 +254,7 @@ extern "C" int esr_jpeg16_compress(const float* x, int B, int H, int W, const fl
     const Planes pl = compress_planes(mode);
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct16_fwd_kernel, grid_of(B, 3, h, w), dim3(256), 0, (hipStream_t)stream, x, h, w, qtab, dct16_tab(), pl, 1,
-                       (w % 4 == 0 && al16(coef)) ? 1 : 0, coef, (const float*)nullptr, (float*)nullptr);
+                       coef_vec(w, coef), coef, (const float*)nullptr, (float*)nullptr);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
@@ -301,7 +262,7 @@ extern "C" int esr_jpeg16_compress(const float* x, int B, int H, int W, const fl
 extern "C" int esr_jpeg16_extract(const float* coef, int coef_C, int coef_c0, const float* y, int form, int B, int h, int w, const float* qtab,
                                   float* coef_out, float* img, esr_stream_t stream) {
     Planes pl;
-    if (!coef || !qtab || !img || !grid_ok(B, h, w) || !al16(img) || !extract_planes(form, &pl) || coef_c0 < 0 || coef_C < coef_c0 + form ||
+    if (!coef || !qtab || !img || !dims_positive(B, h, w) || !al16(img) || !extract_planes(form, &pl) || coef_c0 < 0 || coef_C < coef_c0 + form ||
         ((y || coef_out) && form != 128) || (coef_out && !y))
         return ESR_E_ARG;
     if (!grid_fits(B, pl.n, h)) return ESR_E_UNSUPPORTED;
@@ -309,7 +270,7 @@ extern "C" int esr_jpeg16_extract(const float* coef, int coef_C, int coef_c0, co
     for (int k = 0; k < pl.n; ++k) pl.c_off[k] += coef_c0;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct16_inv_kernel, grid_of(B, pl.n, h, w), dim3(256), 0, (hipStream_t)stream, coef, y, h, w, qtab, dct16_tab(), pl, 0,
-                       (w % 4 == 0 && al16(coef) && al16(y) && al16(coef_out)) ? 1 : 0, coef_out, img);
+                       coef_vec(w, coef, y, coef_out), coef_out, img);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
@@ -317,20 +278,20 @@ extern "C" int esr_jpeg16_extract(const float* coef, int coef_C, int coef_c0, co
 extern "C" int esr_jpeg16_extract_grad(const float* d_img, const float* y, int form, int B, int h, int w, const float* qtab, float* d_coef,
                                        float* d_y, esr_stream_t stream) {
     Planes pl;
-    if (!d_img || !qtab || (!d_coef && !d_y) || (d_y && !y) || !grid_ok(B, h, w) || !al16(d_img) || !extract_planes(form, &pl) ||
+    if (!d_img || !qtab || (!d_coef && !d_y) || (d_y && !y) || !dims_positive(B, h, w) || !al16(d_img) || !extract_planes(form, &pl) ||
         (d_y && form != 128))
         return ESR_E_ARG;
     if (!grid_fits(B, pl.n, h)) return ESR_E_UNSUPPORTED;
     for (int k = 0; k < pl.n; ++k) pl.shift[k] = 0.f;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct16_fwd_kernel, grid_of(B, pl.n, h, w), dim3(256), 0, (hipStream_t)stream, d_img, h, w, qtab, dct16_tab(), pl, 0,
-                       (w % 4 == 0 && al16(d_coef) && al16(y) && al16(d_y)) ? 1 : 0, d_coef, d_y ? y : (const float*)nullptr, d_y);
+                       coef_vec(w, d_coef, y, d_y), d_coef, d_y ? y : (const float*)nullptr, d_y);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
 
 extern "C" int esr_jpeg16_compress_grad(const float* d_coef, int mode, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream) {
-    if (!d_coef || !qtab || !d_x || !grid_ok(B, h, w) || !al16(d_x) ||
+    if (!d_coef || !qtab || !d_x || !dims_positive(B, h, w) || !al16(d_x) ||
         (mode != ESR_JPEG16_ALL && mode != ESR_JPEG16_DOWNSAMPLE && mode != ESR_JPEG16_QUANTIZE))
         return ESR_E_ARG;
     if (!grid_fits(B, 3, h)) return ESR_E_UNSUPPORTED;
@@ -339,7 +300,7 @@ extern "C" int esr_jpeg16_compress_grad(const float* d_coef, int mode, int B, in
     for (int k = 0; k < 3; ++k) pl.shift[k] = 0.f;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(dct16_inv_kernel, grid_of(B, pl.n, h, w), dim3(256), 0, (hipStream_t)stream, d_coef, (const float*)nullptr, h, w, qtab,
-                       dct16_tab(), pl, 1, (w % 4 == 0 && al16(d_coef)) ? 1 : 0, (float*)nullptr, d_x);
+                       dct16_tab(), pl, 1, coef_vec(w, d_coef), (float*)nullptr, d_x);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }

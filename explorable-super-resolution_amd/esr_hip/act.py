@@ -9,6 +9,7 @@ import threading
 import torch
 
 from . import _lib
+from ._image import detach_f32
 from ._lib import ActView, EsrError, check
 
 
@@ -963,3 +964,41 @@ def conv3x3_wgrad_nchw(dy, x, wshape, split=True):
     pack_nchw(dy, gy.view(), 0, Cout)
     pack_nchw(x, gx.view(), 0, Cin)
     return conv3x3_wgrad(gy.view(), gx.view(), None, 0, wshape, B, H, W, 1.0, 1, dy.device)
+
+
+# ------------------------------------------------------------------------------------------------ frozen conv engines (vgg.py, dncnn.py)
+# An engine has forward(x, save) -> (output, saved | None) and backward(saved, d_output) -> d_x; its weights are frozen.
+def launch_by_launch(name):
+    """guard of an engine's passes, which issue their launches directly"""
+    if _rec() is not None:
+        raise EsrError('the %s passes are issued launch by launch; they cannot be collected into a launch list' % name)
+
+
+def gpu_input(x, what):
+    """what an engine's kernels read: x on the GPU, detached, float32, contiguous"""
+    require_gpu(x, what)
+    return detach_f32(x)
+
+
+class _InputGradFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, eng, name, x):
+        out, saved = eng.forward(x, save=True)
+        ctx.eng, ctx.name, ctx.saved = eng, name, saved
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        saved, ctx.saved = ctx.saved, None
+        if saved is None:
+            raise EsrError('%s backward: the saved activations were already released (backward called twice?)' % ctx.name)
+        return None, None, ctx.eng.backward(saved, d_out)
+
+
+def engine_forward(eng, name, x):
+    """The engine's output for x; differentiable w.r.t. x when x requires grad and grad mode is on (input gradient only)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _InputGradFn.apply(eng, name, x)
+    with torch.no_grad():
+        return eng.forward(x, save=False)[0]

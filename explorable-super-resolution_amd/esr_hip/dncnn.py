@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from . import act as A
 from .act import new_at, new_zeroed, view_of
+from ._image import detach_f32
 from ._lib import EsrError, check
 
 def check_shapes(n_channels, depth, in_nc, out_nc, lat_first, lat_rest):
@@ -145,11 +146,8 @@ class DnCNNEngine:
     def forward(self, x, save):
         """x: fp32 [B, L + 64, h, w] = [Z | quantised coefficients] on the GPU -> (y fp32 [B, 64, h, w], the last conv's output BEFORE the
         sigmoid; saved) where saved is what backward() needs (save=True: every layer's input buffer) or None."""
-        if A._rec() is not None:
-            raise EsrError('the DnCNN passes are issued launch by launch; they cannot be collected into a launch list')
-        A.require_gpu(x, 'DnCNN input')
-        x = x.detach()
-        x = (x if x.dtype == torch.float32 else x.float()).contiguous()
+        A.launch_by_launch('DnCNN')
+        x = A.gpu_input(x, 'DnCNN input')
         B, Cin, h, w = x.shape
         if Cin != self.layers[0].cin:
             raise EsrError('DnCNN input has %d channels, the first conv takes %d (latent %d + coefficients)' % (Cin, self.layers[0].cin, self.L))
@@ -192,11 +190,10 @@ class DnCNNEngine:
     @A.one_stream
     def backward(self, saved, d_y):
         """Gradient fp32 [B, L + 64, h, w] of sum(y * d_y) with respect to the input [Z | coefficients] of the forward that produced `saved`."""
-        if A._rec() is not None:
-            raise EsrError('the DnCNN passes are issued launch by launch; they cannot be collected into a launch list')
+        A.launch_by_launch('DnCNN')
         (B, Cin, h, w), ins = saved
         P, dev, s = self.planes, d_y.device, A.stream_ptr()
-        d_y = d_y.detach().float().contiguous()
+        d_y = detach_f32(d_y)
         g = new_at(P, B, (d_y.shape[1] + 7) // 8, h, w, dev)
         check(_lib.lib.esr_pack_nchw_norm(d_y.data_ptr(), B, d_y.shape[1], h, w, None, None, C.byref(view_of(g)), s), 'esr_pack_nchw_norm')
         gv = view_of(g)
@@ -222,26 +219,7 @@ class DnCNNEngine:
         return d_in
 
 
-class _DnCNNFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, eng, x):
-        y, saved = eng.forward(x, save=True)
-        ctx.eng, ctx.saved = eng, saved
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_y):
-        saved, ctx.saved = ctx.saved, None
-        if saved is None:
-            raise EsrError('DnCNN backward: the saved activations were already released (backward called twice?)')
-        return None, ctx.eng.backward(saved, d_y)
-
-
 def dncnn_forward(eng, x):
     """The last conv's pre-sigmoid output for the input [Z | coefficients]; differentiable w.r.t. x when x requires grad and grad mode is on
     (input gradient only)."""
-    if torch.is_grad_enabled() and x.requires_grad:
-        return _DnCNNFn.apply(eng, x)
-    with torch.no_grad():
-        return eng.forward(x, save=False)[0]
+    return A.engine_forward(eng, 'DnCNN', x)

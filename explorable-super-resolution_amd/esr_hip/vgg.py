@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from . import act as A
 from .act import new_at, new_zeroed, view_of
+from ._image import detach_f32
 from ._lib import EsrError, check
 
 # torchvision.models.vgg cfgs ('M' = MaxPool2d(2, 2)); features = [Conv2d(cin, v, 3, padding=1), ReLU(inplace=True)] per number
@@ -154,11 +155,8 @@ class VGGEngine:
     def forward(self, x, save):
         """x: fp32 [B, C, H, W] on the GPU -> (features fp32 [B, C', H', W'], saved) where saved is what backward() needs (save=True: the
         output of every conv and the input of the last op) or None."""
-        if A._rec() is not None:
-            raise EsrError('the VGG passes are issued launch by launch; they cannot be collected into a launch list')
-        A.require_gpu(x, 'VGG input')
-        x = x.detach()
-        x = (x if x.dtype == torch.float32 else x.float()).contiguous()
+        A.launch_by_launch('VGG')
+        x = A.gpu_input(x, 'VGG input')
         B, Cin, H, W = x.shape
         if Cin != self.ops[0].cin:
             raise EsrError('VGG input has %d channels, the first conv takes %d' % (Cin, self.ops[0].cin))
@@ -192,11 +190,10 @@ class VGGEngine:
     @A.one_stream
     def backward(self, saved, d_feat):
         """Input gradient fp32 [B, C, H, W] of sum(features * d_feat) through the forward that produced `saved`."""
-        if A._rec() is not None:
-            raise EsrError('the VGG passes are issued launch by launch; they cannot be collected into a launch list')
+        A.launch_by_launch('VGG')
         (B, Cin, H, W), outs = saved
         P, dev, s = self.planes, d_feat.device, A.stream_ptr()
-        d_feat = d_feat.detach().float().contiguous()
+        d_feat = detach_f32(d_feat)
         last = outs[-1]
         g = new_at(P, B, last.shape[2], last.shape[3] - 2, last.shape[4] - 2, dev)
         nc = d_feat.shape[1]
@@ -232,25 +229,6 @@ class VGGEngine:
         return dxin
 
 
-class _VGGFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, eng, x):
-        feat, saved = eng.forward(x, save=True)
-        ctx.eng, ctx.saved = eng, saved
-        return feat
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_feat):
-        saved, ctx.saved = ctx.saved, None
-        if saved is None:
-            raise EsrError('VGG backward: the saved activations were already released (backward called twice?)')
-        return None, ctx.eng.backward(saved, d_feat)
-
-
 def vgg_forward(eng, x):
     """Features of x through the engine; differentiable w.r.t. x when x requires grad and grad mode is on (input gradient only)."""
-    if torch.is_grad_enabled() and x.requires_grad:
-        return _VGGFn.apply(eng, x)
-    with torch.no_grad():
-        return eng.forward(x, save=False)[0]
+    return A.engine_forward(eng, 'VGG', x)

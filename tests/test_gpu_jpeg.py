@@ -6,7 +6,11 @@ on the same input, computed here from tests/golden/jpeg_dncnn.npz (the factor 4 
 cosine table in place of torch.cos).  For quantities the fixture does not hold (the adjoints, the 16 x 1 x 256 x 256 input) the reference's
 RELATIVE distance on the fixture input of the same kind is used: the transforms are linear and the inputs are drawn alike, so the error scales
 with the magnitude of the result.  The quantised compressor is compared under the tie rule of tests/test_host_jpeg.py.  The CPU fallbacks
-are patched to raise, so a silent fallback cannot pass."""
+are patched to raise, so a silent fallback cannot pass.
+
+Shapes beyond the fixture's (B, h x w blocks of 8 x 8 pixels, rows of the fixture's tables): 'one' a single block; 'ragged' w = 35 — not a
+multiple of 4, so the scalar tail of the 16-byte path, and one workgroup tile of 32 blocks plus a remainder of 3; 'vector' w = 36, the 16-byte
+path with a partial second tile of 4."""
 import copy
 import ctypes as C
 
@@ -39,10 +43,28 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _noise(B, h, w, seed):
+    return torch.floor(seeded_uniform((B, 1, 8 * h, 8 * w), seed) * 256)
+
+
+# name -> (fixture input of the same kind, table rows, input)
+SHAPES = {'one': ('smooth', [3], lambda: G.smooth_pattern(1, 8, 8, 4305)),
+          'ragged': ('noise', [1, 3, 5], lambda: _noise(3, 2, 35, 4310)),
+          'vector': ('noise', [2, 4], lambda: _noise(2, 2, 36, 4320))}
+_cases = {}
+
+
 def _case(name):
-    """(x, tables, reference cn / cq / img_q / img_n) of a module-level case; 'user': 16 x 1 x 256 x 256 noise, bounds of 'noise'"""
+    """(x, tables, reference cn / cq / img_q / img_n or None, the reference's distances) — computed once per name, left unchanged"""
+    if name not in _cases:
+        _cases[name] = _make_case(name)
+    return _cases[name]
+
+
+def _make_case(name):
+    """a module-level case of the fixture; 'user': 16 x 1 x 256 x 256 noise, bounds of 'noise'; a SHAPES entry: bounds of its kind"""
     g = golden()
-    kind = 'noise' if name == 'user' else name
+    kind = 'noise' if name == 'user' else SHAPES[name][0] if name in SHAPES else name
     ref = {k: torch.from_numpy(np.asarray(g['a/%s/%s' % (kind, k)])).float() for k in ('x', 'cq', 'cn', 'img_q', 'img_n')}
     tables = torch.from_numpy(g['a/tables'])
     # the reference's own distances from float64, absolute and relative to the largest value
@@ -56,10 +78,12 @@ def _case(name):
         x = torch.floor(seeded_uniform((16, 1, 256, 256), 4100) * 256).clamp(0, 255)
         tables = tables.repeat(3, 1)[:16]
         return x, tables, None, d
+    if name in SHAPES:
+        return SHAPES[name][2](), tables[SHAPES[name][1]].contiguous(), None, d
     return ref['x'], tables, ref, d
 
 
-@pytest.mark.parametrize('name', ['noise', 'smooth', 'user'])
+@pytest.mark.parametrize('name', ['noise', 'smooth', 'user', 'one', 'ragged', 'vector'])
 def test_kernels_against_float64(name):
     from esr_hip import jpeg as J
     x, tables, ref, d = _case(name)
@@ -88,7 +112,7 @@ def test_kernels_against_float64(name):
             assert err <= 4 * d['extract_' + key]
 
 
-@pytest.mark.parametrize('name', ['smooth', 'user'])
+@pytest.mark.parametrize('name', ['smooth', 'user', 'ragged', 'vector'])
 def test_adjoint_kernels(name):
     """d_coef = qtab * DCT(d_img) and d_x = iDCT(d_coef / qtab) against float64, and <A x, y> = <x, A^T y> with both sides from the kernels"""
     from esr_hip import jpeg as J
@@ -135,7 +159,7 @@ def test_adjoint_kernels(name):
     assert float(xq.grad.abs().max()) == 0.0
 
 
-@pytest.mark.parametrize('name', ['noise', 'smooth', 'user'])
+@pytest.mark.parametrize('name', ['noise', 'smooth', 'user', 'one', 'ragged', 'vector'])
 def test_quantised_compressor_under_the_tie_rule(name):
     from esr_hip import jpeg as J
     x, tables, ref, _ = _case(name)
@@ -155,16 +179,66 @@ def test_quantised_compressor_under_the_tie_rule(name):
 def test_act_out_equals_pack_of_the_fp32_result(planes, quantize):
     from esr_hip import _lib, jpeg as J
     from esr_hip.act import new_zeroed, view_of
-    x, tables, _, _ = _case('smooth')
-    xg, tg = x.to(DEV), tables.to(DEV)
+    for name in ('smooth', 'ragged'):                                                  # 'ragged': a partial tile, the j < nb guard of the store
+        x, tables, _, _ = _case(name)
+        xg, tg = x.to(DEV), tables.to(DEV)
+        B, h, w = x.size(0), x.size(2) // 8, x.size(3) // 8
+        for lead in (0, 8):                                                            # behind `lead` groups of a wider buffer, as behind Z
+            a, b = new_zeroed(planes, B, lead + 8, h, w, DEV), new_zeroed(planes, B, lead + 8, h, w, DEV)
+            coef = J.compress_into(xg, tg, quantize, view_of(a, lead, 8))
+            assert torch.equal(coef, J.compress(xg, tg, quantize))
+            assert _lib.lib.esr_pack_nchw(coef.data_ptr(), 0, B, 64, h, w, 0, 64, 0, 1, C.byref(view_of(b, lead, 8)), _stream()) == 0
+            assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+            assert J.compress_into(xg, tg, quantize, view_of(a, lead, 8), want_coef=False) is None
+
+
+def _off16(t):
+    """(guard buffer, a copy of t that starts 4 bytes behind a 16-byte boundary: the guard's element 0 lies in front of it)"""
+    buf = torch.zeros(t.numel() + 1, device=DEV)
+    off = buf[1:].view(t.shape)
+    off.copy_(t)
+    assert off.data_ptr() % 16 == 4 and off.is_contiguous()
+    return buf, off
+
+
+def test_unaligned_coefficient_pointers_take_the_scalar_path_and_give_the_same_bits():
+    """w = 36 would take the 16-byte path; a coefficient pointer 4 bytes off a 16-byte boundary must fall back: every coefficient-side
+    pointer of the three entry points that have one, one at a time, against the aligned call"""
+    from esr_hip import _lib
+    L = _lib.lib
+    x, tables, _, _ = _case('vector')
     B, h, w = x.size(0), x.size(2) // 8, x.size(3) // 8
-    for lead in (0, 8):                                                                # behind `lead` groups of a wider buffer, as behind Z
-        a, b = new_zeroed(planes, B, lead + 8, h, w, DEV), new_zeroed(planes, B, lead + 8, h, w, DEV)
-        coef = J.compress_into(xg, tg, quantize, view_of(a, lead, 8))
-        assert torch.equal(coef, J.compress(xg, tg, quantize))
-        assert _lib.lib.esr_pack_nchw(coef.data_ptr(), 0, B, 64, h, w, 0, 64, 0, 1, C.byref(view_of(b, lead, 8)), _stream()) == 0
-        assert torch.equal(a.view(torch.int16), b.view(torch.int16))
-        assert J.compress_into(xg, tg, quantize, view_of(a, lead, 8), want_coef=False) is None
+    xg, tg = x.to(DEV), tables.to(DEV)
+    new = lambda *shape: torch.zeros(*shape, device=DEV)
+    # esr_jpeg_compress: the output
+    coef = new(B, 64, h, w)
+    assert L.esr_jpeg_compress(xg.data_ptr(), B, 8 * h, 8 * w, tg.data_ptr(), 1, coef.data_ptr(), None, _stream()) == 0
+    buf, off = _off16(coef * 0)
+    assert L.esr_jpeg_compress(xg.data_ptr(), B, 8 * h, 8 * w, tg.data_ptr(), 1, off.data_ptr(), None, _stream()) == 0
+    assert torch.equal(off, coef) and float(buf[0]) == 0.0
+    # esr_jpeg_extract: coef, y, coef_out
+    y = seeded_uniform((B, 64, h, w), 4330, -3.0, 3.0).to(DEV)
+    c_a, img_a = new(B, 64, h, w), new(B, 1, 8 * h, 8 * w)
+    assert L.esr_jpeg_extract(coef.data_ptr(), y.data_ptr(), B, h, w, tg.data_ptr(), c_a.data_ptr(), img_a.data_ptr(), _stream()) == 0
+    for which in ('coef', 'y', 'coef_out'):
+        args = {'coef': coef, 'y': y, 'coef_out': new(B, 64, h, w)}
+        buf, args[which] = _off16(args[which])
+        img = new(B, 1, 8 * h, 8 * w)
+        assert L.esr_jpeg_extract(args['coef'].data_ptr(), args['y'].data_ptr(), B, h, w, tg.data_ptr(), args['coef_out'].data_ptr(),
+                                  img.data_ptr(), _stream()) == 0, which
+        assert torch.equal(img, img_a) and torch.equal(args['coef_out'], c_a), which
+        assert float(buf[0]) == 0.0, which
+    # esr_jpeg_extract_grad: d_coef, d_y
+    d_img = seeded_uniform((B, 1, 8 * h, 8 * w), 4331, -1.0, 1.0).to(DEV)
+    dc_a, dy_a = new(B, 64, h, w), new(B, 64, h, w)
+    assert L.esr_jpeg_extract_grad(d_img.data_ptr(), y.data_ptr(), B, h, w, tg.data_ptr(), dc_a.data_ptr(), dy_a.data_ptr(), _stream()) == 0
+    for which in ('d_coef', 'd_y'):
+        args = {'d_coef': new(B, 64, h, w), 'd_y': new(B, 64, h, w)}
+        buf, args[which] = _off16(args[which])
+        assert L.esr_jpeg_extract_grad(d_img.data_ptr(), y.data_ptr(), B, h, w, tg.data_ptr(), args['d_coef'].data_ptr(),
+                                       args['d_y'].data_ptr(), _stream()) == 0, which
+        assert torch.equal(args['d_coef'], dc_a) and torch.equal(args['d_y'], dy_a), which
+        assert float(buf[0]) == 0.0, which
 
 
 def test_jpeg_module_on_the_gpu_matches_the_fixture():

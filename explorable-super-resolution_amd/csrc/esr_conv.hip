@@ -86,6 +86,10 @@ struct ConvArgs {
     int resin_g0;                   // EPI_RESIN: index (in the concatenated in0|in1 group order) of the residual's first group
     float resin_scale;              // beta1 / alpha
     int ps, ps_rg0;                 // pixel-shuffle store: factor r (0 = plain) and the first row group of this launch (esr_hip.h)
+    // phase launch (esr_conv3x3_desc.upsample_phases, TMODE 3): the grid is ntiles * nslices workgroups in ONE dimension, the slices of a tile
+    // next to each other in the XCD's sweep (they stage the same input tile: the second to fourth read it out of that XCD's L2)
+    unsigned m_ns, i_ns;            // ceil(2^32 / nslices), as m_tx / i_tx
+    int ph_off;                     // set by the kernel: byte offset of this workgroup's phase row inside a 2x2 output block
     // split K (esr_conv3x3_desc.k_split_ws): blockIdx.z = which run of `ncp` chunks (kz_groups channel groups) of the input this workgroup
     // contracts; its fp32 partial sums go to slab z of the workspace ([B][nchw_ctot][H][W] each, EPI_NCHW store), bias in slab 0 only
     int ksplit, kz_groups;
@@ -209,7 +213,7 @@ __device__ __forceinline__ DmaShare unpack_share(unsigned w) { return DmaShare{(
 template <int NPL, int MT = 1, int NPW = 1, int TMODE = 0>
 __device__ __forceinline__ int dma_count(const DmaShare& d, bool xlo) { return (xlo ? 2 * NPL : 2) * d.nsl + (TMODE != 0 ? MT * NPW : d.wc); }
 
-// tsel (TMODE 1: the chunk's tap-set index (cp >> 1) & 3; TMODE 2: parity of the output slice): the live taps of an embedded stride-2 conv are
+// tsel (TMODE 1: the chunk's tap-set index (cp >> 1) & 3; TMODE 2 / 3: parity of the output slice): the live taps of an embedded stride-2 conv are
 // the 2x2 block of taps at (r0, c0): S2D_FWD[q] -> (1 - (q >> 1), 1 - (q & 1)), S2D_FLIP[q] -> (q >> 1, q & 1) with q = 2 * parity + m.  The dead
 // taps' fragments (5 of 9: zeros in the pack) are neither copied nor read — on the 512-channel layers the weight copies ARE the launch.
 template <int NPL, int MT, int NPW, int TMODE = 0>
@@ -409,7 +413,8 @@ constexpr int S2D_FWD[4] = {432, 216, 54, 27}, S2D_FLIP[4] = {27, 54, 216, 432};
 // (-1: its pixel is pitch padding or outside the image; ncg_out - half otherwise, so that one compare `cg0 < lim` covers both the pixel and
 // the existence of group cg0 + half; `cg0 < lim + half`: the pixel is inside and the pair has its group cg0 — both halves of the wave compute
 // such a pair, the lane exchanges need both).  KIND 1 (fp32 NCHW destination): poff = byte offset inside a channel plane, lim without the
-// half term, 0 outside (every lane stores its own 4 channels of both groups); KIND 2 (pixel-shuffle store): poff = Y << 16 | X.
+// half term, 0 outside (every lane stores its own 4 channels of both groups); KIND 2 (pixel-shuffle store): poff = Y << 16 | X; KIND 3 (phase
+// store): poff = byte offset of pixel (2Y, 2X) of the twice-as-large destination.
 template <int R>
 struct EpiCoord {
     int lim[R];
@@ -428,12 +433,15 @@ __device__ __forceinline__ EpiCoord<R> epi_coords(const ConvArgs& a, int x0, int
         e.lim[r] = valid ? (KIND == 1 ? a.ncg_out : a.ncg_out - half) : (KIND == 1 ? 0 : -1);
         if (KIND == 1) e.poff[r] = (__umul24(Y, a.W) + X) * 4;
         else if (KIND == 2) e.poff[r] = (Y << 16) | X;
+        else if (KIND == 3) e.poff[r] = valid ? (__umul24(2 * Y + 1, 2 * a.W + 2) + 2 * X + 1) * 16 : 0;
         else e.poff[r] = valid ? (__umul24(Y + 1, a.W + 2) + X + 1) * 16 : 0;
     }
     return e;
 }
 
-template <int NPL, int MT, int R, int EPI, int FMT, bool PARTLO>
+// PHASE (the phase launch): both M tiles hold the SAME 32 channels (groups 0-3 of the slice's block) for the output pixels (2Y + py, 2X + m):
+// the row py comes as a.ph_off, the column is the M tile.
+template <int NPL, int MT, int R, int EPI, int FMT, bool PARTLO, bool PHASE = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[MT][R], const int b, const EpiCoord<R>& ec, const int lane) {
     constexpr bool HAS_R1 = (EPI & EPI_RES1) != 0, HAS_R2 = (EPI & EPI_RES2) != 0, HAS_MK = (EPI & EPI_MASK) != 0;
     constexpr bool NCHW = (EPI & EPI_NCHW) != 0, OUT2 = (EPI & EPI_OUT2) != 0, PS = (EPI & EPI_PS) != 0;
@@ -512,7 +520,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
         for (int m = 0; m < MT; ++m) {
 #pragma unroll
             for (int gp = 0; gp < 2; ++gp) {
-                const int cg0 = m * 4 + gp * 2;                  // this pair: output groups cg0, cg0+1
+                const int cg0 = (PHASE ? 0 : m * 4) + gp * 2;    // this pair: output groups cg0, cg0+1
                 // per lane: pixel inside the image and group cg0 exists.  Lane i + 32 computes channels 4-7 of group cg0 for lane i's store (the
                 // exchanges below), so both halves compute the last pair of an odd group count; only lanes whose group cg0 + half exists store.
                 if (!(cg0 < ec.lim[r] + (NCHW ? 0 : half))) continue;
@@ -605,7 +613,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
                     const int cgs = cg0 + half, rg = a.ps_rg0 + cgs, r2 = a.ps * a.ps, sp = rg % r2;
                     const int Y = ec.poff[r] >> 16, X = ec.poff[r] & 0xFFFF;
                     off = ((unsigned)(rg / r2) * (unsigned)a.out.cs + (unsigned)(a.ps * Y + sp / a.ps + 1) * (a.ps * a.W + 2) + (a.ps * X + sp % a.ps + 1)) * 16;
-                } else off = ec.poff[r] + ho + cg0 * ((unsigned)a.out.cs * 16);
+                } else off = ec.poff[r] + ho + cg0 * ((unsigned)a.out.cs * 16) + (PHASE ? (unsigned)a.ph_off + m * 16 : 0u);
                 if (store) {
                     *(uint4*)(oh + off) = hv;
                     if (NPL == 2 && (!PARTLO || ol)) *(uint4*)(ol + off) = lv;
@@ -650,7 +658,9 @@ __device__ __forceinline__ void bias_seed(const float* bias, int half, float (&b
 //             and nobody else covers its DMA waits.
 //   NST == 4: a ring of four stages, three chunks of copies in flight: few, small tiles with a long K axis (the critic's deep layers).
 // TMODE: 0 all taps; 1 the K chunks' tap sets follow S2D_FWD by the parity (cp >> 1) & 3 of their channel quad (forward of an embedded stride-2
-// conv); 2 the M tiles' tap sets follow S2D_FLIP by the parity of output tile 2 * slice + m (its data gradient)
+// conv); 2 the M tiles' tap sets follow S2D_FLIP by the parity of output tile 2 * slice + m (its data gradient); 3 the same tap sets for the four
+// phases of a conv behind a nearest x2 upsample, run on the INPUT grid with folded weights (esr_conv3x3_desc.upsample_phases): slice s, M tile m =
+// output pixels (2y + (s & 1), 2x + m) of channels 32 (s >> 1) ... + 31
 //
 // Order of the prologue (round 5: a lone workgroup per CU pays every instruction in front of its first copy in full): tile decode and the
 // slots' source offsets (multiplications by host-made magic numbers, no division), the first chunk's copies — and only then, while those
@@ -661,7 +671,25 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
     // same staged input.  All workgroups of all slices are in flight together: a 512-channel layer on an 8x8 map is one launch of
     // 32 x 8 workgroups instead of eight launches of 32.  (Everything below is uniform: the shifts are scalar adds; slice 0 adds zero.)
     ConvArgs a = a_in;
-    {
+    // TMODE 3 (the phase launch) only: a one-dimensional grid over (tile, slice), the slice fastest inside an XCD's sweep (xcd_q / xcd_r count
+    // workgroups there) — decoded here, in front of the slice shifts, which need the slice; M tile j = 2 * slice + m holds phase j & 3 of the
+    // 32-channel block j >> 2.  Every other instantiation keeps its tile decode where it was, below.
+    unsigned slice = blockIdx.y, tile3 = 0;
+    if constexpr (TMODE == 3) {
+        static_assert(TMODE != 3 || (MT == 2 && EPI == 0), "the phase launch: two phases per workgroup, plain epilogue");
+        const unsigned xcd3 = blockIdx.x & 7;
+        unsigned wg = xcd3 * a.xcd_q + (xcd3 < (unsigned)a.xcd_r ? xcd3 : (unsigned)a.xcd_r) + (blockIdx.x >> 3);
+        if (a.reverse) wg = (unsigned)a.ntiles * a.nslices - 1 - wg;
+        tile3 = udiv_magic(wg, a.m_ns, a.i_ns);
+        slice = wg - tile3 * a.nslices;
+        const long long blk = slice >> 1;                           // the slice's 32-channel block: its bias, its four output groups
+        a.wpack += (long long)slice * a.wslice;
+        a.bias += blk * 32 * a.bias_stride;
+        a.out.hi += blk * 4 * a.out.cs;
+        if (a.out.lo) a.out.lo += blk * 4 * a.out.cs;
+        a.ncg_out = a.ncg_out - 4 * (int)blk < 4 ? a.ncg_out - 4 * (int)blk : 4;
+        a.ph_off = (slice & 1) ? (2 * a.W + 2) * 16 : 0;
+    } else {
         const long long sl = blockIdx.y;                            // a slice is this kernel's MT * 32 output channels
         a.wpack += sl * a.wslice;
         a.bias += sl * (MT * 32) * a.bias_stride;
@@ -700,9 +728,10 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
     const int stage_bytes = 2 * NPL * plane_bytes + NWI * 1024;
     // XCD-aware tile order: workgroup g runs on XCD g%8; each XCD sweeps a contiguous range of the tile space.  The grid is exactly ntiles
     // workgroups (XCD x owns xcd_q tiles, one more if x < xcd_r): no idle workgroup, no early exit — the prologue is branch-free
+    // (the phase launch decoded its tile above)
     const unsigned xcd = blockIdx.x & 7;
     const unsigned tile_f = xcd * a.xcd_q + (xcd < (unsigned)a.xcd_r ? xcd : (unsigned)a.xcd_r) + (blockIdx.x >> 3);
-    const unsigned tile = a.reverse ? a.ntiles - 1 - tile_f : tile_f;
+    const unsigned tile = TMODE == 3 ? tile3 : (a.reverse ? a.ntiles - 1 - tile_f : tile_f);
     const unsigned trow = udiv_magic(tile, a.m_tx, a.i_tx);         // = image * tiles_y + tile row
     const int b = udiv_magic(trow, a.m_ty, a.i_ty);
     const int x0 = (tile - trow * a.tiles_x) * a.TW, y0 = (trow - b * a.tiles_y) * a.TH;   // tile origin: output interior coords == padded coords of the halo origin
@@ -719,12 +748,12 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
 #endif
     const FetchState<MAXS> fs = setup_tile<MAXS>(a, x0, y0, wave, lane);
     ESR_TR();                                    // (slot 3) tile decoded, slot offsets formed
-    static_assert(TMODE != 2 || MT == 2, "M-tile tap masks come in pairs");
+    static_assert((TMODE != 2 && TMODE != 3) || MT == 2, "M-tile tap masks come in pairs");
     const unsigned char* const sb0 = smem + (lane >> 5) * NPL * plane_bytes + (wave * 32 + (lane & 31)) * 16;
     const unsigned char* const sa0 = smem + 2 * NPL * plane_bytes + lane * 16;
     constexpr int NTERM_CAP = 3;
     // which 2x2 block of taps chunk c's weights live in (dma_chunk)
-    auto tsel_of = [&](const int c) { return TMODE == 1 ? ((c >> 1) & 3) : (TMODE == 2 ? (int)(blockIdx.y & 1) : 0); };
+    auto tsel_of = [&](const int c) { return TMODE == 1 ? ((c >> 1) & 3) : (TMODE == 2 || TMODE == 3 ? (int)(slice & 1) : 0); };
     auto issue = [&](const int c, const unsigned stage, const bool xlo) {
         const Bases<NPL> bs = make_bases<NPL, MT, NPW>(a, c, b);
         dma_chunk<NPL, MT, NPW, TMODE>(fs, bs, share, stage, plane_bytes, xlo, tsel_of(c), wave);
@@ -738,7 +767,7 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
     // What waits for nothing: done behind the first copies.  The accumulators start from the bias (their rows' seed); the epilogue's
     // coordinates are formed here when the registers allow (the lone-workgroup forms and the one-plane 32-channel kernels), otherwise after
     // the K loop (the 64-channel kernels of the large launches sit at their 256-register limit and a co-resident workgroup covers it).
-    constexpr int EKIND = (EPI & EPI_NCHW) ? 1 : ((EPI & EPI_PS) ? 2 : 0);
+    constexpr int EKIND = TMODE == 3 ? 3 : ((EPI & EPI_NCHW) ? 1 : ((EPI & EPI_PS) ? 2 : 0));
     constexpr bool EARLY_COORDS = NST >= 2 || (MT == 1 && NPL == 1);
     f32x16 acc[MT][R];
     EpiCoord<R> ec;
@@ -746,14 +775,16 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
         // (an opaque copy of the lane index: everything per-lane below is loop-invariant and would otherwise be hoisted in front of the copies)
         int lane_o = lane;
         asm volatile("" : "+v"(lane_o));
-        float bz[MT][16];
-        bias_seed<MT>(a.bias, lane_o >> 5, bz);
+        // (the phase launch: both M tiles are the same 32 channels)
+        constexpr int MB = TMODE == 3 ? 1 : MT;
+        float bz[MB][16];
+        bias_seed<MB>(a.bias, lane_o >> 5, bz);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[m][r][i] = bz[m][i];
+                for (int i = 0; i < 16; ++i) acc[m][r][i] = bz[m % MB][i];
         if constexpr (EARLY_COORDS) ec = epi_coords<R, EKIND>(a, x0, y0, wave, lane_o);
     };
     // The first chunk's copies go out in front of the K loop, the seed right behind them.  (Seeding inside the loop's first pass instead —
@@ -806,6 +837,12 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
         } else if constexpr (TMODE == 2) {
             if (blockIdx.y & 1) chunk_mfma<NPL, MT, R, NPW, FMT, xlo, NTERM_CAP, S2D_FLIP[2], S2D_FLIP[3]>(acc, sa, sb, P, plane_bytes);
             else chunk_mfma<NPL, MT, R, NPW, FMT, xlo, NTERM_CAP, S2D_FLIP[0], S2D_FLIP[1]>(acc, sa, sb, P, plane_bytes);
+        } else if constexpr (TMODE == 3) {
+            // the lower phase row's tap sets are the upper one's moved down a row: ONE copy of the chunk body (taps 0, 1 | 3, 4 and 1, 2 | 4, 5)
+            // on bases moved by three taps of weight fragments and one row of the staged tile (uniform adds) — the two-copy form of TMODE 2
+            // does not fit the registers of two resident workgroups with hi+lo operands
+            const int py = slice & 1;
+            chunk_mfma<NPL, MT, R, NPW, FMT, xlo, NTERM_CAP, S2D_FLIP[0], S2D_FLIP[1]>(acc, sa + py * (3 * MT * NPW * 1024), sb + py * (P * 16), P, plane_bytes);
         } else {
             chunk_mfma<NPL, MT, R, NPW, FMT, xlo, NTERM_CAP>(acc, sa, sb, P, plane_bytes);
         }
@@ -819,7 +856,7 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
         for (int cp = lo_end; cp < a.ncp; ++cp) step(std::false_type{}, cp);
     ESR_TR();
     if constexpr (!EARLY_COORDS) ec = epi_coords<R, EKIND>(a, x0, y0, wave, lane);
-    conv_epilogue<NPL, MT, R, EPI, FMT, PARTLO>(a, acc, b, ec, lane);
+    conv_epilogue<NPL, MT, R, EPI, FMT, PARTLO, TMODE == 3>(a, acc, b, ec, lane);
     ESR_TR();
 #ifdef ESR_TRACE
     if (tr && tid == 0) tr[127] = wall_clock64();
@@ -827,6 +864,25 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
 }
 
 // ---- weight packing: [M][K][3][3] fp32 -> [kstep = cp*9+tap][mtile][hi|lo][lane][8] bf16
+// The folded pack of a conv behind a nearest x2 upsample (esr_hip.h, ESR_PACK_FOLD2): the weight of output phase (py, px) at tap position (ty, tx)
+// of the 3x3 window over the SOURCE grid = the sum of the original taps that read that source pixel — rows {0}, {1, 2} at ty = 0, 1 for py = 0,
+// {0, 1}, {2} at ty = 1, 2 for py = 1, columns alike — in fp32, rows first, then columns; 0 at the five positions outside the phase's 2x2 block
+// (masks 27, 54, 216, 432 for phase 0..3).  w9: the nine taps of one (output, input) channel pair.
+__device__ __forceinline__ float fold2_tap(const float* w9, int t, int phase) {
+    const int py = phase >> 1, px = phase & 1, ty = t / 3, tx = t % 3;
+    if (ty < py || ty > py + 1 || tx < px || tx > px + 1) return 0.f;
+    const int r0 = ty == py ? 0 : py + 1, r1 = ty == py ? py : 2;
+    const int c0 = tx == px ? 0 : px + 1, c1 = tx == px ? px : 2;
+    float a = w9[r0 * 3 + c0];
+    if (r1 != r0) a = __fadd_rn(a, w9[r1 * 3 + c0]);
+    if (c1 != c0) {
+        float b = w9[r0 * 3 + c1];
+        if (r1 != r0) b = __fadd_rn(b, w9[r1 * 3 + c1]);
+        a = __fadd_rn(a, b);
+    }
+    return a;
+}
+// `transposed` of the pack entry points: 0 forward, 1 data gradient, 2 + p0 folded forward pack whose M tile m holds phase (p0 + m) & 3
 __global__ void pack_weights_kernel(const float* __restrict__ w, int dim0, int dim1, const int* __restrict__ kmap, int ncg_in,
                                     const int* __restrict__ mmap, int mtiles, int transposed, int npl, int f16, float scale, uint4* __restrict__ out, int total) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (kstep, mtile, lane)
@@ -842,8 +898,10 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, int dim0, int d
     for (int e = 0; e < 8; ++e) {
         const int kch = cg < ncg_in ? kmap[cg * 8 + e] : -1;
         float v = 0.f;
-        if (kch >= 0 && mch >= 0)
-            v = transposed ? w[((long long)kch * dim1 + mch) * 9 + (8 - t)] : w[((long long)mch * dim1 + kch) * 9 + t];
+        if (kch >= 0 && mch >= 0) {
+            if (transposed >= 2) v = fold2_tap(w + ((long long)mch * dim1 + kch) * 9, t, (transposed - 2 + m) & 3);
+            else v = transposed ? w[((long long)kch * dim1 + mch) * 9 + (8 - t)] : w[((long long)mch * dim1 + kch) * 9 + t];
+        }
         v8[e] = v * scale;
     }
     uint4* o = out + ((size_t)(ks * mtiles + m) * npl) * 64 + lane;      // the lo plane of a tile follows its hi plane
@@ -875,11 +933,11 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackEntry
     for (int j = 0; j < 18; ++j) {
         const int f = j * 256 + threadIdx.x;              // walks the source runs: [32 rows][16 x 9] plain, [16 rows][32 x 9] transposed
         int mr, kc, t;
-        if (e.transposed) { kc = f / 288; const int c = f - kc * 288; mr = c / 9; t = 8 - (c - mr * 9); }
+        if (e.transposed == 1) { kc = f / 288; const int c = f - kc * 288; mr = c / 9; t = 8 - (c - mr * 9); }
         else { mr = f / 144; const int c = f - mr * 144; kc = c / 9; t = c - kc * 9; }
         const int kch = kch_s[kc], mch = mch_s[mr];
         float v = 0.f;
-        if (kch >= 0 && mch >= 0) v = e.transposed ? e.w[((long long)kch * e.dim1 + mch) * 9 + (8 - t)] : e.w[((long long)mch * e.dim1 + kch) * 9 + t];
+        if (kch >= 0 && mch >= 0) v = e.transposed == 1 ? e.w[((long long)kch * e.dim1 + mch) * 9 + (8 - t)] : e.w[((long long)mch * e.dim1 + kch) * 9 + t];
         tile[mr * PITCH + kc * 9 + t] = v;
     }
     __syncthreads();
@@ -888,7 +946,7 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackEntry
         const float* src = tile + (lane & 31) * PITCH + (lane >> 5) * 72 + t;
         float x8[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) x8[c] = src[c * 9] * e.scale;
+        for (int c = 0; c < 8; ++c) x8[c] = (e.transposed >= 2 ? fold2_tap(src + c * 9 - t, t, (e.transposed - 2 + mt) & 3) : src[c * 9]) * e.scale;
         uint4* o = e.out + ((size_t)((cp * 9 + t) * e.mtiles + mt) * e.npl) * 64 + lane;
         store8(o, e.npl == 2 ? o + 64 : nullptr, 0, x8, e.f16 ? ESR_FMT_F16 : ESR_FMT_BF16);
     }
@@ -986,7 +1044,8 @@ int launch_nst(const ConvArgs& a, hipStream_t s) {
     const size_t stage = (size_t)2 * NPL * a.NPIX_L * 16 + (size_t)9 * MT * NPW * 1024;
     const size_t lds = (NST == 1 ? 1 : (NST == 4 ? 4 : 2)) * stage;
     ESR_CLEAR_ERR();
-    hipLaunchKernelGGL(k, dim3(a.ntiles, nslices, a.ksplit > 1 ? a.ksplit : 1), dim3(NTHREADS), lds, s, a);
+    const dim3 grid = TMODE == 3 ? dim3(a.ntiles * nslices) : dim3(a.ntiles, nslices, a.ksplit > 1 ? a.ksplit : 1);
+    hipLaunchKernelGGL(k, grid, dim3(NTHREADS), lds, s, a);
     ESR_CHECK_LAUNCH();
     return ESR_OK;
 }
@@ -999,13 +1058,14 @@ int launch(const ConvArgs& a, hipStream_t s) {
     const int force = a.stages_hint;                 // esr_conv3x3_desc.lds_stages: 0 = by launch size, 1 / 2 = that form
     const bool small = ntiles <= 320;
     // few small tiles, long K: the four-stage ring where it fits (plain bf16 kernels — what the critic's deep layers launch)
-    if constexpr ((EPI == 0 || EPI == EPI_NCHW) && !PARTLO && FMT == 0 && MT == 2) {
+    if constexpr ((EPI == 0 || EPI == EPI_NCHW) && !PARTLO && FMT == 0 && MT == 2 && TMODE != 3) {
         const size_t stage = (size_t)2 * NPL * a.NPIX_L * 16 + (size_t)9 * MT * NPW * 1024;
         if (!force && small && a.ncp >= (EPI == EPI_NCHW ? 8 : 16) && 4 * stage <= 160 * 1024) return launch_nst<NPL, MT, EPI, 4, FMT, NPW, PARTLO, TMODE>(a, s);
     }
     // the tap-masked kernels with hi+lo operands (four / two copies of the chunk body with their own tap sets) do not fit the 256 registers of
     // the two-workgroups-per-CU form — they spilled 34-168 VGPRs to scratch: always the two-stage form (one workgroup per CU, 512 registers)
-    if constexpr (TMODE != 0 && NPL == 2) return launch_nst<NPL, MT, EPI, 2, FMT, NPW, PARTLO, TMODE>(a, s);
+    // (the phase launch, TMODE 3, has one copy of the body: both forms)
+    if constexpr ((TMODE == 1 || TMODE == 2) && NPL == 2) return launch_nst<NPL, MT, EPI, 2, FMT, NPW, PARTLO, TMODE>(a, s);
     else {
         const bool two = force ? force == 2 : small;
         return two ? launch_nst<NPL, MT, EPI, 2, FMT, NPW, PARTLO, TMODE>(a, s) : launch_nst<NPL, MT, EPI, 1, FMT, NPW, PARTLO, TMODE>(a, s);
@@ -1076,7 +1136,7 @@ extern "C" size_t esr_conv_wpack_bytes(int ncg_in, int cout, int split) {
 
 extern "C" int esr_pack_conv_weights(const float* w, int cout_w, int cin_w, const int32_t* kmap, int ncg_in, const int32_t* mmap,
                                      int mtiles, int transposed, int split, float scale, void* wpack, esr_stream_t stream) {
-    if (!w || !kmap || !mmap || !wpack || ncg_in <= 0 || mtiles <= 0) return ESR_E_ARG;
+    if (!w || !kmap || !mmap || !wpack || ncg_in <= 0 || mtiles <= 0 || transposed < 0 || transposed > 5) return ESR_E_ARG;
     const int ncp = (ncg_in + 1) / 2;
     const int total = ncp * 9 * mtiles * 64;
     ESR_CLEAR_ERR();
@@ -1089,7 +1149,9 @@ extern "C" int esr_pack_conv_weights(const float* w, int cout_w, int cin_w, cons
 static int64_t pack_batch_blocks(const esr_pack_desc* descs, int n) {
     int64_t nb = 0;
     for (int i = 0; i < n; ++i) {
-        if (!descs[i].w || !descs[i].kmap || !descs[i].mmap || !descs[i].wpack || descs[i].ncg_in <= 0 || descs[i].mtiles <= 0) return ESR_E_ARG;
+        if (!descs[i].w || !descs[i].kmap || !descs[i].mmap || !descs[i].wpack || descs[i].ncg_in <= 0 || descs[i].mtiles <= 0 || descs[i].transposed < 0 ||
+            descs[i].transposed > 5)
+            return ESR_E_ARG;
         nb += (int64_t)((descs[i].ncg_in + 1) / 2) * descs[i].mtiles;             // one block per (K chunk, M tile)
     }
     return nb;
@@ -1145,7 +1207,7 @@ extern "C" int esr_pack_batch_run(const void* workspace, int n, int64_t nblocks,
 static TileCfg conv_tiling(const esr_conv3x3_desc* d, int npl, int mt, int nslices, int ps, bool& mslice) {
     mslice = false;
     auto all_taps = [](const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); };
-    if (nslices == 1 && mt == 2 && d->cout == 64 && !d->out_nchw && !ps && d->lds_stages == 0 && !d->k_split_ws && all_taps(d->tap_mask_k) &&
+    if (nslices == 1 && mt == 2 && d->cout == 64 && !d->out_nchw && !ps && d->upsample_phases != 2 && d->lds_stages == 0 && !d->k_split_ws && all_taps(d->tap_mask_k) &&
         all_taps(d->tap_mask_m) && (!d->mask_src.hi || (d->mask_cg0 == 0 && d->mask_cg1 >= 8))) {
         const TileCfg t2 = pick_tile(d->H, d->W, npl, 2, WGS_MT2);
         mslice = t2.TH != 0 && (long long)t2.tiles_x * t2.tiles_y * d->B <= 320;
@@ -1156,8 +1218,9 @@ static TileCfg conv_tiling(const esr_conv3x3_desc* d, int npl, int mt, int nslic
 
 extern "C" int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling) {
     if (!d || !tiling || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return ESR_E_ARG;
-    if (d->cout > 64 && d->cout % 64) return ESR_E_UNSUPPORTED;
-    const int nslices = d->cout > 64 ? d->cout / 64 : 1;
+    const bool phases = d->upsample_phases == 2;       // two slices (phase rows) of two M tiles (phase columns) per 32-channel block
+    if (!phases && d->cout > 64 && d->cout % 64) return ESR_E_UNSUPPORTED;
+    const int nslices = phases ? 2 * ((d->cout + 31) / 32) : (d->cout > 64 ? d->cout / 64 : 1);
     const int mt = nslices > 1 ? 2 : (d->cout + 31) / 32;
     bool mslice = false;
     const TileCfg t = conv_tiling(d, d->in1.lo ? 2 : 1, mt, nslices, d->pixel_shuffle > 1 ? d->pixel_shuffle : 0, mslice);
@@ -1176,6 +1239,14 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     // the kernel forms the source coordinate (c - 1 + ups) / ups as a multiplication (setup_tile): exact for these factors only
     if (ups > 8 || ups == 5 || ups == 7) return ESR_E_UNSUPPORTED;
     if (ups > 1 && d->in0.hi) return ESR_E_UNSUPPORTED;
+    // the phase launch (upsample_phases = 2): the conv behind a nearest x2 upsample as four 4-tap convs on the input grid; H, W = source size
+    if (d->upsample_phases != 0 && d->upsample_phases != 2) return ESR_E_UNSUPPORTED;
+    const bool phases = d->upsample_phases == 2;
+    if (phases) {
+        if (ups > 1) return ESR_E_ARG;                  // one way of upsampling per launch
+        if (d->in0.hi || d->res1.hi || d->res2.hi || d->mask_src.hi || d->out2.hi || d->out_nchw || d->pixel_shuffle > 1) return ESR_E_UNSUPPORTED;
+        if (!d->out.hi || d->out.H != 2 * d->H || d->out.W != 2 * d->W) return ESR_E_ARG;
+    }
     if (d->in1.H * ups != d->H || d->in1.W * ups != d->W) return ESR_E_ARG;
     if (d->in0.hi && (d->in0.H != d->H || d->in0.W != d->W)) return ESR_E_ARG;
     const bool split = d->in1.lo != nullptr;
@@ -1188,14 +1259,14 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     // cout > 64: output slices of 64 channels in ONE launch (grid y); the caller packs the weights of slice s (rows 64 s .. 64 s + 63) as a
     // 64-row pack at byte offset s * esr_conv_wpack_bytes(groups, 64, fmt) of `wpack`; bias, out, out2, res1, res2 and mask_src are
     // indexed by absolute output channel
-    const int nslices = d->cout > 64 ? d->cout / 64 : 1;
-    if (d->cout > 64 && (d->cout % 64 || d->out_nchw || d->pixel_shuffle > 1 || !d->out.hi)) return ESR_E_UNSUPPORTED;
+    const int nslices = phases ? 2 * ((d->cout + 31) / 32) : (d->cout > 64 ? d->cout / 64 : 1);
+    if (!phases && d->cout > 64 && (d->cout % 64 || d->out_nchw || d->pixel_shuffle > 1 || !d->out.hi)) return ESR_E_UNSUPPORTED;
     const int mt = nslices > 1 ? 2 : (d->cout + 31) / 32;
     const int ps = d->pixel_shuffle > 1 ? d->pixel_shuffle : 0;
     if (ps) {
         if (!d->out.hi || d->out_nchw || d->out2.hi || d->res1.hi || d->res2.hi || d->mask_src.hi || d->cout % 8) return ESR_E_UNSUPPORTED;
         if (d->out.H != ps * d->H || d->out.W != ps * d->W || (d->ps_rowgroup0 + d->cout / 8 + ps * ps - 1) / (ps * ps) > d->out.ncg) return ESR_E_ARG;
-    } else if (d->out.hi && (d->out.H != d->H || d->out.W != d->W)) return ESR_E_ARG;
+    } else if (!phases && d->out.hi && (d->out.H != d->H || d->out.W != d->W)) return ESR_E_ARG;
     if (!ps && d->out.hi && d->out.ncg * 8 < d->cout) return ESR_E_ARG;
     // a missing lo OUTPUT plane with hi+lo inputs is the single-plane-intermediate case (fp16 formats only, checked below)
     if (d->out.hi && d->out.lo && !split) return ESR_E_ARG;
@@ -1213,7 +1284,7 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     if (!a.zero_bias) return ESR_E_LAUNCH;
     a.bias = d->bias ? d->bias : a.zero_bias;
     a.bias_stride = d->bias ? 1 : 0;
-    a.cout = nslices > 1 ? 64 : d->cout;
+    a.cout = phases ? d->cout : (nslices > 1 ? 64 : d->cout);       // (the phase kernel takes its slice's groups from the total)
     a.nslices = nslices;
     a.B = d->B;
     a.H = d->H;
@@ -1230,6 +1301,14 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     a.ntiles = a.tiles_x * a.tiles_y * a.B;
     a.xcd_q = a.ntiles / 8;
     a.xcd_r = a.ntiles % 8;
+    if (phases) {                                      // one grid dimension over (tile, slice): conv3x3_tile_kernel, TMODE 3
+        const long long wgs = (long long)a.ntiles * nslices;
+        if (wgs * nslices >= 0x100000000ll) return ESR_E_UNSUPPORTED;
+        a.xcd_q = (int)(wgs / 8);
+        a.xcd_r = (int)(wgs % 8);
+        a.m_ns = (unsigned)((0x100000000ull + nslices - 1) / nslices);
+        a.i_ns = 0;
+    }
     a.m_tx = a.tiles_x == 1 ? 0 : (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);     // (divisor 1: 2^32 does not fit — udiv_magic adds n * i instead)
     a.m_ty = a.tiles_y == 1 ? 0 : (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
     a.i_tx = a.tiles_x == 1;
@@ -1319,6 +1398,14 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     }
     if (split && d->out.hi && !d->out.lo) partlo = true;
     if (partlo && !f16) return ESR_E_UNSUPPORTED;                   // single-plane intermediates exist for the fp16 formats only
+    if (phases) {
+        if (partlo) return ESR_E_UNSUPPORTED;                       // whole hi+lo or whole one-plane operands and destination
+        a.wslice = (long long)a.ncp * 9 * 2 * wpl * 64;             // one 64-row pack (two phases of one 32-channel block) per slice
+        if (f16 && split && wpl == 2) return launch<2, 2, 0, 1, 2, false, 3>(a, s);
+        if (f16 && split) return launch<2, 2, 0, 1, 1, false, 3>(a, s);
+        if (f16) return launch<1, 2, 0, 1, 1, false, 3>(a, s);
+        return split ? launch<2, 2, 0, 0, 2, false, 3>(a, s) : launch<1, 2, 0, 0, 1, false, 3>(a, s);
+    }
     // tap masks are a HINT (blocks outside them must be zero in the pack): the two patterns with compiled kernels are honoured, anything
     // else multiplies all nine taps — the same result
     auto all9 = [](const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); };

@@ -27,7 +27,7 @@ class Conv3x3Desc(C.Structure):
                 ('reverse_order', C.c_int32), ('weight_planes', C.c_int32), ('in1_lo_groups', C.c_int32),
                 ('pixel_shuffle', C.c_int32), ('ps_rowgroup0', C.c_int32), ('tap_mask_k', C.c_int32 * 4), ('tap_mask_k_shift', C.c_int32),
                 ('tap_mask_m', C.c_int32 * 4), ('k_split_ws', C.c_void_p), ('k_split_ws_floats', C.c_int64), ('lds_stages', C.c_int32),
-                ('range_flag', C.c_void_p), ('range_tag', C.c_uint32)]
+                ('range_flag', C.c_void_p), ('range_tag', C.c_uint32), ('upsample_phases', C.c_int32)]
 
 
 class WgradDesc(C.Structure):
@@ -301,6 +301,7 @@ class _LazyLib:
 lib = _LazyLib()
 
 ESR_OK, ESR_E_ARG, ESR_E_UNSUPPORTED, ESR_E_LAUNCH = 0, -1, -2, -3
+PACK_FOLD2 = 2              # esr_pack_conv_weights / esr_pack_desc `transposed` = PACK_FOLD2 + first phase: the folded pack of a phase launch
 _ERR = {-1: 'ESR_E_ARG (bad argument)', -2: 'ESR_E_UNSUPPORTED (unsupported shape)', -3: 'ESR_E_LAUNCH (HIP launch error)'}
 
 

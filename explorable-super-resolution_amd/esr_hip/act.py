@@ -292,8 +292,11 @@ class PackedConv:
     """MFMA-fragment-ordered copy of one nn.Conv2d(k=3) weight (+ zero-padded bias), re-packed on demand when the
     parameter changes (torch bumps `_version` on every in-place update, e.g. an optimizer step or load_state_dict)."""
 
-    def __init__(self, weight, bias, lat, split=True, transposed=False, m_slice=None, rows=None):
+    def __init__(self, weight, bias, lat, split=True, transposed=False, m_slice=None, rows=None, fold=None):
         self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, bias, lat, split, transposed
+        # forward packs only: the first phase of a pack folded for a phase launch (esr_pack_conv_weights, ESR_PACK_FOLD2), None = plain
+        self.fold = fold
+        assert fold is None or not transposed
         self.m_slice = m_slice        # data-gradient packs: (lo, hi) slice of the main input channels, or 'latent'
         # explicit order of the tensor's OUTPUT channels (pixel-shuffle convs, see esr_conv3x3_desc.pixel_shuffle): forward packs take
         # them as the M rows of this launch, data-gradient packs as the K axis (the layout esr_pixel_unshuffle leaves the gradient in)
@@ -378,7 +381,8 @@ class PackedConv:
         if wd.dtype != torch.float32 or not wd.is_contiguous():
             wd = wd.float().contiguous()
         self._wd = wd                             # keeps a converted copy alive until the pack has run
-        return [(wd, self.kmap, self.ncg_in, self.mmap, self.mtiles, 1 if self.transposed else 0, 1.0, self.wpack.data_ptr())]
+        form = _lib.PACK_FOLD2 + self.fold if self.fold is not None else (1 if self.transposed else 0)
+        return [(wd, self.kmap, self.ncg_in, self.mmap, self.mtiles, form, 1.0, self.wpack.data_ptr())]
 
     @property
     def needs_after_pack(self):
@@ -477,6 +481,44 @@ class PackedConvSlices:
         run_pack_jobs(self.jobs(), self.split)
         self.after_pack()
         return self
+
+
+class PackedConvPhases(PackedConvSlices):
+    """The forward weight of a conv behind a nearest x2 upsample, folded for the phase launch (esr_conv3x3_desc.upsample_phases = 2): per
+    32-channel block c of the output two 64-row slices back to back — phases 0, 1 and phases 2, 3 of the block's rows, each M tile of a slice
+    one phase (esr_pack_conv_weights, ESR_PACK_FOLD2).  The bias is indexed by channel and padded to whole blocks."""
+
+    def __init__(self, weight, bias, split=True):
+        cout = weight.shape[0]
+        self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, bias, 0, split, False
+        self.parts = []
+        for c in range((cout + 31) // 32):
+            rows = [m if m < cout else -1 for m in range(32 * c, 32 * c + 32)]
+            self.parts += [PackedConv(weight, None, 0, split=split, rows=rows + rows, fold=p0) for p0 in (0, 2)]
+        self._key, self.wpack, self.bias = None, None, None
+
+    def prepare(self):
+        if self.wpack is None:
+            w = self.weight
+            require_gpu(w, 'conv weight')
+            per = _lib.lib.esr_conv_wpack_bytes((w.shape[1] + 7) // 8, 64, fmt_code(self.split))
+            self.wpack = torch.empty(len(self.parts) * per, dtype=torch.uint8, device=w.device)
+            for s, pk in enumerate(self.parts):
+                pk.wpack = self.wpack[s * per:(s + 1) * per]
+                pk.prepare()
+            bp, nb = self.bias_p, 32 * (len(self.parts) // 2)
+            if bp is not None and bp.dtype == torch.float32 and bp.is_contiguous() and bp.numel() == nb:
+                self.bias, self._bias_shared = bp.detach(), True
+            else:
+                self.bias, self._bias_shared = torch.zeros(nb, dtype=torch.float32, device=w.device), False
+        return self
+
+    def after_pack(self):
+        if self.bias_p is not None and not self._bias_shared:
+            self.bias[:self.bias_p.numel()].copy_(self.bias_p.detach().float())
+        if self._bias_shared and self.bias.data_ptr() != self.bias_p.data_ptr():
+            self.bias = self.bias_p.detach()
+        self._key = self.key()
 
 
 def run_pack_jobs(jobs, split):
@@ -636,8 +678,9 @@ class watching:
 
 def conv3x3(pc, in1, B, H, W, cout, in0=None, upsample=1, act_slope=1.0, alpha=1.0, res1=None, beta1=0.0, res2=None, beta2=0.0,
             out=None, out2=None, out_nchw=None, use_bias=True, mask_src=None, mask_cg=(0, 0), mask_slope=0.2, reverse=None, in1_lo_groups=0,
-            pixel_shuffle=0, ps_rowgroup0=0, tap_mask_k=None, tap_mask_k_shift=0, tap_mask_m=None, k_split_ws=None, name=None):
+            pixel_shuffle=0, ps_rowgroup0=0, tap_mask_k=None, tap_mask_k_shift=0, tap_mask_m=None, k_split_ws=None, name=None, upsample_phases=0):
     d = _lib.Conv3x3Desc()
+    d.upsample_phases = upsample_phases       # 2: pc is a PackedConvPhases and H, W are the SOURCE size (esr_conv3x3_desc)
     if _range_watch is not None:
         d.range_flag, d.range_tag = _range_watch.flag.data_ptr(), len(_range_watch.names)
         _range_watch.names.append(name or 'conv %d' % len(_range_watch.names))

@@ -234,6 +234,14 @@ class RRDBEngine:
                 if name.startswith('up') and self._pshuf:
                     for q in range(self._pshuf ** 2):         # 64 * r^2 conv channels = r^2 launches of 64 rows
                         d[name, q] = A.PackedConv(c.weight, c.bias, lat, split=self._wfmt(name.startswith('rrdb')), rows=self._ps_rows(q))
+                elif name.startswith('up') and self.net.upscale != 3:      # nearest x2 + conv: the four-phase form on the input grid
+                    # a folded weight is rounded ONCE where the nine-tap form rounds its (up to four) taps one by one, errors that partly cancel: in
+                    # the one-plane fp16 weight format that is what the output error of these last layers is made of (configs[1] probe, f16x2:
+                    # 7.5e-4 -> 1.1e-3 against the 1e-3 bar), so hi+lo activations get the hi+lo weight pack here — 12 MFMAs per product pair
+                    # where the nine-tap form had 18
+                    d[name] = A.PackedConvPhases(c.weight, c.bias, split='f16x3' if self.split == 'f16x2' else self._wfmt(False))
+                    # the nine-tap pack of the same layer: the differentiable forward keeps that form (_forward_launches)
+                    d[name, 'taps9'] = (A.PackedConvSlices if c.weight.shape[0] > 64 else A.PackedConv)(c.weight, c.bias, lat, split=self._wfmt(False))
                 elif c.weight.shape[0] > 64:                  # nf = 128, 192, ...: output slices of one launch
                     d[name] = A.PackedConvSlices(c.weight, c.bias, lat, split=self._wfmt(name.startswith('rrdb')))
                 else:
@@ -479,8 +487,17 @@ class RRDBEngine:
             if self._pshuf:     # conv 64 -> 64*f^2 at the INPUT resolution, pixel shuffle folded into the store, LeakyReLU before it (it commutes)
                 for q in range(f * f):
                     conv(pk['up%d' % j, q], src.view(), B, s // f * h, s // f * w, 64, act_slope=0.2, out=bufs['ups'][j].view(), pixel_shuffle=f, ps_rowgroup0=8 * q, name='upconv%d' % j)
+            elif f == 2 and keep is False:
+                # inference: four 4-tap phase convs on the input grid with folded weights (esr_conv3x3_desc.upsample_phases): 4/9 of the products
+                conv(pk['up%d' % j], src.view(), B, s // f * h, s // f * w, nf, upsample_phases=2, act_slope=0.2, out=bufs['ups'][j].view(), name='upconv%d' % j)
             else:
-                conv(pk['up%d' % j], src.view(), B, s * h, s * w, nf, upsample=f, act_slope=0.2, out=bufs['ups'][j].view(), name='upconv%d' % j)
+                # x3, and every forward that keeps activations for a backward pass: nine taps on the upsampled grid.  The phase form is as
+                # accurate (error rms of HR_conv0's pre-activations against float64 1.11e-5 of their rms either way), but it is another
+                # rounding, and a gradient is only piecewise continuous in the activations: the golden input gradient of the x8 generator on
+                # an 8 x 8 image (tests/test_gpu_backward.py) then sees five of 262144 HR_conv0 activations with |pre| < 1.1e-5 rms on the other
+                # branch and its median bar (2e-4) reads 1.9e-3.  The backward reads the unfolded weights in any case.
+                conv(pk[('up%d' % j, 'taps9') if f == 2 else 'up%d' % j], src.view(), B, s * h, s * w, nf, upsample=f, act_slope=0.2, out=bufs['ups'][j].view(),
+                     name='upconv%d' % j)
             src = bufs['ups'][j]
         conv(pk['hr0'], src.view(), B, H, W, nf, in0=zhr, act_slope=0.2, out=bufs['hr0'].view(), name='HR_conv0')
         conv(pk['hr1'], bufs['hr0'].view(), B, H, W, net.out_nc, in0=zhr, out_nchw=g)

@@ -160,13 +160,30 @@ typedef struct {
      * consumes the pass's result: the smallest tag names the first layer that left the range. */
     uint32_t* range_flag;
     uint32_t range_tag;
+    /* the conv behind a nearest x2 upsample (codes/models/modules/block.py:293-309) as four 4-tap convs on the INPUT grid, in place of
+     * upsample = 2: every 2x2 block of the upsampled image holds one value, so output phase (py, px) of out[2y + py][2x + px] reads only the 2x2
+     * source neighbourhood (y - 1 + py .. y + py, x - 1 + px .. x + px), with weights that are sums of the original taps — 4/9 of the products.
+     * upsample_phases = 2: H, W and in1 are the SOURCE size, out.H == 2 * H and out.W == 2 * W (ESR_E_ARG otherwise, and with upsample > 1);
+     * `wpack` holds the folded packs of esr_pack_conv_weights (transposed = ESR_PACK_FOLD2 + p0): for every 32-channel block c of the output two
+     * 64-row packs back to back, slice 2c (phases 0, 1: p0 = 0) and slice 2c + 1 (phases 2, 3: p0 = 2), both M tiles of a slice mapping the rows of
+     * block c, slice s at byte offset s * esr_conv_wpack_bytes(in1.ncg, 64, fmt); `bias` has ceil(cout / 32) * 32 floats, indexed by channel.
+     * The 32-row tile j = 2 * slice + tile of the launch is phase j & 3 of channels 32 * (j >> 2) ..., the order tap_mask_m = {27, 54, 216, 432}
+     * describes; only the four live taps' weight fragments are copied and multiplied.  Epilogue: bias and alpha * LeakyReLU; one launch, a whole
+     * 16-byte pixel vector per lane and group as in the plain store; the source's stored zero border is the upsampled image's zero padding.
+     * Accepted: every element format (bf16, split bf16, f16, f16 hi+lo with 1 or 2 weight planes), any cout with out.ncg * 8 >= cout, both LDS
+     * forms (lds_stages).  Refused with ESR_E_UNSUPPORTED: in0, res1, res2, mask_src, out2, out_nchw, pixel_shuffle, partial lo planes
+     * (in1_lo_groups != 0, out.lo == NULL with hi+lo inputs), any other value than 0 or 2; tap masks and k_split_ws are ignored.  NOT checked,
+     * because a pack carries no mark of how it was made: that `wpack` is the folded pack in this slice order with the planes weight_planes
+     * says — a plain pack passed here is multiplied as if it were folded and the launch returns ESR_OK with a wrong result.  The result
+     * differs from the upsample = 2 launch by the fp32 rounding of the folded weights (at most three additions per weight) and the shorter sum. */
+    int32_t upsample_phases;
 } esr_conv3x3_desc;
 
 int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream);
 
 /* Host-only query (no device access, nothing launched): how esr_conv3x3 would tile the launch `d` describes, without split K.
  * tiling[0] / [1] = output tiles per image along x / y, [2] = M tiles (32 output channels) per workgroup, [3] = output slices (grid y; 2 when a
- * 64-channel layer of a small launch runs as two 32-channel slices).  The launch has tiling[0] * tiling[1] * B * tiling[3] workgroups; up to 320
+ * 64-channel layer of a small launch runs as two 32-channel slices; 2 * ceil(cout / 32) with upsample_phases = 2, whose tiles lie on the source grid).  The launch has tiling[0] * tiling[1] * B * tiling[3] workgroups; up to 320
  * of them take the small-launch (multi-stage) form.  Checks only the sizes it needs (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise). */
 int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling);
 
@@ -184,10 +201,17 @@ size_t esr_conv_wpack_bytes(int ncg_in, int cout, int split);
  *   mmap[mtiles*32] : for each output row the index into the "M" channel axis, or -1 (zero)
  *   transposed = 0 : forward     — M axis = dim 0 (cout_w), K axis = dim 1 (cin_w), tap (dy,dx) as stored
  *   transposed = 1 : data-grad   — M axis = dim 1 (cin_w),  K axis = dim 0 (cout_w), tap flipped (2-dy,2-dx)
+ *   transposed = ESR_PACK_FOLD2 + p0 (p0 = 0..3) : forward orientation, folded for esr_conv3x3_desc.upsample_phases = 2.  M tile m of the pack holds
+ *                    phase p = (p0 + m) & 3, (py, px) = (p >> 1, p & 1): at tap position (ty, tx) of the 3x3 window over the source grid the fp32
+ *                    sum of the original taps that read that source pixel — rows {0} and {1, 2} at ty = 0, 1 for py = 0, {0, 1} and {2} at
+ *                    ty = 1, 2 for py = 1, columns alike; row sums first (lower index first), then the two column terms — and zero at the five
+ *                    positions outside the phase's 2x2 block (tap masks 27, 54, 216, 432 for p = 0..3).  The sum is then scaled and split as
+ *                    any other weight.  Other values: ESR_E_ARG.  (esr_pack_desc.transposed takes the same codes.)
  * kmap/mmap are device int32 arrays; every weight is multiplied by `scale` before it is split.
  * The pack is chunk-major ([pair of K groups][tap][mtile][hi|lo][lane]): the K axis of one launch may concatenate several tensors
  * by packing each at byte offset  first_group/2 * esr_conv_wpack_bytes(2, mtiles*32, split)  of one buffer (first_group even) —
  * how the dense-block data gradient sums  W_5^T*dy_5 + ... + W_j^T*dy_j  in a single conv (block.py:230-235 backwards). */
+#define ESR_PACK_FOLD2 2
 int esr_pack_conv_weights(const float* w, int cout_w, int cin_w, const int32_t* kmap, int ncg_in,
                           const int32_t* mmap, int mtiles, int transposed, int split, float scale, void* wpack,
                           esr_stream_t stream);

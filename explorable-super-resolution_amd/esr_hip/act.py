@@ -288,12 +288,89 @@ def pack_nchw(src, dst_view, c0, nc, pad=0, down=1, hw=None, batch_stride=0, cha
           'esr_pack_nchw')
 
 
-class PackedConv:
-    """MFMA-fragment-ordered copy of one nn.Conv2d(k=3) weight (+ zero-padded bias), re-packed on demand when the
-    parameter changes (torch bumps `_version` on every in-place update, e.g. an optimizer step or load_state_dict)."""
+class _Pack:
+    """What every weight pack is: an MFMA-fragment-ordered copy (`wpack`) of the weight tensor(s) weights() names, re-packed on demand when
+    one of them changes (torch bumps `_version` on every in-place update, e.g. an optimizer step or load_state_dict), plus the `bias` the
+    kernel reads.  get() is the stand-alone path; the engines' batched re-pack (PackBatch) is assembled from prepare / jobs / after_pack.
+    A subclass says what differs: _build(dev), once (geometry, maps, destination, _bind_bias), and jobs()."""
+
+    def __init__(self, split, transposed=False, bias=None):
+        self.split, self.transposed, self.bias_p = split, transposed, bias
+        self._key = self.wpack = self.bias = None
+        self._built = self._bias_shared = False
+        self._bias_rows = None
+
+    def _fwd_bias(self):
+        """The bias parameter the kernel adds: forward packs only (a data-gradient pack ignores it)."""
+        return None if self.transposed else self.bias_p
+
+    def weights(self):
+        """The tensors the pack follows.  The bias too: without an epoch, PackBatch.run lets a pack with a shared bias re-read its address
+        (after_pack) only when one of these moved."""
+        bp = self._fwd_bias()
+        return (self.weight,) if bp is None else (self.weight, bp)
+
+    def key(self):
+        return tuple((t.data_ptr(), t._version) for t in self.weights())
+
+    def stale(self):
+        return self.key() != self._key
+
+    def prepare(self):
+        if not self._built:
+            w = self.weights()[0]
+            require_gpu(w, 'conv weight')
+            self._build(w.device)
+            self._built = True
+        return self
+
+    def _bind_bias(self, n, dev, rows=None):
+        """Bind a bias of n floats, `rows`: the parameter's elements in the order the launch wants them.  The kernel reads the parameter's own
+        storage (always current) when that IS those n floats; a private zero-padded copy otherwise, refreshed by after_pack()."""
+        bp = self._fwd_bias()
+        self._bias_shared = bp is not None and rows is None and bp.dtype == torch.float32 and bp.is_contiguous() and bp.numel() == n
+        self.bias = bp.detach() if self._bias_shared else torch.zeros(n, dtype=torch.float32, device=dev)
+        if bp is not None and rows is not None:
+            self._bias_rows = torch.tensor(rows, dtype=torch.long, device=dev)
+
+    @property
+    def needs_after_pack(self):
+        """False when after_pack() has nothing to do besides staleness bookkeeping (the batched re-pack skips it then): no bias to copy —
+        the kernel reads the parameter's own storage, whose address the engine's pointer epoch watches."""
+        return self._fwd_bias() is not None and not self._bias_shared
+
+    def after_pack(self):
+        bp = self._fwd_bias()
+        if self._bias_shared:
+            if self.bias.data_ptr() != bp.data_ptr():
+                self.bias = bp.detach()           # the parameter's storage was replaced
+        elif bp is not None:
+            b = bp.detach().float()
+            if self._bias_rows is not None:
+                b = b[self._bias_rows]
+            self.bias[:b.numel()].copy_(b)
+        self._key = self.key()
+
+    def get(self):
+        if self.stale():
+            self.prepare()
+            run_pack_jobs(self.jobs(), self.split)
+            self.after_pack()
+        return self
+
+
+def _fp32(w):
+    """w detached, as the pack kernels read it (fp32, contiguous): itself, or a converted copy the caller keeps alive until the pack has run."""
+    wd = w.detach()
+    return wd if wd.dtype == torch.float32 and wd.is_contiguous() else wd.float().contiguous()
+
+
+class PackedConv(_Pack):
+    """One nn.Conv2d(k=3) weight of up to 64 rows (+ its bias, zero-padded to whole M tiles)."""
 
     def __init__(self, weight, bias, lat, split=True, transposed=False, m_slice=None, rows=None, fold=None):
-        self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, bias, lat, split, transposed
+        super().__init__(split, transposed, bias)
+        self.weight, self.lat = weight, lat
         # forward packs only: the first phase of a pack folded for a phase launch (esr_pack_conv_weights, ESR_PACK_FOLD2), None = plain
         self.fold = fold
         assert fold is None or not transposed
@@ -301,9 +378,6 @@ class PackedConv:
         # explicit order of the tensor's OUTPUT channels (pixel-shuffle convs, see esr_conv3x3_desc.pixel_shuffle): forward packs take
         # them as the M rows of this launch, data-gradient packs as the K axis (the layout esr_pixel_unshuffle leaves the gradient in)
         self.rows = rows
-        self._key = None
-        self.wpack = None
-        self.bias = None
 
     def _maps(self, dev):
         w = self.weight
@@ -345,80 +419,47 @@ class PackedConv:
         self.m_channels = len([m for m in mmap if m >= 0])
         return (torch.tensor(kmap, dtype=torch.int32, device=dev), torch.tensor(mmap, dtype=torch.int32, device=dev))
 
-    # -- pieces the engine's batched re-pack is assembled from (esr_pack_batch_*); get() is the stand-alone path
-    def weights(self):
-        return (self.weight,)
-
-    def key(self):
-        w = self.weight
-        return (w.data_ptr(), w._version, None if self.bias_p is None else (self.bias_p.data_ptr(), self.bias_p._version))
-
-    def stale(self):
-        return self.key() != self._key
-
-    def prepare(self):
-        w = self.weight
-        require_gpu(w, 'conv weight')
-        if getattr(self, 'kmap', None) is None:
-            dev = w.device
-            self.kmap, self.mmap = self._maps(dev)
-            if self.rows is not None:
-                self._rows_t = torch.tensor(self.rows, dtype=torch.long, device=dev)
-            nbytes = _lib.lib.esr_conv_wpack_bytes(self.ncg_in, self.mtiles * 32, fmt_code(self.split))
-            if self.wpack is None:
-                self.wpack = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            assert self.wpack.numel() == nbytes      # a caller-supplied destination (one slice of a multi-slice pack, esr_hip/critic.py)
-            bp = self.bias_p
-            if bp is not None and not self.transposed and self.rows is None and bp.dtype == torch.float32 and bp.is_contiguous() and bp.numel() == self.mtiles * 32:
-                self.bias, self._bias_shared = bp.detach(), True        # the kernel reads the parameter itself: always current
-            else:
-                self.bias, self._bias_shared = torch.zeros(self.mtiles * 32, dtype=torch.float32, device=dev), False
-        return self
+    def _build(self, dev):
+        self.kmap, self.mmap = self._maps(dev)
+        nbytes = _lib.lib.esr_conv_wpack_bytes(self.ncg_in, self.mtiles * 32, fmt_code(self.split))
+        if self.wpack is None:
+            self.wpack = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        assert self.wpack.numel() == nbytes      # a caller-supplied destination (one slice of a multi-slice pack)
+        self._bind_bias(self.mtiles * 32, dev, self.rows)
 
     def jobs(self):
         """[(fp32 contiguous weight tensor, kmap, ncg_in, mmap, mtiles, transposed, scale, destination pointer)]"""
-        wd = self.weight.detach()
-        if wd.dtype != torch.float32 or not wd.is_contiguous():
-            wd = wd.float().contiguous()
-        self._wd = wd                             # keeps a converted copy alive until the pack has run
+        self._wd = _fp32(self.weight)
         form = _lib.PACK_FOLD2 + self.fold if self.fold is not None else (1 if self.transposed else 0)
-        return [(wd, self.kmap, self.ncg_in, self.mmap, self.mtiles, form, 1.0, self.wpack.data_ptr())]
-
-    @property
-    def needs_after_pack(self):
-        """False when after_pack() has nothing to do besides staleness bookkeeping (the batched re-pack skips it then): no bias to copy —
-        the kernel reads the parameter's own storage, whose address the engine's pointer epoch watches."""
-        return not (self.bias_p is None or self.transposed or self._bias_shared)
-
-    def after_pack(self):
-        if self.bias_p is not None and not self.transposed and not self._bias_shared:
-            if self.rows is not None:
-                self.bias[:len(self.rows)].copy_(self.bias_p.detach().float()[self._rows_t])
-            else:
-                self.bias[:self.weight.shape[0]].copy_(self.bias_p.detach().float())
-        if self._bias_shared and self.bias.data_ptr() != self.bias_p.data_ptr():
-            self.bias = self.bias_p.detach()      # the parameter's storage was replaced
-        self._key = self.key()
-
-    def get(self):
-        if not self.stale():
-            return self
-        self.prepare()
-        run_pack_jobs(self.jobs(), self.split)
-        self.after_pack()
-        return self
+        return [(self._wd, self.kmap, self.ncg_in, self.mmap, self.mtiles, form, 1.0, self.wpack.data_ptr())]
 
 
-class PackedConvSlices:
-    """A conv weight as PackedConv slices of up to 64 rows, back to back in one buffer — the layout esr_conv3x3 takes for more than 64 output
-    channels (output slices of one launch, include/esr_hip.h).  Forward: one slice per 64 output channels (one slice of cout rows for
-    cout <= 64); the bias is indexed by absolute channel.  transposed=True: the data-gradient pack (transposed + flipped, no bias), one slice per
-    64 INPUT channels.  `weight` is any fp32 tensor of a 3x3 conv's shape (the critic packs the 3x3 embedding of its 4x4 weights).  Same duck
-    type as PackedConv for the batched re-pack (prepare / jobs / weights / after_pack)."""
+class _PackedParts(_Pack):
+    """A pack made of PackedConv `parts` (which carry no bias) back to back in ONE buffer, each part packing its own rows of `weight`."""
+
+    def _build_parts(self, ncg_in, m, dev):
+        """One buffer of len(parts) packs of (ncg_in K groups, m rows) each: slice s is part s's destination."""
+        per = _lib.lib.esr_conv_wpack_bytes(ncg_in, m, fmt_code(self.split))
+        self.wpack = torch.empty(len(self.parts) * per, dtype=torch.uint8, device=dev)
+        for s, pk in enumerate(self.parts):
+            pk.wpack = self.wpack[s * per:(s + 1) * per]
+            pk.prepare()                          # (checks that its slice is as long as its pack)
+
+    def jobs(self):
+        return [j for pk in self.parts for j in pk.jobs()]
+
+
+class PackedConvSlices(_PackedParts):
+    """A conv weight as PackedConv slices of up to 64 rows, back to back in one buffer — the layout esr_conv3x3
+    takes for more than 64 output channels (output slices of one launch, include/esr_hip.h).  Forward: one slice per 64 output channels (one
+    slice of cout rows for cout <= 64); the bias is indexed by absolute channel.  transposed=True: the data-gradient pack (transposed + flipped,
+    no bias), one slice per 64 INPUT channels.  `weight` is any fp32 tensor of a 3x3 conv's shape (the critic packs the 3x3 embedding of its
+    4x4 weights)."""
 
     def __init__(self, weight, bias, lat=0, split=True, transposed=False):
+        super().__init__(split, transposed, None if transposed else bias)
+        self.weight, self.lat = weight, lat
         cout, cin = weight.shape[0], weight.shape[1]
-        self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, (None if transposed else bias), lat, split, transposed
         if transposed:
             assert lat == 0
             if cin > 64 and cin % 64:
@@ -427,98 +468,32 @@ class PackedConvSlices:
         else:
             assert cout <= 64 or cout % 64 == 0
             self.parts = [PackedConv(weight, None, lat, split=split, rows=list(range(m0, min(cout, m0 + 64)))) for m0 in range(0, cout, 64)]
-        self._key, self.wpack, self.bias = None, None, None
 
-    def weights(self):
-        # the bias too: without an epoch, PackBatch.run lets a pack with a shared bias re-read its address (after_pack) only when one of these moved
-        return (self.weight,) if self.bias_p is None else (self.weight, self.bias_p)
-
-    def key(self):
-        w = self.weight
-        return (w.data_ptr(), w._version, None if self.bias_p is None else (self.bias_p.data_ptr(), self.bias_p._version))
-
-    def stale(self):
-        return self.key() != self._key
-
-    def prepare(self):
-        if self.wpack is None:
-            w = self.weight
-            require_gpu(w, 'conv weight')
-            if self.transposed:                   # (K groups, M rows) of one slice
-                ncg_in, m = (w.shape[0] + 7) // 8, min(w.shape[1], 64)
-            else:
-                ncg_in, m = (1 if self.lat else 0) + (w.shape[1] - self.lat + 7) // 8, min(w.shape[0], 64)
-            per = _lib.lib.esr_conv_wpack_bytes(ncg_in, m, fmt_code(self.split))
-            self.wpack = torch.empty(len(self.parts) * per, dtype=torch.uint8, device=w.device)
-            for s, pk in enumerate(self.parts):
-                pk.wpack = self.wpack[s * per:(s + 1) * per]
-                pk.prepare()                      # (checks that its slice is as long as its pack)
-            bp = self.bias_p
-            if bp is not None and bp.dtype == torch.float32 and bp.is_contiguous():
-                self.bias, self._bias_shared = bp.detach(), True
-            else:
-                self.bias, self._bias_shared = torch.zeros(w.shape[0], dtype=torch.float32, device=w.device), False
-        return self
-
-    def jobs(self):
-        return [j for pk in self.parts for j in pk.jobs()]
-
-    @property
-    def needs_after_pack(self):
-        return not (self.bias_p is None or self._bias_shared)
-
-    def after_pack(self):
-        if self.bias_p is not None and not self._bias_shared:
-            self.bias.copy_(self.bias_p.detach().float())
-        if self._bias_shared and self.bias.data_ptr() != self.bias_p.data_ptr():
-            self.bias = self.bias_p.detach()
-        self._key = self.key()
-
-    def get(self):
-        if not self.stale():
-            return self
-        self.prepare()
-        run_pack_jobs(self.jobs(), self.split)
-        self.after_pack()
-        return self
+    def _build(self, dev):
+        cout, cin = self.weight.shape[0], self.weight.shape[1]
+        if self.transposed:
+            self._build_parts((cout + 7) // 8, min(cin, 64), dev)
+        else:
+            self._build_parts((1 if self.lat else 0) + (cin - self.lat + 7) // 8, min(cout, 64), dev)
+        self._bind_bias(cout, dev)
 
 
-class PackedConvPhases(PackedConvSlices):
+class PackedConvPhases(_PackedParts):
     """The forward weight of a conv behind a nearest x2 upsample, folded for the phase launch (esr_conv3x3_desc.upsample_phases = 2): per
     32-channel block c of the output two 64-row slices back to back — phases 0, 1 and phases 2, 3 of the block's rows, each M tile of a slice
     one phase (esr_pack_conv_weights, ESR_PACK_FOLD2).  The bias is indexed by channel and padded to whole blocks."""
 
     def __init__(self, weight, bias, split=True):
+        super().__init__(split, False, bias)
+        self.weight, self.lat, self.parts = weight, 0, []
         cout = weight.shape[0]
-        self.weight, self.bias_p, self.lat, self.split, self.transposed = weight, bias, 0, split, False
-        self.parts = []
         for c in range((cout + 31) // 32):
             rows = [m if m < cout else -1 for m in range(32 * c, 32 * c + 32)]
             self.parts += [PackedConv(weight, None, 0, split=split, rows=rows + rows, fold=p0) for p0 in (0, 2)]
-        self._key, self.wpack, self.bias = None, None, None
 
-    def prepare(self):
-        if self.wpack is None:
-            w = self.weight
-            require_gpu(w, 'conv weight')
-            per = _lib.lib.esr_conv_wpack_bytes((w.shape[1] + 7) // 8, 64, fmt_code(self.split))
-            self.wpack = torch.empty(len(self.parts) * per, dtype=torch.uint8, device=w.device)
-            for s, pk in enumerate(self.parts):
-                pk.wpack = self.wpack[s * per:(s + 1) * per]
-                pk.prepare()
-            bp, nb = self.bias_p, 32 * (len(self.parts) // 2)
-            if bp is not None and bp.dtype == torch.float32 and bp.is_contiguous() and bp.numel() == nb:
-                self.bias, self._bias_shared = bp.detach(), True
-            else:
-                self.bias, self._bias_shared = torch.zeros(nb, dtype=torch.float32, device=w.device), False
-        return self
-
-    def after_pack(self):
-        if self.bias_p is not None and not self._bias_shared:
-            self.bias[:self.bias_p.numel()].copy_(self.bias_p.detach().float())
-        if self._bias_shared and self.bias.data_ptr() != self.bias_p.data_ptr():
-            self.bias = self.bias_p.detach()
-        self._key = self.key()
+    def _build(self, dev):
+        self._build_parts((self.weight.shape[1] + 7) // 8, 64, dev)
+        self._bind_bias(32 * (len(self.parts) // 2), dev)
 
 
 def run_pack_jobs(jobs, split):
@@ -566,76 +541,45 @@ class PackBatch:
             self.n, self.nblocks = len(jobs), int(nb)
             self.pack_ids, self.wptrs, self.epoch, self.npacks = tuple(id(pk) for pk in packs), wptrs, epoch, len(packs)
             # packs with work of their own after the launch (a bias copy: permuted rows / a bias that is not the parameter itself)
-            self.post = [pk for pk in packs if getattr(pk, 'needs_after_pack', True)]
+            self.post = [pk for pk in packs if pk.needs_after_pack]
         check(_lib.lib.esr_pack_batch_run(self.ws.data_ptr(), self.n, self.nblocks, stream_ptr()), 'esr_pack_batch_run')
         for pk in (self.post if same else packs):      # after a rebuild every pack re-reads its parameter pointers (shared biases)
             pk.after_pack()
 
 
-class PackedSum:
+class PackedSum(_Pack):
     """Data-gradient pack whose K axis concatenates the output channels of SEVERAL conv layers: one launch then evaluates
     sum_i scale_i * conv_T(W_i)[rows] (dy_i) with the dy_i stored back to back in one gradient buffer — the backward of a dense
     block is itself a dense block (reference block.py:230-235 run backwards).  pieces: [(weight, scale)], K order = list order;
     rows: per piece, the indices into that weight's input-channel axis that form the M axis (same count for every piece)."""
 
     def __init__(self, pieces, rows, split=True):
-        self.pieces, self.rows, self.split = pieces, rows, split
-        self.transposed = True
-        self._key = None
-        self.wpack = None
-        self.bias = None
+        super().__init__(split, True)
+        self.pieces, self.rows = pieces, rows
 
     def weights(self):
         return tuple(w for w, _ in self.pieces)
 
-    def key(self):
-        return tuple((w.data_ptr(), w._version) for w, _ in self.pieces)
-
-    def stale(self):
-        return self.key() != self._key
-
-    def prepare(self):
-        if self.wpack is None:
-            dev = self.pieces[0][0].device
-            require_gpu(self.pieces[0][0], 'conv weight')
-            nrows = len(self.rows[0])
-            mt = (nrows + 31) // 32
-            self.mtiles, self.m_channels = mt, nrows
-            self.maps, g = [], 0
-            for (w, _), rows in zip(self.pieces, self.rows):
-                assert w.shape[0] % 16 == 0 and len(rows) == nrows
-                kmap = torch.arange(w.shape[0], dtype=torch.int32, device=dev)
-                mmap = torch.tensor(list(rows) + [-1] * (mt * 32 - nrows), dtype=torch.int32, device=dev)
-                self.maps.append((kmap, mmap, g))
-                g += w.shape[0] // 8
-            self.ncg_in = g
-            self.wpack = torch.empty(_lib.lib.esr_conv_wpack_bytes(g, mt * 32, fmt_code(self.split)), dtype=torch.uint8, device=dev)
-            self.bias = torch.zeros(mt * 32, dtype=torch.float32, device=dev)
-            self.chunk_bytes = _lib.lib.esr_conv_wpack_bytes(2, mt * 32, fmt_code(self.split))
-        return self
+    def _build(self, dev):
+        nrows = len(self.rows[0])
+        mt = (nrows + 31) // 32
+        self.mtiles, self.m_channels = mt, nrows
+        self.maps, g = [], 0
+        for (w, _), rows in zip(self.pieces, self.rows):
+            assert w.shape[0] % 16 == 0 and len(rows) == nrows
+            kmap = torch.arange(w.shape[0], dtype=torch.int32, device=dev)
+            mmap = torch.tensor(list(rows) + [-1] * (mt * 32 - nrows), dtype=torch.int32, device=dev)
+            self.maps.append((kmap, mmap, g))
+            g += w.shape[0] // 8
+        self.ncg_in = g
+        self.wpack = torch.empty(_lib.lib.esr_conv_wpack_bytes(g, mt * 32, fmt_code(self.split)), dtype=torch.uint8, device=dev)
+        self._bind_bias(mt * 32, dev)             # (no bias: the zero block)
+        self.chunk_bytes = _lib.lib.esr_conv_wpack_bytes(2, mt * 32, fmt_code(self.split))
 
     def jobs(self):
-        out, self._wd = [], []
-        for (w, scale), (kmap, mmap, g0) in zip(self.pieces, self.maps):
-            wd = w.detach()
-            if wd.dtype != torch.float32 or not wd.is_contiguous():
-                wd = wd.float().contiguous()
-            self._wd.append(wd)
-            out.append((wd, kmap, wd.shape[0] // 8, mmap, self.mtiles, 1, scale, self.wpack.data_ptr() + (g0 // 2) * self.chunk_bytes))
-        return out
-
-    needs_after_pack = False
-
-    def after_pack(self):
-        self._key = self.key()
-
-    def get(self):
-        if not self.stale():
-            return self
-        self.prepare()
-        run_pack_jobs(self.jobs(), self.split)
-        self.after_pack()
-        return self
+        self._wd = [_fp32(w) for w, _ in self.pieces]       # keeps converted copies alive until the pack has run
+        return [(wd, kmap, wd.shape[0] // 8, mmap, self.mtiles, 1, scale, self.wpack.data_ptr() + (g0 // 2) * self.chunk_bytes)
+                for wd, (_, scale), (kmap, mmap, g0) in zip(self._wd, self.pieces, self.maps)]
 
 
 _launch_parity = 0
@@ -807,6 +751,21 @@ def unpack_grad_nchw(G, dst, C_, h, w, c0, nc, pad=0, down=1, accumulate=False, 
                                         1 if accumulate else 0, stream_ptr()), 'esr_unpack_grad_nchw')
 
 
+def conv3x3_nchw_parts(parts, in1, B, H, W, out, **kw):
+    """The fp32 NCHW tensor `out` from packs of up to 64 rows each, which together hold its channels in order: one conv3x3() launch per
+    pack (the kernel produces up to 64 channels per launch, and output slices of ONE launch exist for the activation layout only), each
+    but a lone one into a tensor of its own, copied into place."""
+    m0 = 0
+    for pc in parts:
+        mc = pc.m_channels
+        tmp = out if mc == out.shape[1] else torch.empty(B, mc, H, W, dtype=torch.float32, device=out.device)
+        conv3x3(pc, in1, B, H, W, mc, out_nchw=tmp, **kw)
+        if tmp is not out:
+            out[:, m0:m0 + mc] = tmp
+        m0 += mc
+    return out
+
+
 def conv3x3_nchw(x, weight, bias, act_slope=1.0, split=True):
     """Stand-alone conv3x3 on fp32 NCHW tensors (pack -> MFMA conv -> fp32 NCHW).  Used by block-level calls and tests; the
     whole-generator path keeps activations in the kernels' layout instead (engine.py)."""
@@ -819,18 +778,11 @@ def conv3x3_nchw(x, weight, bias, act_slope=1.0, split=True):
     ncg = (Cin + 7) // 8
     src = ActBuf(B, ncg, H, W, x.device, split)
     pack_nchw(x, src.view(), 0, Cin)
-    out = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-    if cout <= 64:
-        pc = PackedConv(weight, bias, 0, split=split).get()
-        conv3x3(pc, src.view(), B, H, W, cout, act_slope=act_slope, out_nchw=out)
-        return out
-    for m0 in range(0, cout, 64):      # the kernel produces up to 64 output channels per launch
-        mc = min(64, cout - m0)
-        sub = PackedConv(weight.detach()[m0:m0 + mc].contiguous(), None if bias is None else bias.detach()[m0:m0 + mc].contiguous(), 0, split=split).get()
-        tmp = torch.empty(B, mc, H, W, dtype=torch.float32, device=x.device)
-        conv3x3(sub, src.view(), B, H, W, mc, act_slope=act_slope, out_nchw=tmp)
-        out[:, m0:m0 + mc] = tmp
-    return out
+    # any cout: contiguous copies of 64-row slices of the weight and the bias, the last one as short as it comes (a PackedConvSlices takes
+    # whole slices only); up to 64 channels the slice is the tensor itself
+    parts = [PackedConv(weight.detach()[m0:m0 + 64].contiguous(), None if bias is None else bias.detach()[m0:m0 + 64].contiguous(), 0, split=split).get()
+             for m0 in range(0, cout, 64)]
+    return conv3x3_nchw_parts(parts, src.view(), B, H, W, torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device), act_slope=act_slope)
 
 
 def conv3x3_dgrad_nchw(dy, weight, split=True):
@@ -843,15 +795,8 @@ def conv3x3_dgrad_nchw(dy, weight, split=True):
     assert weight.shape[0] == Cout
     src = ActBuf(B, (Cout + 7) // 8, H, W, dy.device, split)
     pack_nchw(dy, src.view(), 0, Cout)
-    dx = torch.empty(B, cin, H, W, dtype=torch.float32, device=dy.device)
-    for lo in range(0, cin, 64):
-        hi = min(cin, lo + 64)
-        pc = PackedConv(weight, None, 0, split=split, transposed=True, m_slice=(lo, hi)).get()
-        tmp = dx if (lo == 0 and hi == cin) else torch.empty(B, hi - lo, H, W, dtype=torch.float32, device=dy.device)
-        conv3x3(pc, src.view(), B, H, W, hi - lo, out_nchw=tmp, use_bias=False)
-        if tmp is not dx:
-            dx[:, lo:hi] = tmp
-    return dx
+    parts = [PackedConv(weight, None, 0, split=split, transposed=True, m_slice=(lo, min(cin, lo + 64))).get() for lo in range(0, cin, 64)]
+    return conv3x3_nchw_parts(parts, src.view(), B, H, W, torch.empty(B, cin, H, W, dtype=torch.float32, device=dy.device), use_bias=False)
 
 
 def wgrad_desc(dy, x_main, x_lat, lat, wshape, B, H, W, alpha, upsample, device, out=None, tap_masks=None):

@@ -163,14 +163,10 @@ class DnCNNEngine:
                 if ly.cout <= 64:
                     A.conv3x3(ly.fwd, view_of(t), B, h, w, ly.cout, out_nchw=y, act_slope=1.0, use_bias=ly.b is not None, reverse=False)
                     break
-                # more than 64 output channels (the chroma generator's 128): an fp32 NCHW store covers one 64-row slice of the pack per
-                # launch (esr_conv3x3: output slices exist for the activation layout only), each into its own tensor, copied into place
+                # more than 64 output channels (the chroma generator's 128): one launch per 64-row slice of the pack; the slices carry no bias
                 if ly.b is not None:
                     raise EsrError('DnCNN: a last conv of %d > 64 channels with a bias' % ly.cout)
-                for s, part in enumerate(ly.fwd.parts):
-                    ys = torch.empty(B, 64, h, w, dtype=torch.float32, device=dev)
-                    A.conv3x3(part, view_of(t), B, h, w, 64, out_nchw=ys, act_slope=1.0, use_bias=False, reverse=False)
-                    y[:, 64 * s:64 * (s + 1)] = ys
+                A.conv3x3_nchw_parts(ly.fwd.parts, view_of(t), B, h, w, y, act_slope=1.0, use_bias=False, reverse=False)
                 break
             nxt = self.layers[k + 1]
             zg = nxt.lat // 8

@@ -41,7 +41,8 @@ def test_pack_unpack_roundtrip():
 
 
 @pytest.mark.parametrize('cin,cout,H,W,slope', [(3, 64, 12, 16, 1.0), (64, 32, 17, 23, 0.2), (67, 32, 9, 40, 0.2), (192, 64, 33, 21, 1.0),
-                                                (64, 3, 40, 37, 1.0), (96, 128, 10, 10, 0.2)])
+                                                (64, 3, 40, 37, 1.0), (96, 128, 10, 10, 0.2),
+                                                (32, 96, 11, 13, 0.2), (40, 72, 9, 10, 1.0)])     # a short last slice: 32 rows, 8 rows
 def test_conv3x3_matches_torch_cpu(cin, cout, H, W, slope):
     from esr_hip import act as A
     x = seeded_uniform((2, cin, H, W), cin + cout, -1.0, 1.0)

@@ -349,3 +349,184 @@ def test_sliced_packs_of_every_engine_are_their_slices_packed_alone(precision):
         assert isinstance(pk, A.PackedConvSlices), name
         want = alone(pk)
         assert pk.wpack.shape == want.shape and torch.equal(pk.wpack, want), (name, int((pk.wpack != want).sum()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the bias side of the weight packs (pack only, no conv launch): what the kernel will read through pack.bias
+
+def _w(co, ci):
+    return torch.randn(co, ci, 3, 3, device='cuda')
+
+
+def _b(n, dtype=torch.float32):
+    return torch.randn(n, device='cuda', dtype=dtype)
+
+
+def _repacker(A, packs, route):
+    """One re-pack of every pack: stand-alone (get) or through ONE PackBatch without an epoch."""
+    if route == 'get':
+        return lambda: [pk.get() for pk in packs]
+    batch = A.PackBatch()
+    return lambda: batch.run(packs)
+
+
+@pytest.mark.parametrize('route', ['get', 'batch'])
+def test_shared_bias_follows_the_parameter_into_a_new_storage(route):
+    """An fp32 contiguous bias of exactly the length the launch reads is read in place; when the parameter's storage is replaced the pack
+    re-reads the address at the next re-pack — through PackBatch.run without an epoch too, which sees the move only because weights()
+    names the bias."""
+    from esr_hip import act as A
+    torch.manual_seed(11)
+    packs = [A.PackedConv(_w(32, 8), _b(32), 0), A.PackedConv(_w(64, 16), _b(64), 0), A.PackedConvSlices(_w(128, 8), _b(128)),
+             A.PackedConvPhases(_w(64, 16), _b(64))]
+    repack = _repacker(A, packs, route)
+    repack()
+    for pk in packs:
+        assert pk.bias.data_ptr() == pk.bias_p.data_ptr() and not pk.needs_after_pack, type(pk).__name__
+    old = [pk.bias_p.data for pk in packs]                # (kept alive: the new storages cannot land on the old addresses)
+    for pk in packs:
+        pk.bias_p.data = pk.bias_p.data.clone()
+    assert all(pk.bias_p.data_ptr() != o.data_ptr() for pk, o in zip(packs, old))
+    repack()
+    for pk in packs:
+        assert pk.bias.data_ptr() == pk.bias_p.data_ptr(), type(pk).__name__
+
+
+@pytest.mark.parametrize('route', ['get', 'batch'])
+def test_private_bias_is_a_zero_padded_copy_refreshed_by_every_repack(route):
+    """Ragged channel counts (padded to whole M tiles / 32-channel blocks, the tail zero), permuted rows (bias[i] = parameter[rows[i]]) and a
+    bias that is not fp32 get a copy of their own, which holds the parameter's values after every re-pack."""
+    from esr_hip import act as A
+    torch.manual_seed(12)
+    perm = [int(i) for i in torch.randperm(64)]
+    packs = [A.PackedConv(_w(40, 8), _b(40), 0), A.PackedConv(_w(64, 16), _b(64), 0, rows=perm), A.PackedConvPhases(_w(48, 16), _b(48)),
+             A.PackedConv(_w(32, 8), _b(32, torch.float64), 0)]
+    sizes = [64, 64, 64, 32]
+
+    def want(pk, n):
+        src = pk.bias_p.float()
+        if getattr(pk, 'rows', None) is not None:
+            src = src[torch.tensor(pk.rows, device='cuda')]
+        return torch.cat([src, torch.zeros(n - src.numel(), device='cuda')])
+
+    repack = _repacker(A, packs, route)
+    for step in range(3):                                 # the first pack and two refreshes
+        repack()
+        for pk, n in zip(packs, sizes):
+            assert pk.needs_after_pack and pk.bias.data_ptr() != pk.bias_p.data_ptr(), type(pk).__name__
+            assert pk.bias.dtype == torch.float32 and pk.bias.numel() == n and torch.equal(pk.bias, want(pk, n)), (step, type(pk).__name__)
+        for pk in packs:
+            pk.bias_p.add_(1)
+
+
+def test_transposed_packs_ignore_their_bias():
+    """A data-gradient pack carries no bias: a bias-only update leaves it current, and the batched re-pack owes it no work of its own."""
+    from esr_hip import act as A
+    torch.manual_seed(13)
+    for cls, kw in ((A.PackedConv, dict(lat=0)), (A.PackedConvSlices, {})):
+        bias = _b(32)
+        pk = cls(_w(32, 16), bias, transposed=True, **kw).get()
+        assert not pk.stale() and pk.needs_after_pack is False
+        bias.add_(1)
+        assert not pk.stale() and pk.needs_after_pack is False, cls.__name__
+        assert all(w is pk.weight for w in pk.weights())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the launch wrappers whose recorded form no engine pass executes: issued directly against recorded + replayed
+
+def _filled(A, ncg, H, W, split, seed):
+    """ActBuf [1][ncg][H+2][W+2][8] with a random interior (hi + residue in lo), zero border."""
+    buf = A.ActBuf(1, ncg, H, W, 'cuda', split)
+    dt = torch.float16 if buf.fmt else torch.bfloat16
+    v = torch.rand(1, ncg, H, W, 8, generator=torch.Generator().manual_seed(seed)) * 2 - 1
+    hi = v.to(dt)
+    buf.hi[:, :, 1:-1, 1:-1] = hi.view(torch.int16).cuda()
+    if buf.lo is not None:
+        buf.lo[:, :, 1:-1, 1:-1] = (v - hi.float()).to(dt).view(torch.int16).cuda()
+    return buf
+
+
+def _planes(*bufs):
+    return [p for b in bufs for p in (b.hi, b.lo) if p is not None]
+
+
+def _direct_and_replayed(make, n_cmds):
+    """make() -> (call, tensors it writes, externals): the call issued directly on one fresh state, recorded (which must launch nothing) and
+    replayed on another; returns both results."""
+    from esr_hip import act as A
+    call, outs, _ = make()
+    call()
+    direct = [t.clone() for t in outs]
+    call, outs, ext = make()
+    before = [t.clone() for t in outs]
+    rec = A.Recorder(ext)
+    with A.recording(rec):
+        call()
+    assert all(torch.equal(a, b) for a, b in zip(before, outs)), 'a recorded call launched'
+    plan = rec.finish()
+    assert plan.n_cmds == n_cmds
+    plan.run(ext)
+    return direct, [t.clone() for t in outs]
+
+
+def _assert_same(direct, replayed):
+    assert len(direct) == len(replayed) > 0
+    for i, (a, b) in enumerate(zip(direct, replayed)):
+        assert torch.equal(a, b), i
+
+
+@pytest.mark.parametrize('hasA,hasB,s,mask', [(True, False, 1, False), (False, True, 2, False), (True, True, 2, True), (False, False, 1, True)])
+def test_act_combine_recorded_is_the_direct_call(hasA, hasB, s, mask):
+    from esr_hip import act as A
+
+    def make():
+        out = _filled(A, 1, 4, 6, True, 20)               # (what a missing operand would leave: must be overwritten the same way)
+        a = _filled(A, 1, 4, 6, True, 21) if hasA else None
+        bv = _filled(A, 1, 4 * s, 6 * s, True, 22) if hasB else None
+        m = _filled(A, 1, 4, 6, False, 23) if mask else None
+        v = lambda buf: None if buf is None else buf.view()         # (the closure keeps the buffers alive: a view is raw pointers)
+        return (lambda: A.act_combine(out.view(), 1, A_=v(a), alpha=0.75, Bv=v(bv), beta=-1.5, s=s, mask=v(m), mask_slope=0.2)), _planes(out), {}
+    _assert_same(*_direct_and_replayed(make, 1))
+
+
+def test_pixel_unshuffle_recorded_is_the_direct_call():
+    from esr_hip import act as A
+
+    def make():
+        src, dst = _filled(A, 1, 4, 6, True, 30), A.ActBuf(1, 4, 2, 3, 'cuda', True)
+        return (lambda: A.pixel_unshuffle(src.view(), 2, dst.view(), 1)), _planes(dst), {}
+    direct, replayed = _direct_and_replayed(make, 1)
+    _assert_same(direct, replayed)
+    assert int(direct[0].ne(0).sum()) > 0
+
+
+def test_grad_scaler_recorded_is_the_direct_calls():
+    """rescale() (one absmax + one scale per view) and rescaled_copy(): the gradient buffers, the copy, the slot and the scale chain."""
+    from esr_hip import act as A
+
+    def make():
+        g0, g1, src, dst = (_filled(A, 1, 4, 6, 'f16x2', 40 + i) for i in range(4))
+        gs = A.GradScaler('cuda', torch.tensor(0.5, device='cuda'))
+        then = gs.current
+
+        def call():
+            gs.rescale(1, [g0.view(), g1.view()], 10)
+            gs.rescaled_copy(1, src.view(), dst.view(), then)
+        return call, _planes(g0, g1, dst) + [gs.slots, gs.scales], {}
+    direct, replayed = _direct_and_replayed(make, 4)
+    _assert_same(direct, replayed)
+    assert float(direct[-1][1]) != 1.0                    # the scale moved: max|g0| < 1 brought up to [2^9, 2^10)
+
+
+@pytest.mark.parametrize('accumulate', [False, True])
+def test_unpack_grad_nchw_recorded_is_the_direct_call(accumulate):
+    from esr_hip import act as A
+
+    def make():
+        G = _filled(A, 1, 4, 6, True, 50)
+        dst = seeded_uniform((1, 8, 4, 6), 51).cuda()
+        return (lambda: A.unpack_grad_nchw(G.view(), dst, 8, 4, 6, 0, 8, accumulate=accumulate)), [dst], {'dst': dst}
+    direct, replayed = _direct_and_replayed(make, 1)
+    _assert_same(direct, replayed)
+    assert not torch.equal(direct[0], seeded_uniform((1, 8, 4, 6), 51).cuda())

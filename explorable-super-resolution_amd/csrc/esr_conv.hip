@@ -953,6 +953,8 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackEntry
 }
 
 struct TileCfg { int TH, TW, P, NPIX_T, NPIX_L, tiles_x, tiles_y; size_t lds; };
+// bytes of one LDS stage: a chunk's activation tile (2 channel groups x npl planes of npix_l pixel vectors) and its 9 x mt x npw weight fragments
+constexpr size_t stage_bytes(int npl, int npix_l, int mt, int npw) { return (size_t)2 * npl * npix_l * 16 + (size_t)9 * mt * npw * 1024; }
 
 // Choose (TH, TW): minimise the number of workgroup tiles (every wave always runs R column tiles per tile) plus a small
 // halo-traffic term, under the LDS budget that keeps `nwg` workgroups resident per CU.
@@ -987,7 +989,7 @@ TileCfg pick_tile_search(int H, int W, int npl, int mt, int nwg) {
             int npix_l = max_px + 2 * P + 2;
             if (npix_l < npix_t) npix_l = npix_t;
             if (npix_l > MAXS * NW * 64) continue;
-            const size_t lds = nwg * ((size_t)2 * npl * npix_l * 16 + (size_t)9 * mt * npl * 1024);
+            const size_t lds = nwg * stage_bytes(npl, npix_l, mt, npl);
             if (lds > budget) continue;
             const int nty = (H + TH - 1) / TH;
             const double halo = (double)(TH + 2) * P / ((double)TH * TW);
@@ -1036,72 +1038,72 @@ void dma_share_host(int npl, int nwi, int nslots, unsigned (&out)[NW]) {
     }
 }
 
-template <int NPL, int MT, int EPI, int NST, int FMT, int NPW, bool PARTLO, int TMODE = 0>
-int launch_nst(const ConvArgs& a, hipStream_t s) {
-    void (*k)(const ConvArgs) = conv3x3_tile_kernel<NPL, MT, EPI, NST, FMT, NPW, PARTLO, TMODE>;
-    ESR_ALLOW_160K_LDS(k);
-    const int nslices = a.wslice ? a.nslices : 1;
-    const size_t stage = (size_t)2 * NPL * a.NPIX_L * 16 + (size_t)9 * MT * NPW * 1024;
-    const size_t lds = (NST == 1 ? 1 : (NST == 4 ? 4 : 2)) * stage;
-    ESR_CLEAR_ERR();
-    const dim3 grid = TMODE == 3 ? dim3(a.ntiles * nslices) : dim3(a.ntiles, nslices, a.ksplit > 1 ? a.ksplit : 1);
-    hipLaunchKernelGGL(k, grid, dim3(NTHREADS), lds, s, a);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
-}
+// no more workgroups than CUs (+25 %): every workgroup of such a launch is alone on its CU, so it pipelines its own DMA through two or four LDS
+// stages (conv_plan); the same bound decides the two-slice form of a 64-channel layer (conv_plan_shape) and the split-K factor
+constexpr int CONV_SMALL_WGS = 320;
 
-template <int NPL, int MT, int EPI, int FMT, int NPW, bool PARTLO, int TMODE = 0>
-int launch(const ConvArgs& a, hipStream_t s) {
-    // no more tiles than CUs (+25 %): every workgroup is alone on its CU, so it pipelines its own DMA (two stages fit: the tile
-    // geometry is chosen for two resident single-stage workgroups)
-    const int ntiles = a.tiles_x * a.tiles_y * a.B * (a.wslice ? a.nslices : 1) * (a.ksplit > 1 ? a.ksplit : 1);
-    const int force = a.stages_hint;                 // esr_conv3x3_desc.lds_stages: 0 = by launch size, 1 / 2 = that form
-    const bool small = ntiles <= 320;
-    // few small tiles, long K: the four-stage ring where it fits (plain bf16 kernels — what the critic's deep layers launch)
-    if constexpr ((EPI == 0 || EPI == EPI_NCHW) && !PARTLO && FMT == 0 && MT == 2 && TMODE != 3) {
-        const size_t stage = (size_t)2 * NPL * a.NPIX_L * 16 + (size_t)9 * MT * NPW * 1024;
-        if (!force && small && a.ncp >= (EPI == EPI_NCHW ? 8 : 16) && 4 * stage <= 160 * 1024) return launch_nst<NPL, MT, EPI, 4, FMT, NPW, PARTLO, TMODE>(a, s);
-    }
-    // the tap-masked kernels with hi+lo operands (four / two copies of the chunk body with their own tap sets) do not fit the 256 registers of
-    // the two-workgroups-per-CU form — they spilled 34-168 VGPRs to scratch: always the two-stage form (one workgroup per CU, 512 registers)
-    // (the phase launch, TMODE 3, has one copy of the body: both forms)
-    if constexpr ((TMODE == 1 || TMODE == 2) && NPL == 2) return launch_nst<NPL, MT, EPI, 2, FMT, NPW, PARTLO, TMODE>(a, s);
-    else {
-        const bool two = force ? force == 2 : small;
-        return two ? launch_nst<NPL, MT, EPI, 2, FMT, NPW, PARTLO, TMODE>(a, s) : launch_nst<NPL, MT, EPI, 1, FMT, NPW, PARTLO, TMODE>(a, s);
-    }
-}
+// Everything esr_conv3x3 decides about a launch, as plain host arithmetic (conv_plan): the kernel instantiation, its grid and LDS, and what
+// conv_args needs to fill the kernel arguments.  The first block is the shape part (conv_plan_shape), all that esr_conv3x3_tiling reports.
+struct ConvPlan {
+    bool phases, mslice;            // the phase launch (upsample_phases = 2); a 64-channel layer run as two 32-channel slices
+    int npl, ps, nslices, mt;       // activation planes, pixel-shuffle factor (0: plain store), output slices and M tiles of the layer as it is packed
+    int mt_k, kslices;              // M tiles per workgroup of the kernel that runs (1 with mslice) and the slices it steps through (ConvArgs.nslices)
+    TileCfg tile;
+    int ups, fmt, wpl;              // input upsample factor, element format (0 bf16, 1 f16), weight planes
+    bool partlo;                    // some operand or the destination has no lo plane (fp16 formats)
+    int in0g, ncp, lo_chunks;       // in0's channel groups, K chunks of the whole input, and how many leading ones carry a lo plane
+    int tmode, epi, nst, S;         // the kernel's tap mode, epilogue bits and LDS stages; split-K sets of workgroups (1: none)
+    int resin_g0;                   // EPI_RESIN: see ConvArgs
+    float resin_scale;
+    dim3 grid;
+    size_t lds;
+};
+
+// ---- which conv3x3_tile_kernel<NPL, MT, EPI, NST, FMT, NPW, PARTLO, TMODE> exist: written here once, for conv_plan (which chooses among them)
+// and conv_kernel (which instantiates exactly these)
+template <int... V> struct Ints {};
+template <int... V> constexpr bool among(Ints<V...>, int v) { return ((v == V) || ...); }
 
 // the epilogue combinations the RRDB forward / backward plans use
-template <int NPL, int MT, int FMT, int NPW, bool PARTLO = false>
-int launch_epi(const ConvArgs& a, int epi, hipStream_t s) {
-    if (FMT == 1) {              // f16: the inference forward and the data gradient of 'mixed' (EPI_MASK)
-        switch (epi) {
-            case EPI_MASK: return launch<NPL, MT, EPI_MASK, FMT, NPW, PARTLO>(a, s);
-            case 0: return launch<NPL, MT, 0, FMT, NPW, PARTLO>(a, s);
-            case EPI_RES1: return launch<NPL, MT, EPI_RES1, FMT, NPW, PARTLO>(a, s);
-            case EPI_RES1 | EPI_RES2: return launch<NPL, MT, EPI_RES1 | EPI_RES2, FMT, NPW, PARTLO>(a, s);
-            case EPI_RESIN: return launch<NPL, MT, EPI_RESIN, FMT, NPW, PARTLO>(a, s);
-            case EPI_RESIN | EPI_RES2: return launch<NPL, MT, EPI_RESIN | EPI_RES2, FMT, NPW, PARTLO>(a, s);
-            case EPI_NCHW: return launch<NPL, MT, EPI_NCHW, FMT, NPW, PARTLO>(a, s);
-            case EPI_OUT2: return launch<NPL, MT, EPI_OUT2, FMT, NPW, PARTLO>(a, s);
-            case EPI_PS: return launch<NPL, MT, EPI_PS, FMT, NPW, PARTLO>(a, s);
-            default: return ESR_E_UNSUPPORTED;
-        }
-    }
-    switch (epi) {
-        case 0: return launch<NPL, MT, 0, FMT, NPW, PARTLO>(a, s);
-        case EPI_RES1: return launch<NPL, MT, EPI_RES1, FMT, NPW, PARTLO>(a, s);
-        case EPI_RES1 | EPI_RES2: return launch<NPL, MT, EPI_RES1 | EPI_RES2, FMT, NPW, PARTLO>(a, s);
-        case EPI_RESIN: return launch<NPL, MT, EPI_RESIN, FMT, NPW, PARTLO>(a, s);
-        case EPI_RESIN | EPI_RES2: return launch<NPL, MT, EPI_RESIN | EPI_RES2, FMT, NPW, PARTLO>(a, s);
-        case EPI_NCHW: return launch<NPL, MT, EPI_NCHW, FMT, NPW, PARTLO>(a, s);
-        case EPI_OUT2: return launch<NPL, MT, EPI_OUT2, FMT, NPW, PARTLO>(a, s);
-        case EPI_RES1 | EPI_MASK: return launch<NPL, MT, EPI_RES1 | EPI_MASK, FMT, NPW, PARTLO>(a, s);
-        case EPI_MASK: return launch<NPL, MT, EPI_MASK, FMT, NPW, PARTLO>(a, s);
-        case EPI_PS: return launch<NPL, MT, EPI_PS, FMT, NPW, PARTLO>(a, s);
-        default: return ESR_E_UNSUPPORTED;
-    }
+typedef Ints<0, EPI_RES1, EPI_RES1 | EPI_RES2, EPI_RESIN, EPI_RESIN | EPI_RES2, EPI_NCHW, EPI_OUT2, EPI_RES1 | EPI_MASK, EPI_MASK, EPI_PS> ConvEpis;
+// few small tiles, long K: the four-stage ring where it fits (plain bf16 kernels — what the critic's deep layers launch)
+constexpr bool has_ring4(int mt, int epi, int fmt, bool partlo, int tmode) { return (epi == 0 || epi == EPI_NCHW) && !partlo && fmt == 0 && mt == 2 && tmode != 3; }
+// the tap-masked kernels with hi+lo operands (four / two copies of the chunk body with their own tap sets) do not fit the 256 registers of
+// the two-workgroups-per-CU form — they spilled 34-168 VGPRs to scratch: always the two-stage form (one workgroup per CU, 512 registers)
+// (the phase launch, TMODE 3, has one copy of the body: both forms)
+constexpr bool two_stages_only(int npl, int tmode) { return (tmode == 1 || tmode == 2) && npl == 2; }
+
+constexpr bool conv_kernel_exists(int npl, int mt, int epi, int nst, int fmt, int npw, bool partlo, int tmode) {
+    // operands: bf16 weights have the activations' planes; f16 hi+lo activations take one or two weight planes, and may lack lo planes in part
+    if (fmt == 0 ? (npw != npl || partlo) : (npw > npl || (partlo && npl == 1))) return false;
+    if (nst == 4 ? !has_ring4(mt, epi, fmt, partlo, tmode) : (nst == 1 && two_stages_only(npl, tmode))) return false;
+    // all taps: every epilogue in every format, 32 and 64 channels per workgroup (conv_plan refuses RES1 | MASK for f16; its kernels are built)
+    if (tmode == 0) return among(ConvEpis{}, epi);
+    // the critic's tap-masked convs: plain bf16 launches, stored directly or as split-K slabs (EPI_NCHW); the phase launch: every format, plain store
+    if (mt != 2 || partlo) return false;
+    return tmode == 3 ? epi == 0 : (fmt == 0 && (epi == 0 || epi == EPI_NCHW));
+}
+
+// the instantiation a plan names, its dynamic-LDS limit raised to 160 KiB on the current device; nullptr if there is none.  conv_pick takes one
+// value list per template parameter still open and descends into the entry that equals *v.
+typedef void (*ConvKernel)(const ConvArgs);
+template <int NPL, int MT, int EPI, int NST, int FMT, int NPW, int PARTLO, int TMODE>
+ConvKernel conv_pick(Ints<NPL, MT, EPI, NST, FMT, NPW, PARTLO, TMODE>, const int*) {
+    if constexpr (conv_kernel_exists(NPL, MT, EPI, NST, FMT, NPW, PARTLO != 0, TMODE)) {
+        ConvKernel k = conv3x3_tile_kernel<NPL, MT, EPI, NST, FMT, NPW, PARTLO != 0, TMODE>;
+        ESR_ALLOW_160K_LDS(k);
+        return k;
+    } else return nullptr;
+}
+template <int... C, int... V, class... More>
+ConvKernel conv_pick(Ints<C...>, const int* v, Ints<V...>, More... more) {
+    ConvKernel k = nullptr;
+    ((*v == V ? void(k = conv_pick(Ints<C..., V>{}, v + 1, more...)) : void()), ...);
+    return k;
+}
+ConvKernel conv_kernel(const ConvPlan& p) {
+    const int v[8] = {p.npl, p.mt_k, p.epi, p.nst, p.fmt, p.wpl, p.partlo, p.tmode};
+    return conv_pick(Ints<>{}, v, Ints<1, 2>{}, Ints<1, 2>{}, ConvEpis{}, Ints<1, 2, 4>{}, Ints<0, 1>{}, Ints<1, 2>{}, Ints<0, 1>{}, Ints<0, 1, 2, 3>{});
 }
 
 // split K, second launch: out = sum of the S fp32 partial slabs (fixed order: the result does not depend on scheduling), stored as bf16 hi [+ lo]
@@ -1199,40 +1201,15 @@ extern "C" int esr_pack_batch_run(const void* workspace, int n, int64_t nblocks,
     return ESR_OK;
 }
 
-// The kernel form a launch runs and its tile geometry (esr_conv3x3, esr_conv3x3_tiling).
-// A 64-channel layer whose launch would leave every workgroup alone on its CU (no more tiles than CUs: the 52 x 52 training crops, a single
-// image of the Z search) runs as TWO 32-channel output slices of the MT = 1 kernel instead (mslice; grid y; same pack, ConvArgs.wtap): twice the
-// workgroups, so that two are resident per CU and cover each other's copy issue and waits — at the price of staging the input tile twice
-// (the second copy comes out of the same XCD's L2).  Same arithmetic per output channel: results are bit-identical to the 64-channel form.
-static TileCfg conv_tiling(const esr_conv3x3_desc* d, int npl, int mt, int nslices, int ps, bool& mslice) {
-    mslice = false;
-    auto all_taps = [](const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); };
-    if (nslices == 1 && mt == 2 && d->cout == 64 && !d->out_nchw && !ps && d->upsample_phases != 2 && d->lds_stages == 0 && !d->k_split_ws && all_taps(d->tap_mask_k) &&
-        all_taps(d->tap_mask_m) && (!d->mask_src.hi || (d->mask_cg0 == 0 && d->mask_cg1 >= 8))) {
-        const TileCfg t2 = pick_tile(d->H, d->W, npl, 2, WGS_MT2);
-        mslice = t2.TH != 0 && (long long)t2.tiles_x * t2.tiles_y * d->B <= 320;
-    }
-    const int mt_k = mslice ? 1 : mt;
-    return pick_tile(d->H, d->W, npl, mt_k, mt_k == 1 ? WGS_MT1 : WGS_MT2);
-}
+// ---- esr_conv3x3 = conv_validate -> conv_plan -> conv_args -> conv_launch; esr_conv3x3_tiling answers from the shape part of the same plan
 
-extern "C" int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling) {
-    if (!d || !tiling || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return ESR_E_ARG;
-    const bool phases = d->upsample_phases == 2;       // two slices (phase rows) of two M tiles (phase columns) per 32-channel block
-    if (!phases && d->cout > 64 && d->cout % 64) return ESR_E_UNSUPPORTED;
-    const int nslices = phases ? 2 * ((d->cout + 31) / 32) : (d->cout > 64 ? d->cout / 64 : 1);
-    const int mt = nslices > 1 ? 2 : (d->cout + 31) / 32;
-    bool mslice = false;
-    const TileCfg t = conv_tiling(d, d->in1.lo ? 2 : 1, mt, nslices, d->pixel_shuffle > 1 ? d->pixel_shuffle : 0, mslice);
-    if (t.TH == 0) return ESR_E_UNSUPPORTED;
-    tiling[0] = t.tiles_x;
-    tiling[1] = t.tiles_y;
-    tiling[2] = mslice ? 1 : mt;
-    tiling[3] = mslice ? 2 : nslices;
-    return ESR_OK;
-}
+// tap masks are a HINT (blocks outside them must be zero in the pack): the two patterns with compiled kernels are honoured, anything
+// else multiplies all nine taps — the same result
+static bool all_taps(const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); }
+static bool same_taps(const int32_t (&m)[4], const int (&p)[4]) { return m[0] == p[0] && m[1] == p[1] && m[2] == p[2] && m[3] == p[3]; }
 
-extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
+// The argument and shape checks that need nothing the plan decides.
+static int conv_validate(const esr_conv3x3_desc* d) {
     if (!d || !d->in1.hi || !d->wpack || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return ESR_E_ARG;
     if (!d->out.hi && !d->out_nchw) return ESR_E_ARG;
     const int ups = d->upsample <= 0 ? 1 : d->upsample;
@@ -1250,7 +1227,6 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     if (d->in1.H * ups != d->H || d->in1.W * ups != d->W) return ESR_E_ARG;
     if (d->in0.hi && (d->in0.H != d->H || d->in0.W != d->W)) return ESR_E_ARG;
     const bool split = d->in1.lo != nullptr;
-    const bool f16 = d->in1.fmt == ESR_FMT_F16;
     // one element format per launch
     if ((d->in0.hi && d->in0.fmt != d->in1.fmt) || (d->out.hi && d->out.fmt != d->in1.fmt) || (d->out2.hi && d->out2.fmt != d->in1.fmt) ||
         (d->res1.hi && d->res1.fmt != d->in1.fmt) || (d->res2.hi && d->res2.fmt != d->in1.fmt))
@@ -1259,202 +1235,216 @@ extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
     // cout > 64: output slices of 64 channels in ONE launch (grid y); the caller packs the weights of slice s (rows 64 s .. 64 s + 63) as a
     // 64-row pack at byte offset s * esr_conv_wpack_bytes(groups, 64, fmt) of `wpack`; bias, out, out2, res1, res2 and mask_src are
     // indexed by absolute output channel
-    const int nslices = phases ? 2 * ((d->cout + 31) / 32) : (d->cout > 64 ? d->cout / 64 : 1);
     if (!phases && d->cout > 64 && (d->cout % 64 || d->out_nchw || d->pixel_shuffle > 1 || !d->out.hi)) return ESR_E_UNSUPPORTED;
-    const int mt = nslices > 1 ? 2 : (d->cout + 31) / 32;
     const int ps = d->pixel_shuffle > 1 ? d->pixel_shuffle : 0;
     if (ps) {
         if (!d->out.hi || d->out_nchw || d->out2.hi || d->res1.hi || d->res2.hi || d->mask_src.hi || d->cout % 8) return ESR_E_UNSUPPORTED;
         if (d->out.H != ps * d->H || d->out.W != ps * d->W || (d->ps_rowgroup0 + d->cout / 8 + ps * ps - 1) / (ps * ps) > d->out.ncg) return ESR_E_ARG;
     } else if (!phases && d->out.hi && (d->out.H != d->H || d->out.W != d->W)) return ESR_E_ARG;
     if (!ps && d->out.hi && d->out.ncg * 8 < d->cout) return ESR_E_ARG;
-    // a missing lo OUTPUT plane with hi+lo inputs is the single-plane-intermediate case (fp16 formats only, checked below)
+    // a missing lo OUTPUT plane with hi+lo inputs is the single-plane-intermediate case (fp16 formats only, checked in conv_plan)
     if (d->out.hi && d->out.lo && !split) return ESR_E_ARG;
     if (d->out2.hi && (!d->out.hi || (d->out2.lo && !d->out.lo))) return ESR_E_ARG;      // out2 may drop the lo plane, not add one
     // (the epilogue evaluates alpha * LeakyReLU as a max of two products; act_slope 0 is ReLU: max(alpha*y, 0))
     if (d->act_slope < 0.f || d->act_slope > 1.f || !(d->alpha >= 0.f)) return ESR_E_ARG;
-
-    ConvArgs a{};
-    a.in0 = to_dview(d->in0);
-    a.in1 = to_dview(d->in1);
-    a.ups = ups;
-    a.Win_p = d->in1.W + 2;
-    a.wpack = (const uint4*)d->wpack;
-    a.zero_bias = zero_bias();
-    if (!a.zero_bias) return ESR_E_LAUNCH;
-    a.bias = d->bias ? d->bias : a.zero_bias;
-    a.bias_stride = d->bias ? 1 : 0;
-    a.cout = phases ? d->cout : (nslices > 1 ? 64 : d->cout);       // (the phase kernel takes its slice's groups from the total)
-    a.nslices = nslices;
-    a.B = d->B;
-    a.H = d->H;
-    a.W = d->W;
-    const int npl = split ? 2 : 1;
-    bool mslice = false;
-    const TileCfg t = conv_tiling(d, npl, mt, nslices, ps, mslice);
-    const int mt_k = mslice ? 1 : mt;                              // M tiles per workgroup of the kernel that runs
-    if (t.TH == 0) return ESR_E_UNSUPPORTED;
-    if (mslice) { a.cout = 32; a.nslices = 2; }
-    a.TH = t.TH; a.TW = t.TW; a.P = t.P; a.NPIX_T = t.NPIX_T; a.NPIX_L = t.NPIX_L;
-    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
-    // the kernel's divisions by launch constants, as multiplications (ConvArgs; conv3x3_tile_kernel's prologue)
-    a.ntiles = a.tiles_x * a.tiles_y * a.B;
-    a.xcd_q = a.ntiles / 8;
-    a.xcd_r = a.ntiles % 8;
-    if (phases) {                                      // one grid dimension over (tile, slice): conv3x3_tile_kernel, TMODE 3
-        const long long wgs = (long long)a.ntiles * nslices;
-        if (wgs * nslices >= 0x100000000ll) return ESR_E_UNSUPPORTED;
-        a.xcd_q = (int)(wgs / 8);
-        a.xcd_r = (int)(wgs % 8);
-        a.m_ns = (unsigned)((0x100000000ull + nslices - 1) / nslices);
-        a.i_ns = 0;
-    }
-    a.m_tx = a.tiles_x == 1 ? 0 : (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);     // (divisor 1: 2^32 does not fit — udiv_magic adds n * i instead)
-    a.m_ty = a.tiles_y == 1 ? 0 : (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
-    a.i_tx = a.tiles_x == 1;
-    a.i_ty = a.tiles_y == 1;
-    a.m_P = ((1u << 20) + a.P - 1) / a.P;
-    a.m_ups = ((1u << 16) + ups - 1) / ups;
-    a.nslots = (a.NPIX_L + 63) / 64;
-    a.ncg_out = (a.cout + 7) >> 3;
-    // (udiv_magic is exact while n * d < 2^32: tile / tiles_x with tile < ntiles, and trow / tiles_y with trow < B * tiles_y)
-    if (d->H + 2 >= 32768 || d->W + 2 >= 32768 || (long long)a.ntiles * a.tiles_x >= 0x100000000ll ||
-        (long long)a.B * a.tiles_y * a.tiles_y >= 0x100000000ll)
+    // every per-lane address of the kernel is a uniform per-image base + a 32-bit byte offset, every pixel coordinate 15 bits
+    auto fits = [](const esr_act_view& v) { return !v.hi || (long long)v.ncg * v.cg_stride * 16 < 0x100000000ll; };
+    if (d->H + 2 >= 32768 || d->W + 2 >= 32768 || !fits(d->in0) || !fits(d->in1) || !fits(d->out) || !fits(d->out2) || !fits(d->res1) || !fits(d->res2) ||
+        !fits(d->mask_src) || (d->out_nchw && (long long)d->cout * d->H * d->W * 4 >= 0x100000000ll))
         return ESR_E_UNSUPPORTED;
-    {
-        // every per-lane address of the kernel is a uniform per-image base + a 32-bit byte offset
-        auto fits = [](const esr_act_view& v) { return !v.hi || (long long)v.ncg * v.cg_stride * 16 < 0x100000000ll; };
-        if (!fits(d->in0) || !fits(d->in1) || !fits(d->out) || !fits(d->out2) || !fits(d->res1) || !fits(d->res2) || !fits(d->mask_src)) return ESR_E_UNSUPPORTED;
-        if (d->out_nchw && (long long)d->cout * d->H * d->W * 4 >= 0x100000000ll) return ESR_E_UNSUPPORTED;
-        // residuals cover every output group (the epilogue reads them for all of them)
-        const int ncg_all = (d->cout + 7) >> 3;
-        if ((d->res1.hi && d->res1.ncg < ncg_all) || (d->res2.hi && d->res2.ncg < ncg_all)) return ESR_E_ARG;
-        if (d->mask_src.hi && d->mask_src.ncg < (d->mask_cg1 < ncg_all ? d->mask_cg1 : ncg_all) - d->mask_cg0) return ESR_E_ARG;
+    return ESR_OK;
+}
+
+// The shape part of the plan: slices, M tiles and the tile geometry, from the fields esr_conv3x3_tiling reads (sizes, the planes of in1, and the
+// options that pick the kernel form — no pack, no destination).
+// A 64-channel layer whose launch would leave every workgroup alone on its CU (no more tiles than CUs: the 52 x 52 training crops, a single
+// image of the Z search) runs as TWO 32-channel output slices of the MT = 1 kernel instead (mslice; grid y; same pack, ConvArgs.wtap): twice the
+// workgroups, so that two are resident per CU and cover each other's copy issue and waits — at the price of staging the input tile twice
+// (the second copy comes out of the same XCD's L2).  Same arithmetic per output channel: results are bit-identical to the 64-channel form.
+static int conv_plan_shape(const esr_conv3x3_desc* d, ConvPlan& p) {
+    p.phases = d->upsample_phases == 2;                // two slices (phase rows) of two M tiles (phase columns) per 32-channel block
+    if (!p.phases && d->cout > 64 && d->cout % 64) return ESR_E_UNSUPPORTED;
+    p.nslices = p.phases ? 2 * ((d->cout + 31) / 32) : (d->cout > 64 ? d->cout / 64 : 1);
+    p.mt = p.nslices > 1 ? 2 : (d->cout + 31) / 32;
+    p.npl = d->in1.lo ? 2 : 1;
+    p.ps = d->pixel_shuffle > 1 ? d->pixel_shuffle : 0;
+    p.mslice = false;
+    if (p.nslices == 1 && p.mt == 2 && d->cout == 64 && !d->out_nchw && !p.ps && d->lds_stages == 0 && !d->k_split_ws && all_taps(d->tap_mask_k) &&
+        all_taps(d->tap_mask_m) && (!d->mask_src.hi || (d->mask_cg0 == 0 && d->mask_cg1 >= 8))) {
+        const TileCfg t2 = pick_tile(d->H, d->W, p.npl, 2, WGS_MT2);
+        p.mslice = t2.TH != 0 && (long long)t2.tiles_x * t2.tiles_y * d->B <= CONV_SMALL_WGS;
     }
-    a.ncp = (a.in0.ncg + a.in1.ncg + 1) / 2;
-    a.act_slope = d->act_slope;
-    a.alpha = d->alpha;
-    a.beta1 = d->beta1;
-    a.beta2 = d->beta2;
-    a.res1 = to_dview(d->res1);
-    a.res2 = to_dview(d->res2);
-    a.out = to_dview(d->out);
-    a.out2 = to_dview(d->out2);
-    a.mask = to_dview(d->mask_src);
-    a.out_nchw = d->out_nchw;
-    a.nchw_ctot = d->cout;
-    a.mask_cg0 = d->mask_cg0;
-    a.mask_cg1 = d->mask_cg1;
-    a.mask_slope = d->mask_slope;
-    a.reverse = d->reverse_order;
-    a.stages_hint = (d->lds_stages == 1 || d->lds_stages == 2) ? d->lds_stages : 0;
-    a.range_flag = f16 ? d->range_flag : nullptr;
-    a.range_tag = d->range_tag;
-    a.ps = ps;
-    a.ps_rg0 = d->ps_rowgroup0;
-#ifdef ESR_TRACE
-    a.trace = g_trace;
-#endif
-    int epi = 0;
-    if (d->res1.hi) epi |= EPI_RES1;
+    p.mt_k = p.mslice ? 1 : p.mt;
+    p.kslices = p.mslice ? 2 : p.nslices;
+    p.tile = pick_tile(d->H, d->W, p.npl, p.mt_k, p.mt_k == 1 ? WGS_MT1 : WGS_MT2);
+    return p.tile.TH ? ESR_OK : ESR_E_UNSUPPORTED;
+}
+
+// The whole plan of a validated descriptor.  The refusals that depend on what is decided here are made here, in the order esr_conv3x3 has
+// always made them (a descriptor that trips two of them keeps its return code).
+static int conv_plan(const esr_conv3x3_desc* d, ConvPlan& p) {
+    if (int rc = conv_plan_shape(d, p)) return rc;
+    const TileCfg& t = p.tile;
+    const bool split = p.npl == 2, f16 = d->in1.fmt == ESR_FMT_F16;
+    const int ntiles = t.tiles_x * t.tiles_y * d->B;
+    // the kernel's divisions by launch constants are multiplications (conv_args).  udiv_magic is exact while n * d < 2^32: tile / tiles_x with
+    // tile < ntiles, trow / tiles_y with trow < B * tiles_y, and the phase launch's workgroup / nslices
+    if ((p.phases && (long long)ntiles * p.nslices * p.nslices >= 0x100000000ll) || (long long)ntiles * t.tiles_x >= 0x100000000ll ||
+        (long long)d->B * t.tiles_y * t.tiles_y >= 0x100000000ll)
+        return ESR_E_UNSUPPORTED;
+    // residuals cover every output group (the epilogue reads them for all of them)
+    const int ncg_all = (d->cout + 7) >> 3;
+    if ((d->res1.hi && d->res1.ncg < ncg_all) || (d->res2.hi && d->res2.ncg < ncg_all)) return ESR_E_ARG;
+    if (d->mask_src.hi && d->mask_src.ncg < (d->mask_cg1 < ncg_all ? d->mask_cg1 : ncg_all) - d->mask_cg0) return ESR_E_ARG;
+    p.ups = d->upsample <= 0 ? 1 : d->upsample;
+    p.fmt = f16 ? 1 : 0;
+    p.in0g = d->in0.hi ? d->in0.ncg : 0;
+    p.ncp = (p.in0g + d->in1.ncg + 1) / 2;
+
+    p.epi = d->res1.hi ? EPI_RES1 : 0;
     // residual 1 == a channel-group slice of this conv's own main input, linear epilogue: take it from the staged LDS tile
-    if (nslices == 1 && d->res1.hi && d->act_slope == 1.f && d->alpha != 0.f && ups == 1 && !d->mask_src.hi && !d->out_nchw &&
+    if (p.nslices == 1 && d->res1.hi && d->act_slope == 1.f && d->alpha != 0.f && p.ups == 1 && !d->mask_src.hi && !d->out_nchw &&
         d->res1.batch_stride == d->in1.batch_stride && d->res1.cg_stride == d->in1.cg_stride && ((d->res1.lo != nullptr) == split) &&
         d->in1_lo_groups >= 0) {
         const long long unit = (long long)d->in1.cg_stride * 16;
         const long long off = (const char*)d->res1.hi - (const char*)d->in1.hi;
         const bool lo_ok = !split || ((const char*)d->res1.lo - (const char*)d->in1.lo) == off;
         if (lo_ok && off >= 0 && off % unit == 0 && off / unit + (d->cout + 7) / 8 <= d->in1.ncg) {
-            a.resin_g0 = a.in0.ncg + (int)(off / unit);
-            a.resin_scale = d->beta1 / d->alpha;
-            epi = (epi & ~EPI_RES1) | EPI_RESIN;
+            p.resin_g0 = p.in0g + (int)(off / unit);
+            p.resin_scale = d->beta1 / d->alpha;
+            p.epi = EPI_RESIN;
         }
     }
-    if (d->res2.hi) epi |= EPI_RES2;
-    if (d->mask_src.hi) epi |= EPI_MASK;
-    if (d->out_nchw) epi |= EPI_NCHW;
-    if (d->out2.hi) epi |= EPI_OUT2;
-    if (ps) epi |= EPI_PS;
-    if ((epi & EPI_NCHW) && d->out.hi) return ESR_E_UNSUPPORTED;     // one destination kind per launch
-    hipStream_t s = (hipStream_t)stream;
-    int wpl = d->weight_planes;
-    if (wpl == 0) wpl = f16 ? 1 : npl;
-    if (wpl < 1 || wpl > npl || (!f16 && wpl != npl)) return ESR_E_ARG;
-    a.wslice = nslices > 1 ? (long long)a.ncp * 9 * 2 * wpl * 64 : 0;
-    a.wchunk = (long long)9 * mt * wpl * 64;
-    a.wtap = mt * wpl;
-    if (mslice) a.wslice = (long long)wpl * 64;                   // slice s = M tile s of every (chunk, tap) block of the 64-row pack
-    dma_share_host(npl, 9 * mt_k * wpl, a.nslots, a.share);
+    p.epi |= (d->res2.hi ? EPI_RES2 : 0) | (d->mask_src.hi ? EPI_MASK : 0) | (d->out_nchw ? EPI_NCHW : 0) | (d->out2.hi ? EPI_OUT2 : 0) | (p.ps ? EPI_PS : 0);
+    if ((p.epi & EPI_NCHW) && d->out.hi) return ESR_E_UNSUPPORTED;     // one destination kind per launch
+    p.wpl = d->weight_planes ? d->weight_planes : (f16 ? 1 : p.npl);
+    if (p.wpl < 1 || p.wpl > p.npl || (!f16 && p.wpl != p.npl)) return ESR_E_ARG;
     // which leading chunks of the concatenated input carry a lo plane
-    a.lo_chunks = a.ncp;
-    bool partlo = false;
-    if (split && d->in1_lo_groups > 0 && d->in1_lo_groups < d->in1.ncg) {
-        a.lo_chunks = (a.in0.ncg + d->in1_lo_groups + 1) / 2;
-        partlo = true;
-    }
-    if (split && d->in1_lo_groups < 0) {                             // the conv reads hi planes only (lo planes exist but are not operands)
-        a.lo_chunks = 0;
-        partlo = true;
-    }
-    if (split && d->out.hi && !d->out.lo) partlo = true;
-    if (partlo && !f16) return ESR_E_UNSUPPORTED;                   // single-plane intermediates exist for the fp16 formats only
-    if (phases) {
-        if (partlo) return ESR_E_UNSUPPORTED;                       // whole hi+lo or whole one-plane operands and destination
-        a.wslice = (long long)a.ncp * 9 * 2 * wpl * 64;             // one 64-row pack (two phases of one 32-channel block) per slice
-        if (f16 && split && wpl == 2) return launch<2, 2, 0, 1, 2, false, 3>(a, s);
-        if (f16 && split) return launch<2, 2, 0, 1, 1, false, 3>(a, s);
-        if (f16) return launch<1, 2, 0, 1, 1, false, 3>(a, s);
-        return split ? launch<2, 2, 0, 0, 2, false, 3>(a, s) : launch<1, 2, 0, 0, 1, false, 3>(a, s);
-    }
-    // tap masks are a HINT (blocks outside them must be zero in the pack): the two patterns with compiled kernels are honoured, anything
-    // else multiplies all nine taps — the same result
-    auto all9 = [](const int32_t (&m)[4]) { return (m[0] == 0 || m[0] == 0x1FF) && (m[1] == 0 || m[1] == 0x1FF) && (m[2] == 0 || m[2] == 0x1FF) && (m[3] == 0 || m[3] == 0x1FF); };
-    auto same = [](const int32_t (&m)[4], const int (&p)[4]) { return m[0] == p[0] && m[1] == p[1] && m[2] == p[2] && m[3] == p[3]; };
-    const bool plain = epi == 0 && !f16 && !partlo && mt == 2 && a.in0.ncg == 0;
-    const bool tm1 = plain && same(d->tap_mask_k, S2D_FWD) && d->tap_mask_k_shift == 1 && all9(d->tap_mask_m) && (a.in1.ncg % 4) == 0;
-    const bool tm2 = plain && !tm1 && same(d->tap_mask_m, S2D_FLIP) && all9(d->tap_mask_k);
+    p.lo_chunks = p.ncp;
+    p.partlo = split && (d->in1_lo_groups < 0 || (d->in1_lo_groups > 0 && d->in1_lo_groups < d->in1.ncg) || (d->out.hi && !d->out.lo));
+    if (split && d->in1_lo_groups > 0 && d->in1_lo_groups < d->in1.ncg) p.lo_chunks = (p.in0g + d->in1_lo_groups + 1) / 2;
+    if (split && d->in1_lo_groups < 0) p.lo_chunks = 0;              // the conv reads hi planes only (lo planes exist but are not operands)
+    if (p.partlo && !f16) return ESR_E_UNSUPPORTED;                 // single-plane intermediates exist for the fp16 formats only
+    if (p.phases && p.partlo) return ESR_E_UNSUPPORTED;             // whole hi+lo or whole one-plane operands and destination
+    if (!among(ConvEpis{}, p.epi) || (f16 && p.epi == (EPI_RES1 | EPI_MASK))) return ESR_E_UNSUPPORTED;      // (f16 EPI_MASK: the data gradient of 'mixed')
+
+    const bool plain = p.epi == 0 && !f16 && !p.partlo && p.mt == 2 && p.in0g == 0;
+    const bool tm1 = plain && same_taps(d->tap_mask_k, S2D_FWD) && d->tap_mask_k_shift == 1 && all_taps(d->tap_mask_m) && (d->in1.ncg % 4) == 0;
+    const bool tm2 = plain && !tm1 && same_taps(d->tap_mask_m, S2D_FLIP) && all_taps(d->tap_mask_k);
+    p.tmode = p.phases ? 3 : (tm1 ? 1 : (tm2 ? 2 : 0));
+    // the slices the grid steps through (none without input chunks: their weights are ConvArgs.wslice = 0 apart)
+    const int gslices = p.mslice || (p.nslices > 1 && p.ncp) ? p.kslices : 1;
     // split K (k_split_ws): launches of few workgroups with a long K axis — the critic's 256- / 512-channel layers on 16x16 ... 4x4 maps are 24-100
     // workgroups walking 32-128 chunks each on a 256-CU part.  S = 8, 4 or 2 sets of workgroups (grid z) contract 1/S of the input channels each
-    // into their own fp32 slab; a second launch adds the slabs in order.  Chosen here, from the tiling: the caller only lends the workspace.
-    if (plain && d->k_split_ws && d->act_slope == 1.f && ups == 1 && d->cout % 64 == 0) {
-        const long long slab = (long long)d->B * d->cout * d->H * d->W;
-        const long long wgs = (long long)a.tiles_x * a.tiles_y * a.B * nslices;
-        int S = 1;
-        for (int c = 8; c >= 2; c /= 2) {
-            if (a.ncp % c || a.ncp / c < 8 || (tm1 && (a.ncp / c) % 8)) continue;
-            if (wgs * c > 320 || slab * c > d->k_split_ws_floats) continue;
-            S = c;
-            break;
+    // into their own fp32 slab (EPI_NCHW); a second launch adds the slabs in order.  Chosen here, from the tiling: the caller only lends the workspace.
+    p.S = 1;
+    if (!p.phases && plain && d->k_split_ws && d->act_slope == 1.f && p.ups == 1 && d->cout % 64 == 0) {
+        const long long slab = (long long)d->B * d->cout * d->H * d->W, wgs = (long long)ntiles * p.nslices;
+        for (int c = 8; c >= 2 && p.S == 1; c /= 2) {
+            if (p.ncp % c || p.ncp / c < 8 || (tm1 && (p.ncp / c) % 8)) continue;
+            if (wgs * c <= CONV_SMALL_WGS && slab * c <= d->k_split_ws_floats) p.S = c;
         }
-        if (S > 1) {
-            a.ksplit = S;
-            a.ncp /= S;                      // (a.wslice above is the stride of the FULL pack)
-            a.kz_groups = 2 * a.ncp;
-            a.in1.ncg = a.kz_groups;
-            a.kz_slab = slab;
-            a.out_nchw = d->k_split_ws;
-            int rc;
-            if (tm1) rc = split ? launch<2, 2, EPI_NCHW, 0, 2, false, 1>(a, s) : launch<1, 2, EPI_NCHW, 0, 1, false, 1>(a, s);
-            else if (tm2) rc = split ? launch<2, 2, EPI_NCHW, 0, 2, false, 2>(a, s) : launch<1, 2, EPI_NCHW, 0, 1, false, 2>(a, s);
-            else rc = split ? launch<2, 2, EPI_NCHW, 0, 2, false>(a, s) : launch<1, 2, EPI_NCHW, 0, 1, false>(a, s);
-            if (rc != ESR_OK) return rc;
-            const long long total = (long long)d->B * (d->cout / 8) * d->H * d->W;
-            ESR_CLEAR_ERR();
-            hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)d->k_split_ws, S, slab, a.out,
-                               d->cout, d->H, d->W, total);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
-        }
+        if (p.S > 1) p.epi = EPI_NCHW;
     }
-    if (tm1)
-        return split ? launch<2, 2, 0, 0, 2, false, 1>(a, s) : launch<1, 2, 0, 0, 1, false, 1>(a, s);
-    if (tm2)
-        return split ? launch<2, 2, 0, 0, 2, false, 2>(a, s) : launch<1, 2, 0, 0, 1, false, 2>(a, s);
-    if (f16 && split && partlo && wpl == 2) return mt_k == 1 ? launch_epi<2, 1, 1, 2, true>(a, epi, s) : launch_epi<2, 2, 1, 2, true>(a, epi, s);
-    if (f16 && split && partlo) return mt_k == 1 ? launch_epi<2, 1, 1, 1, true>(a, epi, s) : launch_epi<2, 2, 1, 1, true>(a, epi, s);
-    if (f16 && split && wpl == 2) return mt_k == 1 ? launch_epi<2, 1, 1, 2>(a, epi, s) : launch_epi<2, 2, 1, 2>(a, epi, s);
-    if (f16 && split) return mt_k == 1 ? launch_epi<2, 1, 1, 1>(a, epi, s) : launch_epi<2, 2, 1, 1>(a, epi, s);
-    if (f16) return mt_k == 1 ? launch_epi<1, 1, 1, 1>(a, epi, s) : launch_epi<1, 2, 1, 1>(a, epi, s);
-    if (split) return mt_k == 1 ? launch_epi<2, 1, 0, 2>(a, epi, s) : launch_epi<2, 2, 0, 2>(a, epi, s);
-    return mt_k == 1 ? launch_epi<1, 1, 0, 1>(a, epi, s) : launch_epi<1, 2, 0, 1>(a, epi, s);
+
+    // LDS stages.  esr_conv3x3_desc.lds_stages: 0 = by launch size (slices and K sets included), 1 / 2 = that form
+    const int force = (d->lds_stages == 1 || d->lds_stages == 2) ? d->lds_stages : 0;
+    const bool small = ntiles * gslices * p.S <= CONV_SMALL_WGS;
+    const size_t stage = stage_bytes(p.npl, t.NPIX_L, p.mt_k, p.wpl);
+    if (has_ring4(p.mt_k, p.epi, p.fmt, p.partlo, p.tmode) && !force && small && p.ncp / p.S >= (p.epi == EPI_NCHW ? 8 : 16) && 4 * stage <= 160 * 1024) p.nst = 4;
+    else if (two_stages_only(p.npl, p.tmode)) p.nst = 2;
+    else p.nst = force ? force : (small ? 2 : 1);
+    p.lds = p.nst * stage;
+    p.grid = p.tmode == 3 ? dim3(ntiles * gslices) : dim3(ntiles, gslices, p.S);
+    return ESR_OK;
+}
+
+// The kernel arguments of a planned launch.
+static ConvArgs conv_args(const esr_conv3x3_desc* d, const ConvPlan& p, const float* zero) {
+    const TileCfg& t = p.tile;
+    ConvArgs a{};
+    a.in0 = to_dview(d->in0); a.in1 = to_dview(d->in1);
+    a.ups = p.ups; a.Win_p = d->in1.W + 2;
+    a.wpack = (const uint4*)d->wpack;
+    a.zero_bias = zero;
+    a.bias = d->bias ? d->bias : zero; a.bias_stride = d->bias ? 1 : 0;
+    a.cout = p.mslice ? 32 : (p.nslices > 1 && !p.phases ? 64 : d->cout);       // (the phase kernel takes its slice's groups from the total)
+    a.nslices = p.kslices;
+    a.B = d->B; a.H = d->H; a.W = d->W;
+    a.TH = t.TH; a.TW = t.TW; a.P = t.P; a.NPIX_T = t.NPIX_T; a.NPIX_L = t.NPIX_L;
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    // the kernel's divisions by launch constants, as multiplications (ConvArgs; conv3x3_tile_kernel's prologue)
+    a.ntiles = a.tiles_x * a.tiles_y * a.B;
+    const long long wgs = p.phases ? (long long)a.ntiles * p.nslices : a.ntiles;      // the phase launch: one grid dimension over (tile, slice)
+    a.xcd_q = (int)(wgs / 8); a.xcd_r = (int)(wgs % 8);
+    if (p.phases) a.m_ns = (unsigned)((0x100000000ull + p.nslices - 1) / p.nslices);
+    a.m_tx = a.tiles_x == 1 ? 0 : (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);     // (divisor 1: 2^32 does not fit — udiv_magic adds n * i instead)
+    a.m_ty = a.tiles_y == 1 ? 0 : (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
+    a.i_tx = a.tiles_x == 1; a.i_ty = a.tiles_y == 1;
+    a.m_P = ((1u << 20) + a.P - 1) / a.P; a.m_ups = ((1u << 16) + p.ups - 1) / p.ups;
+    a.nslots = (a.NPIX_L + 63) / 64;
+    a.ncg_out = (a.cout + 7) >> 3;
+    a.ncp = p.ncp / p.S; a.lo_chunks = p.lo_chunks;
+    a.act_slope = d->act_slope; a.alpha = d->alpha; a.beta1 = d->beta1; a.beta2 = d->beta2;
+    a.res1 = to_dview(d->res1); a.res2 = to_dview(d->res2); a.mask = to_dview(d->mask_src);
+    a.out = to_dview(d->out); a.out2 = to_dview(d->out2);
+    a.out_nchw = d->out_nchw; a.nchw_ctot = d->cout;
+    a.mask_cg0 = d->mask_cg0; a.mask_cg1 = d->mask_cg1; a.mask_slope = d->mask_slope;
+    a.resin_g0 = p.resin_g0; a.resin_scale = p.resin_scale;
+    a.reverse = d->reverse_order;
+    a.stages_hint = (d->lds_stages == 1 || d->lds_stages == 2) ? d->lds_stages : 0;      // (kept for the layout of the kernel arguments: no kernel reads it)
+    a.range_flag = p.fmt ? d->range_flag : nullptr; a.range_tag = d->range_tag;
+    a.ps = p.ps; a.ps_rg0 = d->ps_rowgroup0;
+#ifdef ESR_TRACE
+    a.trace = g_trace;
+#endif
+    // where the pack's fragments sit (ConvArgs.wchunk): the slices of a multi-slice or phase launch are whole 64-row packs apart, the two
+    // 32-channel slices of a 64-channel layer one M tile of every (chunk, tap) block
+    a.wslice = p.mslice ? (long long)p.wpl * 64 : (p.nslices > 1 ? (long long)p.ncp * 9 * 2 * p.wpl * 64 : 0);
+    a.wchunk = (long long)9 * p.mt * p.wpl * 64;
+    a.wtap = p.mt * p.wpl;
+    dma_share_host(p.npl, 9 * p.mt_k * p.wpl, a.nslots, a.share);
+    if (p.S > 1) {                           // (a.wslice above is the stride of the FULL pack)
+        a.ksplit = p.S;
+        a.kz_groups = 2 * a.ncp;
+        a.in1.ncg = a.kz_groups;
+        a.kz_slab = (long long)d->B * d->cout * d->H * d->W;
+        a.out_nchw = d->k_split_ws;
+    }
+    return a;
+}
+
+// The one launch site: the plan's kernel with the plan's grid and LDS, then split K's sum of the slabs.
+static int conv_launch(const esr_conv3x3_desc* d, const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    const ConvKernel k = conv_kernel(p);
+    if (!k) return ESR_E_UNSUPPORTED;
+    ESR_CLEAR_ERR();
+    hipLaunchKernelGGL(k, p.grid, dim3(NTHREADS), p.lds, s, a);
+    ESR_CHECK_LAUNCH();
+    if (p.S > 1) {
+        const long long total = (long long)d->B * (d->cout / 8) * d->H * d->W;
+        ESR_CLEAR_ERR();
+        hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)d->k_split_ws, p.S, a.kz_slab, a.out,
+                           d->cout, d->H, d->W, total);
+        ESR_CHECK_LAUNCH();
+    }
+    return ESR_OK;
+}
+
+extern "C" int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling) {
+    if (!d || !tiling || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return ESR_E_ARG;
+    ConvPlan p{};
+    if (int rc = conv_plan_shape(d, p)) return rc;
+    tiling[0] = p.tile.tiles_x; tiling[1] = p.tile.tiles_y;
+    tiling[2] = p.mt_k; tiling[3] = p.kslices;
+    return ESR_OK;
+}
+
+extern "C" int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream) {
+    if (int rc = conv_validate(d)) return rc;
+    ConvPlan p{};
+    if (int rc = conv_plan(d, p)) return rc;
+    const float* zero = zero_bias();
+    if (!zero) return ESR_E_LAUNCH;
+    return conv_launch(d, p, conv_args(d, p, zero), (hipStream_t)stream);
 }

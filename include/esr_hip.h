@@ -145,7 +145,7 @@ typedef struct {
     /* optional split-K workspace (caller-owned device memory, `k_split_ws_floats` floats; NULL: never split).  A launch of few output tiles
      * with a long K axis (the critic's 256- / 512-channel layers on 16x16 ... 4x4 maps: 24-100 workgroups x 32-128 K chunks on 256 CUs) may be
      * run as S = 2, 4 or 8 sets of workgroups that each contract 1/S of the input channels into an fp32 slab of B*cout*H*W floats, followed by a
-     * second launch that adds the slabs in a fixed order and stores `out`.  The library decides from its tiling (S * workgroups <= 320, >= 8 chunks
+     * second launch that adds the slabs in a fixed order and stores `out`.  The library decides from its tiling (S * workgroups within the small-launch bound, 320; >= 8 chunks
      * per set, S slabs fit); only plain launches qualify (act_slope 1, no residual / mask / out2 / out_nchw / pixel_shuffle / upsample / in0,
      * bf16 formats, cout a multiple of 64).  The result differs from the unsplit launch by fp32 summation order only. */
     float* k_split_ws;
@@ -183,8 +183,8 @@ int esr_conv3x3(const esr_conv3x3_desc* d, esr_stream_t stream);
 
 /* Host-only query (no device access, nothing launched): how esr_conv3x3 would tile the launch `d` describes, without split K.
  * tiling[0] / [1] = output tiles per image along x / y, [2] = M tiles (32 output channels) per workgroup, [3] = output slices (grid y; 2 when a
- * 64-channel layer of a small launch runs as two 32-channel slices; 2 * ceil(cout / 32) with upsample_phases = 2, whose tiles lie on the source grid).  The launch has tiling[0] * tiling[1] * B * tiling[3] workgroups; up to 320
- * of them take the small-launch (multi-stage) form.  Checks only the sizes it needs (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise). */
+ * 64-channel layer of a small launch runs as two 32-channel slices; 2 * ceil(cout / 32) with upsample_phases = 2, whose tiles lie on the source grid).  The launch has tiling[0] * tiling[1] * B * tiling[3] workgroups; up to
+ * 320 of them (CONV_SMALL_WGS in esr_conv.hip, the one small-launch bound) take the small-launch (multi-stage) form.  Checks only the sizes it needs (ESR_E_ARG / ESR_E_UNSUPPORTED otherwise). */
 int esr_conv3x3_tiling(const esr_conv3x3_desc* d, int32_t* tiling);
 
 /* Adjoint of the pixel-shuffle store: dst[b][g*r^2 + s][y][x] = src[b][g][r*y + s / r][r*x + s % r] for every group g of `src`

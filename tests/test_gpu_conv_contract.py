@@ -30,7 +30,7 @@ a mask window shifted by one group), and that nothing outside the launch's desti
 [0, ceil(cout/8)), the lo plane of a hi-only out2, the guard elements around out_nchw and the pixel-shuffle groups of other row groups
 keep a NaN sentinel bit for bit.
 
-Which test reaches which case of launch_epi (esr_conv.hip) and which format branch at the end of esr_conv3x3:
+Which test reaches which epilogue of ConvEpis (esr_conv.hip) and which operand form of conv_kernel_exists:
     plain        test_epilogues[<fmt>-plain], test_epilogues[<fmt>-plain_relu_nobias], test_geometry[plain-*], test_four_stage_ring
     RES1         test_epilogues[<fmt>-res1], test_resin_near_misses, test_partial_lo, test_cout
     RES1|RES2    test_epilogues[<fmt>-res12], test_formats, test_geometry[heavy-*], test_slices

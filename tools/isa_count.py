@@ -4,7 +4,7 @@ last MFMA (K-loop tail + epilogue), registers and scratch.  VERDICT r4 item 1 as
 
     python tools/isa_count.py [--only NPL,MT,FMT,NPW] [--filter "1,1,"] [--src path/to/esr_conv.hip] [--keep out.s]
 
---only compiles a scratch copy of the translation unit whose launch() dispatches just that operand form (seconds instead of minutes); without
+--only compiles a scratch copy of the translation unit whose conv_kernel_exists() admits just that operand form (seconds instead of minutes); without
 it every instantiation of the shipping file is compiled (about three minutes)."""
 import argparse
 import os
@@ -28,13 +28,10 @@ def main():
     tmp = tempfile.mkdtemp()
     if a.only:
         npl, mt, fmt, npw = [int(v) for v in a.only.split(',')]
-        # restrict launch<>() — where every launch_nst<> instantiation comes from — to the requested form
-        head = 'int launch(const ConvArgs& a, hipStream_t s) {\n'
+        # restrict conv_kernel_exists() — the one list of instantiations — to the requested form
+        head = 'constexpr bool conv_kernel_exists(int npl, int mt, int epi, int nst, int fmt, int npw, bool partlo, int tmode) {\n'
         assert head in src
-        src = src.replace(head, head + '    if constexpr (!(NPL == %d && MT == %d && FMT == %d && NPW == %d && !PARTLO && TMODE == 0)) return ESR_E_UNSUPPORTED; else {\n' % (npl, mt, fmt, npw))
-        tail = "        return two ? launch_nst<NPL, MT, EPI, 2, FMT, NPW, PARTLO, TMODE>(a, s) : launch_nst<NPL, MT, EPI, 1, FMT, NPW, PARTLO, TMODE>(a, s);\n    }\n}\n"
-        assert tail in src
-        src = src.replace(tail, tail[:-2] + '    }\n}\n')
+        src = src.replace(head, head + '    if (!(npl == %d && mt == %d && fmt == %d && npw == %d && !partlo && tmode == 0)) return false;\n' % (npl, mt, fmt, npw))
     cp = os.path.join(tmp, 'esr_conv_isa.hip')
     open(cp, 'w').write(src.replace('#include "esr_common.h"', '#include "%s/esr_common.h"' % CSRC))
     out = a.keep or os.path.join(tmp, 'conv.s')

@@ -253,6 +253,11 @@ _SIGS = {
                                      C.c_void_p]),
     'esr_jpeg16_extract_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'esr_jpeg16_compress_grad': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'esr_psnr_ssim_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'esr_psnr_ssim': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    'esr_sample_std_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'esr_sample_std': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -301,6 +306,7 @@ class _LazyLib:
 lib = _LazyLib()
 
 ESR_OK, ESR_E_ARG, ESR_E_UNSUPPORTED, ESR_E_LAUNCH = 0, -1, -2, -3
+PIXELS_FLOAT, PIXELS_ROUND, PIXELS_RAW = 0, 1, 2     # esr_psnr_ssim `quantize`
 PACK_FOLD2 = 2              # esr_pack_conv_weights / esr_pack_desc `transposed` = PACK_FOLD2 + first phase: the folded pack of a phase launch
 _ERR = {-1: 'ESR_E_ARG (bad argument)', -2: 'ESR_E_UNSUPPORTED (unsupported shape)', -3: 'ESR_E_LAUNCH (HIP launch error)'}
 

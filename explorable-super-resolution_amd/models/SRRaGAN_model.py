@@ -625,6 +625,13 @@ class SRRaGANModel(BaseModel):
             out_dict['HR'] = mov(sel(self.var_H))
         return out_dict
 
+    def current_metrics(self, crop_border=0, out_type=np.float32):
+        """{'psnr': [B], 'ssim': [B]} float64 on the device: fake_H against var_H of the last feed_data / test, scored as the reference's test.py
+        scores one image (util.tensor2img -> util.calculate_psnr / calculate_ssim, codes/test.py:198-242) without leaving the GPU."""
+        from esr_hip import metrics
+        psnr, ssim = metrics.psnr_ssim(self.fake_H, self.var_H, out_type=out_type, crop_border=crop_border)
+        return {'psnr': psnr, 'ssim': ssim}
+
     def print_network(self):
         s, n = self.get_network_description(self.netG)
         print('Number of parameters in G: {:,d}'.format(n))

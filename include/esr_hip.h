@@ -713,6 +713,30 @@ int esr_jpeg16_extract_grad(const float* d_img, const float* y, int form, int B,
  *   is written (the rounded Cb and Cr planes have zero gradient, as torch.round's: the caller passes d_x zero-filled). */
 int esr_jpeg16_compress_grad(const float* d_coef, int mode, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream);
 
+/* ---- scores of the SR output: PSNR, SSIM and the spread over Z samples (codes/utils/util.py:196-228, :340-391; codes/test.py:198-242) ----
+ * esr_psnr_ssim — a and b are fp32 [B][C][H][W], C 1 or 3.  Every value becomes a pixel as util.tensor2img makes one, in fp32 and in this order:
+ *   v = (clamp(x, lo, hi) - lo) / (hi - lo) (an IEEE division), p = 255 v, and with ESR_PIXELS_ROUND p = rint(p) (NumPy's .round(): half to
+ *   even); ESR_PIXELS_RAW takes x as the pixel (an image that is in 0...255 already; lo and hi are not read).  `border` pixels are dropped on
+ *   every side.  From p on the arithmetic is fp64, as util.calculate_psnr / util.ssim cast first:
+ *     sums[b][0] = sum over the C H' W' pixels of (pa - pb)^2                                       (PSNR = 20 log10(255 / sqrt(sums[b][0] / (C H' W'))))
+ *     sums[b][1] = sum over channels and over the (H' - 10)(W' - 10) windows that fit of the SSIM map (SSIM = sums[b][1] / (C (H' - 10)(W' - 10)))
+ *   with the 11-tap Gaussian window of sigma 1.5 normalised to sum 1 (cv2.getGaussianKernel(11, 1.5), outer product), C1 = (0.01 255)^2,
+ *   C2 = (0.03 255)^2.  Where H' or W' is below 11 no window fits and sums[b][1] = 0.  `partial` is a workspace of
+ *   2 B esr_psnr_ssim_partials(C, H, W, border) doubles (one pair per workgroup); they are added in a fixed order, no atomics: two calls give the
+ *   same bits.  B C and H' / 21 up to 65535 (ESR_E_UNSUPPORTED beyond). */
+#define ESR_PIXELS_FLOAT 0
+#define ESR_PIXELS_ROUND 1
+#define ESR_PIXELS_RAW 2
+int64_t esr_psnr_ssim_partials(int C, int H, int W, int border);
+int esr_psnr_ssim(const float* a, const float* b, int B, int C, int H, int W, float lo, float hi, int quantize, int border, double* partial,
+                  double* sums, esr_stream_t stream);
+/* esr_sample_std — x is fp32 [S][B][C][H][W]: map[b][c][y][x] = 255 std_s clamp(x, 0, 1), the population STD (np.std, ddof 0) over the S samples
+ *   (codes/test.py:224-233; the projection subtracted there is the same for every sample of an image and leaves the STD unchanged), two passes
+ *   in fp64 per pixel, stored as fp32; sums[b] = the fp64 sum of the un-rounded values of image b.  S = 1 gives zeros.  `partial` is a workspace of
+ *   B esr_sample_std_partials(C, H, W) doubles, added as above.  B up to 65535. */
+int64_t esr_sample_std_partials(int C, int H, int W);
+int esr_sample_std(const float* x, int S, int B, int C, int H, int W, float* map, double* partial, double* sums, esr_stream_t stream);
+
 int esr_version(void);
 
 #ifdef __cplusplus

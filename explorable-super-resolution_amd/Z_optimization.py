@@ -49,10 +49,19 @@ training mode (HR_unpadder), the region constraint (non_local_Z_optimization on 
 six names above (the other local and periodicity ones refuse it, the whole-image ones ignore it), the '*_localSTD' histogram variants and the
 automatic histogram temperature.
 JPEG mode (jpeg_extractor given; models/DecompCNN_model.py): the model's fake_H holds DCT coefficients and its image is output_image (0...255),
-Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' in place of 'LR'.  Accepted there: 'l1', 'TV',
-'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', which read Output_Batch(within_0_1=True) only; every other name is refused.  On a colour
-model (chroma_mode) Z_size is still the Y grid, the objectives see the RGB output, Z's gradient runs through both generators, and a model fed
-with the Y coefficients as 'Comp' gets data['uncompressed_chroma'] ([B, 2, H, W] Cb, Cr) passed to model.test.
+Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' in place of 'LR'.  Accepted on either model: 'l1',
+'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease'.  On a colour model (chroma_mode) Z_size is still the Y grid, the objectives see the RGB
+output, Z's gradient runs through both generators, and a model fed with the Y coefficients as 'Comp' gets data['uncompressed_chroma']
+([B, 2, H, W] Cb, Cr) passed to model.test.  The colour model (the one the reference's JPEG GUI builds) also takes the editing objectives: the
+local-STD, periodicity, periodicityPlus and patch-magnitude names, 'scribble', 'hist' and the patch-histogram / dictionary names, 'random_l1' and
+'random_l1_limited'.  The reference evaluates all of them on model.Output_Batch(within_0_1=True) whatever the model (:617, :680); so here: an
+objective's value in JPEG mode is, by definition, its SR-mode value on model.Output_Image_0_1() (the un-clamped RGB image in 0...1, csrc/
+esr_jpeg_edit.hip's esr_ycbcr_rgb on the GPU) in place of fake_H, the clamp inside the kernels as there.  The region constraint takes its
+block-grid form (:355-357): Z mask = min(1, E + D), E = 1 inside a margin of 24 // 8 blocks, D the 8 x 8 block maximum of dilate16(image_mask).
+The caller smears the scribble mask to whole blocks (esr_hip.jpeg_edit.smear_mask_to_blocks, as the GUI does, GUI.py:1998); Z_optimizer does
+not.  One intended divergence: 'random_l1_limited' keeps Output_Image_0_1() at construction as the image to stay close to, where the reference
+keeps model.output_image (YCbCr, 0...255) and subtracts it from an RGB 0...1 image (:547, :691).  Refused in JPEG mode: everything above on the
+Y-only model, the VGG names (the model has no netF), HR_unpadder, the reference's 'digit' objective, and whatever SR mode refuses.
 
 Multi-GPU: the Z batch is sharded over ranks (independent samples, no data-path collective - with ONE exception: the random objectives compare
 every sample with every other, so each rank all-gathers the detached D of all ranks once per iteration, esr_hip.dist.all_gather_tensor, and
@@ -298,8 +307,10 @@ RANDOM_OBJECTIVES = ('random_l1', 'random_l1_limited', 'random_VGG')
 # objectives (reference :391-394, :450-455, :717-722) and periodicityPlus (:470-477, :723-726, :799-806).  Accepted by exact name only.
 MAG_OBJECTIVES = ('local_Mag_increase', 'local_Mag_decrease')
 PLUS_OBJECTIVES = tuple(pre + 'nonInt_periodicityPlus' + post for pre in ('local_STD_', '') for post in ('', '_1D'))
-# accepted with jpeg_extractor (JPEG mode): they read the model's Output_Batch(within_0_1=True) only, never fake_H
+# accepted with jpeg_extractor (JPEG mode) on either model, and the editing objectives the colour model (chroma_mode) also takes there
 JPEG_OBJECTIVES = ('l1', 'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease')
+JPEG_EDIT_OBJECTIVES = LOCAL_STD_OBJECTIVES + PERIODICITY_OBJECTIVES + PLUS_OBJECTIVES + MAG_OBJECTIVES + ('scribble', 'hist') + HIST_OBJECTIVES + \
+    ('random_l1', 'random_l1_limited')
 
 
 class Z_optimizer():
@@ -314,9 +325,13 @@ class Z_optimizer():
         # JPEG mode (the explorable JPEG decoder, models/DecompCNN_model.py): the model's fake_H holds DCT coefficients [B, 64, h, w] and its image
         # is output_image (0...255); Z lives on the block grid, Z_size = [H/8, W/8]; data carries 'Uncomp' or 'Comp' and 'QF' instead of 'LR'
         self.jpeg_mode = jpeg_extractor is not None
-        if self.jpeg_mode and (objective not in JPEG_OBJECTIVES or HR_unpadder is not None):
-            raise NotImplementedError("Z objective '%s'%s in JPEG mode (jpeg_extractor given) is not part of this build: implemented there are %s" % (
-                objective, '' if HR_unpadder is None else ' with HR_unpadder (training)', list(JPEG_OBJECTIVES)))
+        colour = bool(getattr(model, 'chroma_mode', False))
+        if self.jpeg_mode and (HR_unpadder is not None or (objective not in JPEG_OBJECTIVES and not (colour and objective in JPEG_EDIT_OBJECTIVES))):
+            raise NotImplementedError("Z objective '%s'%s in JPEG mode (jpeg_extractor given) on the %s model is not part of this build: implemented "
+                                      "there are %s%s" % (objective, '' if HR_unpadder is None else ' with HR_unpadder (training)',
+                                                          'colour' if colour else 'Y-channel', list(JPEG_OBJECTIVES),
+                                                          ' and the editing objectives %s' % (list(JPEG_EDIT_OBJECTIVES),) if colour else
+                                                          ' (the editing objectives belong to the colour model, chroma_mode=True)'))
         if 'localSTD' in objective:
             hist_objective_config(objective)            # raises, naming the variant
         if objective == 'scribble' and image_mask is None:
@@ -376,7 +391,7 @@ class Z_optimizer():
         self.non_local_Z_optimization = (objective == 'scribble' or special) and bool(unsupported.get('non_local_Z_optimization')) and \
             image_mask is not None and np.mean(image_mask) < 1
         if self.non_local_Z_optimization:
-            Z_mask = esr_scribble.rebuilt_z_mask(image_mask)
+            Z_mask = esr_scribble.rebuilt_z_mask(image_mask, block_size=8 if self.jpeg_mode else 1)
         self.Z_mask = Z_mask
         self.objective, self.model, self.data, self.loggers = objective, model, data, loggers
         self.device = model.device
@@ -405,13 +420,13 @@ class Z_optimizer():
         self.local_STD = objective.startswith('local_') and objective not in MAG_OBJECTIVES
         periodic = objective in PERIODICITY_OBJECTIVES or objective in PLUS_OBJECTIVES
         if self.local_STD or periodic:
-            H, W = model.fake_H.shape[2:] if image_mask is None else np.asarray(image_mask).shape
+            H, W = self._image().shape[2:] if image_mask is None else np.asarray(image_mask).shape
         if self.local_STD:
             # every 7 x 7 window inside the opened image mask (ReturnPatchExtractionMat with overlap 1, :391-398); no mask: the whole output
             self.patches = esr_local.PatchSet(image_mask, H, W)
         if periodic:
             self.periodicity_pairs = [esr_local.ShiftPair(p, H, W, interpolated='nonInt' in objective) for p in data['periodicity_points']]
-        if not self.model_training and ('fake_H' in model.__dict__ if not self.jpeg_mode else getattr(model, 'output_image', None) is not None):
+        if not self.model_training and self._model_has_output():
             self.initial_output = model.Output_Batch(within_0_1=True).detach()
             # every sample's own initial STD (the reference's first_image_only flag is honoured by its 'local' objectives only,
             # Z_optimization.py:617-627): per-sample reference points, so sharding the batch over ranks needs no exchange
@@ -429,7 +444,8 @@ class Z_optimizer():
         if 'l1' in objective and not self.random and data is not None and 'desired' in data:
             self.desired_im = data['desired'].to(self.device)
         if self.random and 'limited' in objective:           # reference :546-548
-            self.initial_image = 1 * model.output_image.detach()
+            # (JPEG mode: the RGB 0...1 image the objective compares with; the reference keeps the YCbCr 0...255 output_image there)
+            self.initial_image = self._image().detach().clone() if self.jpeg_mode else 1 * model.output_image.detach()
             self._check_initial_batch(self.initial_image, 'output_image')
             self.rmse_weight = float(data['rmse_weight'])
         if objective == 'scribble':
@@ -455,15 +471,27 @@ class Z_optimizer():
         self.HR_unpadder = HR_unpadder
         self.STD_PRESERVING_WEIGHT = 100 if 'TV' in objective else 20      # reference Z_optimization.py:508-509 (TV), :471 (others)
 
+    _iter_image = None
+
     def _image(self):
         """the model's output image before the clamp to [0, 1]: fake_H itself for the SR model; in JPEG mode output_image / 255, converted to
-        RGB for the colour model"""
-        return self.model.Output_Image_0_1() if self.jpeg_mode else self.model.fake_H
+        RGB for the colour model (built once per iteration of optimize())"""
+        if not self.jpeg_mode:
+            return self.model.fake_H
+        if self._iter_image is not None:
+            return self._iter_image
+        return self.model.Output_Image_0_1()
+
+    def _model_has_output(self):
+        """the model holds a current output (its test() has run)"""
+        if self.jpeg_mode:
+            return getattr(self.model, 'output_image', None) is not None
+        return self.model.__dict__.get('fake_H') is not None
 
     def Masked_STD(self, first_image_only=False):
         if self.local_STD:
             # the STD of every selected 7 x 7 window [P, B] (reference :616-627); first_image_only: image 0 only, [P, 1]
-            x = self.model.fake_H[:1] if first_image_only else self.model.fake_H
+            x = self._image()[:1] if first_image_only else self._image()
             return esr_local.patch_std(x, self.patches)
         # whole-image objectives: the STD of EVERY sample, [1, B], whatever the flag says (as the reference, see __init__)
         if self._image().is_cuda:            # clamp, mask and the two moments in one pass over the batch (esr_img_stats)
@@ -481,7 +509,7 @@ class Z_optimizer():
 
     def _set_scribble(self, image_mask, data):
         """labels, desired image and constraint of the scribble objective (reference :401-448, :385-390), built once"""
-        if 'fake_H' not in self.model.__dict__ or self.model.fake_H is None:
+        if not self._model_has_output():
             raise ValueError("Z objective 'scribble' needs the model's current output (its brightened pixels and the region constraint start from it)")
         initial = self.initial_output
         self._check_initial_batch(initial)
@@ -496,7 +524,7 @@ class Z_optimizer():
     def _set_special(self, image_mask, data):
         """what the patch-magnitude and periodicityPlus objectives build once: the desired patches (reference :450-455) or the desired STD
         (:476-477), and with the region constraint its reference output and weight (:385-390, :455)"""
-        if 'fake_H' not in self.model.__dict__ or self.model.fake_H is None:
+        if not self._model_has_output():
             raise ValueError("Z objective '%s' needs the model's current output (its desired %s from it)" %
                              (self.objective, 'patches start' if self.objective in MAG_OBJECTIVES else 'STD starts'))
         inc = float(data['STD_increment'])
@@ -591,13 +619,17 @@ class Z_optimizer():
             self.model.feed_data(data, need_GT=False, **({'detach_Y': False} if self.jpeg_mode else {}))
             # drop the previous iteration's output first: its graph holds the generator's saved-activation buffers, and a forward that finds
             # them busy allocates a second full set (2 x 90 GB at the configs[3] shape)
-            self.output_image = Z_loss = loss = None
+            self.output_image = self._iter_image = Z_loss = loss = None
             self.model.fake_H = self.model.output_image = None
             if self.jpeg_mode and data.get('uncompressed_chroma') is not None:      # colour model fed with Y coefficients (reference :679)
                 self.model.test(prevent_grads_calc=False, uncompressed_chroma=data['uncompressed_chroma'])
             else:
                 self.model.test(prevent_grads_calc=False)
-            self.output_image = self.model.Output_Batch(within_0_1=True)
+            if self.jpeg_mode:       # one colour conversion per iteration; Output_Batch(within_0_1=True) is its clamp
+                self._iter_image = self.model.Output_Image_0_1()
+                self.output_image = torch.clamp(self._iter_image, 0, 1)
+            else:
+                self.output_image = self.model.Output_Batch(within_0_1=True)
             if self.model_training:
                 self.output_image = self.HR_unpadder(self.output_image)
             if self.random:
@@ -607,7 +639,7 @@ class Z_optimizer():
                 if 'VGG' in self.objective:
                     D, clamp01 = self.model.netF(self.output_image), False
                 else:
-                    D, clamp01 = self.model.fake_H, True         # clamped inside the term, as Output_Batch(within_0_1=True)
+                    D, clamp01 = self._image(), True             # clamped inside the term, as Output_Batch(within_0_1=True)
                 D_all = None
                 if esr_dist.is_distributed():
                     D_all = esr_dist.all_gather_tensor(D, [b - a for a, b in (esr_dist.shard_range(self.global_batch, r) for r in range(esr_dist.world_size()))])
@@ -621,21 +653,20 @@ class Z_optimizer():
                 Z_loss = (self.output_image - self.desired_im).abs().mean(dim=(1, 2, 3))
             elif self.objective == 'scribble':
                 # per-image L1 + local TV, and the region constraint's share of l1 over the GLOBAL batch (0 when it is off)
-                H, W = self.model.fake_H.shape[2:]
-                Z_loss, constraint = esr_scribble.scribble_loss(self.model.fake_H, self.scribble,
-                                                                constraint_norm=self.global_batch * self.model.fake_H.size(1) * H * W)
+                image = self._image()
+                Z_loss, constraint = esr_scribble.scribble_loss(image, self.scribble, constraint_norm=self.global_batch * image[0].numel())
             elif 'VGG' in self.objective:
                 Z_loss = self.loss(self.model.netF(self.output_image), self.GT_HR_VGG).reshape(1)
             elif self.objective in MAG_OBJECTIVES:
-                Z_loss = esr_patchmag.patch_mag(self.model.fake_H, self.mag)
+                Z_loss = esr_patchmag.patch_mag(self._image(), self.mag)
             elif self.objective in PLUS_OBJECTIVES:
                 # the STD-preserving term gives way to one that raises the STD by the increment, a scalar over the (local) batch (reference :723-726)
-                Z_loss = esr_local.shift_l1(self.model.fake_H, self.image_mask, self.periodicity_pairs) + \
+                Z_loss = esr_local.shift_l1(self._image(), self.image_mask, self.periodicity_pairs) + \
                     (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.desired_STD) ** 2).mean()
             elif 'periodicity' in self.objective:
                 # one STD-preserving scalar over the whole (local) batch and all patches, added to every sample (reference :799-815)
                 Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean() + \
-                    esr_local.shift_l1(self.model.fake_H, self.image_mask, self.periodicity_pairs)
+                    esr_local.shift_l1(self._image(), self.image_mask, self.periodicity_pairs)
             elif 'TV' in self.objective:
                 Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean(0) + \
                     (TV_Loss(self._image(), self.image_mask, clamp01=True) if not self.model_training else
@@ -649,9 +680,8 @@ class Z_optimizer():
                 Z_loss = -1 * Z_loss
             if self.non_local_Z_optimization and self.objective != 'scribble':
                 # the region constraint's share of l1 over the GLOBAL batch, on the scribble kernels
-                H, W = self.model.fake_H.shape[2:]
-                constraint = esr_scribble.region_constraint(self.model.fake_H, self.constraint_spec,
-                                                            norm=self.global_batch * self.model.fake_H.size(1) * H * W)
+                image = self._image()
+                constraint = esr_scribble.region_constraint(image, self.constraint_spec, norm=self.global_batch * image[0].numel())
             self.latest_Z_loss_values = [v.item() for v in Z_loss.reshape(-1)]
             # mean over the GLOBAL batch (reference :742): this shard contributes sum/B_global
             if loss is None:
@@ -672,6 +702,7 @@ class Z_optimizer():
             # against it (reference :765-766, which raises IndexError when a single value is left)
             self.loss_values[0] = self.loss_values[1]
         self.cur_iter = z_iter + 1
+        self._iter_image = None
         Z_2_return = self.Z_model.Return_Detached_Z()
         self.Manage_Model_Grad_Requirements(verify_disabled=False)
         if self.model_training:    # one more forward with gradients enabled for the model (reference :788-795)

@@ -1,9 +1,11 @@
-// Shared by the block-DCT kernels of the JPEG consistency layer (esr_jpeg.hip: 8-point, esr_jpeg16.hip: 16-point): the coefficient side of a
-// workgroup tile.  Coefficient planes are contiguous along w (blocks per image row); a thread moves four consecutive w positions of one plane,
+// Shared by the block-DCT kernels of the JPEG consistency layer (esr_jpeg.hip: 8-point, esr_jpeg16.hip: 16-point, esr_jpeg_edit.hip: the editing
+// tools on both): the cosine tables and the 16-point one-dimensional transforms, and the coefficient side of a workgroup tile.  Coefficient planes are contiguous along w (blocks per image row); a thread moves four consecutive w positions of one plane,
 // as one 16-byte access when `vec` (w % 4 == 0 and every pointer of the call 16-byte aligned: coef_vec) and element by element otherwise.
 // The generator's sigmoid tail and its backward are fused here.  `o` is the element offset in coef, `oy` the one in y / dy / coef_out, which
 // the 16-point kernels index as a tensor of another channel count; the 8-point kernels pass the same offset twice.
 #pragma once
+#include <math.h>
+
 #include "esr_common.h"
 
 namespace {
@@ -58,7 +60,72 @@ __device__ __forceinline__ void coef_store4(const float4 v, float* __restrict__ 
     }
 }
 
-// ---- host side of the eight entry points
+// ---- the transforms: the cosine tables (computed in double on the host, once; a by-value kernel argument, so that with the loops unrolled
+// every cosine is a scalar operand) and the 16-point one-dimensional transforms
+struct DctTab {
+    float c[64];  // c[8k + n] = a(k) cos((2n + 1) k pi / 16), a(0) = sqrt(1/8), a(k > 0) = 1/2: the orthonormal DCT-II matrix
+};
+
+const DctTab& dct_tab() {
+    static const DctTab tab = [] {
+        DctTab t;
+        for (int k = 0; k < 8; ++k)
+            for (int n = 0; n < 8; ++n)
+                t.c[8 * k + n] = (float)((k == 0 ? sqrt(0.125) : 0.5) * cos((2 * n + 1) * k * M_PI / 16.0));
+        return t;
+    }();
+    return tab;
+}
+
+struct Dct16Tab {
+    float c[128];  // c[8k + n] = a(k) cos((2n + 1) k pi / 32), n < 8;  a(0) = 1/4, a(k > 0) = sqrt(1/8)
+};
+
+const Dct16Tab& dct16_tab() {
+    static const Dct16Tab tab = [] {
+        Dct16Tab t;
+        for (int k = 0; k < 16; ++k)
+            for (int n = 0; n < 8; ++n) t.c[8 * k + n] = (float)((k == 0 ? 0.25 : sqrt(0.125)) * cos((2 * n + 1) * k * M_PI / 32.0));
+        return t;
+    }();
+    return tab;
+}
+
+// out[k] = sum_n c(k, n) x[n], k < K, by the even/odd split
+template <int K>
+__device__ __forceinline__ void dct16(const Dct16Tab& tab, const float (&x)[16], float (&out)[16]) {
+    float e[8], o[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+        e[n] = x[n] + x[15 - n];
+        o[n] = x[n] - x[15 - n];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float s = 0.f;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) s = fmaf(tab.c[8 * k + n], (k & 1) ? o[n] : e[n], s);
+        out[k] = s;
+    }
+}
+
+// x[n] = sum_{k < K} c(k, n) in[k], n < 16
+template <int K>
+__device__ __forceinline__ void idct16(const Dct16Tab& tab, const float (&in)[16], float (&x)[16]) {
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+        float e = 0.f, o = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k += 2) {
+            e = fmaf(tab.c[8 * k + n], in[k], e);
+            o = fmaf(tab.c[8 * (k + 1) + n], in[k + 1], o);
+        }
+        x[n] = e + o;
+        x[15 - n] = e - o;
+    }
+}
+
+// ---- host side of the entry points
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // the 16-byte form of the coefficient side: rows of whole float4s, and every coefficient-side pointer of the call (null: not used) aligned
 inline int coef_vec(int w, const void* a, const void* b = nullptr, const void* c = nullptr) {

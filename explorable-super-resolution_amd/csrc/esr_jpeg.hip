@@ -22,21 +22,6 @@ constexpr int TP = TB + 1;      // floats per (r, v) row of T
 constexpr int OP = TB + 4;      // floats per coefficient row of O (a multiple of 4: 16-byte reads)
 constexpr int XO_FLOATS = 64 * OP > 8 * XP ? 64 * OP : 8 * XP;
 
-struct DctTab {
-    float c[64];  // c[8k + n] = a(k) cos((2n + 1) k pi / 16), a(0) = sqrt(1/8), a(k > 0) = 1/2: the orthonormal DCT-II matrix
-};
-
-const DctTab& dct_tab() {
-    static const DctTab tab = [] {
-        DctTab t;
-        for (int k = 0; k < 8; ++k)
-            for (int n = 0; n < 8; ++n)
-                t.c[8 * k + n] = (float)((k == 0 ? sqrt(0.125) : 0.5) * cos((2 * n + 1) * k * M_PI / 16.0));
-        return t;
-    }();
-    return tab;
-}
-
 // image -> coefficients:  c = DCT(img - shift) (/ or *) qtab, optionally rounded half to even
 //   coef (optional): fp32 planes;  act (optional): the same values in the conv kernels' activation layout, groups [0, 8) of the view
 //   y / dy (optional, together): dy = c * s (1 - s), s = sigmoid(y)   (the generator tail's backward)

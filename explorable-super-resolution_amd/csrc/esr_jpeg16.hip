@@ -27,20 +27,6 @@ constexpr int TR = 16 * TB + 16;  // floats per r of T
 constexpr int OP = TB;            // floats per coefficient row of O
 constexpr int XO_FLOATS = 256 * OP > 16 * XP ? 256 * OP : 16 * XP;
 
-struct Dct16Tab {
-    float c[128];  // c[8k + n] = a(k) cos((2n + 1) k pi / 32), n < 8;  a(0) = 1/4, a(k > 0) = sqrt(1/8)
-};
-
-const Dct16Tab& dct16_tab() {
-    static const Dct16Tab tab = [] {
-        Dct16Tab t;
-        for (int k = 0; k < 16; ++k)
-            for (int n = 0; n < 8; ++n) t.c[8 * k + n] = (float)((k == 0 ? 0.25 : sqrt(0.125)) * cos((2 * n + 1) * k * M_PI / 32.0));
-        return t;
-    }();
-    return tab;
-}
-
 // which planes a launch transforms, and where each lives in the tensors
 struct Planes {
     int n;            // image planes transformed (grid z = B * n)
@@ -52,40 +38,6 @@ struct Planes {
     int y_off[3];     // first channel in y / dy / coef_out, tensors of y_C channels
     int img_C, c_C, y_C;
 };
-
-// out[k] = sum_n c(k, n) x[n], k < K, by the even/odd split
-template <int K>
-__device__ __forceinline__ void dct16(const Dct16Tab& tab, const float (&x)[16], float (&out)[16]) {
-    float e[8], o[8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        e[n] = x[n] + x[15 - n];
-        o[n] = x[n] - x[15 - n];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        float s = 0.f;
-#pragma unroll
-        for (int n = 0; n < 8; ++n) s = fmaf(tab.c[8 * k + n], (k & 1) ? o[n] : e[n], s);
-        out[k] = s;
-    }
-}
-
-// x[n] = sum_{k < K} c(k, n) in[k], n < 16
-template <int K>
-__device__ __forceinline__ void idct16(const Dct16Tab& tab, const float (&in)[16], float (&x)[16]) {
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        float e = 0.f, o = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; k += 2) {
-            e = fmaf(tab.c[8 * k + n], in[k], e);
-            o = fmaf(tab.c[8 * (k + 1) + n], in[k + 1], o);
-        }
-        x[n] = e + o;
-        x[15 - n] = e - o;
-    }
-}
 
 template <int K>
 __device__ __forceinline__ void fwd_tile(const Dct16Tab& tab, float* XO, float* T, const float* qs, float shift, int divide, int do_round) {

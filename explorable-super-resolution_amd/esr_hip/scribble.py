@@ -120,12 +120,18 @@ def dilate16(mask):
     return np.max(np.stack([rows[:, j:j + W] for j in range(DILATION)]), 0)
 
 
-def rebuilt_z_mask(image_mask):
-    """the region constraint's Z mask (reference :352-364): min(1, E + dilate16(image_mask)), E = 1 on [24:-24, 24:-24] (empty below 48 px)"""
+def rebuilt_z_mask(image_mask, block_size=1):
+    """the region constraint's Z mask (reference :352-364): min(1, E + dilate16(image_mask)), E = 1 on [24:-24, 24:-24] (empty below 48 px).
+    block_size 8 (JPEG mode, :355-357): Z lives on the 8 x 8 block grid [H/8, W/8]; E = 1 on [3:-3, 3:-3] blocks (the margin 24 // 8 with the
+    reference's slicing) and the dilated mask is reduced to every block's maximum."""
     m = np.asarray(image_mask)
-    E = np.zeros(m.shape, dtype=np.float64)
-    E[NON_EDIT_MARGINS:-NON_EDIT_MARGINS, NON_EDIT_MARGINS:-NON_EDIT_MARGINS] = 1
-    return np.minimum(1, E + dilate16(m)).astype(np.float32)
+    if m.ndim != 2 or m.shape[0] % block_size or m.shape[1] % block_size:
+        raise ValueError('rebuilt_z_mask: a 2-D image mask of whole %d x %d blocks, got %s' % (block_size, block_size, m.shape))
+    h, w = m.shape[0] // block_size, m.shape[1] // block_size
+    E = np.zeros((h, w), dtype=np.float64)
+    E[NON_EDIT_MARGINS // block_size:-NON_EDIT_MARGINS // block_size, NON_EDIT_MARGINS // block_size:-NON_EDIT_MARGINS // block_size] = 1
+    D = dilate16(m).reshape(h, block_size, w, block_size).max(axis=(1, 3))
+    return np.minimum(1, E + D).astype(np.float32)
 
 
 class ScribbleSpec(DeviceCopies):

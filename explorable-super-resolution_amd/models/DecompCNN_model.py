@@ -1,6 +1,6 @@
 """DecompCNNModel — the explorable JPEG decoder's model wrapper (reference codes/models/DecompCNN_model.py), inference surface: feed_data /
 test / Output_Batch / GetLatent / load with the reference's names, for the Y-channel (grey-scale) model and, with chroma_mode=True, the colour
-model that contains it.  Training (is_train) and Enforce_pair_Consistency are not part of this build.
+model that contains it, and the colour model's Enforce_pair_Consistency (imprinting).  Training (is_train) is not part of this build.
 
 Y model (8x8 blocks):
     compressed coefficients = JPEG['compressor'](image)            [B, 64, H/8, W/8], quantised with the image's QF table
@@ -24,6 +24,7 @@ import torch
 
 import models.networks as networks
 from esr_hip import jpeg as esr_jpeg
+from esr_hip import jpeg_edit as esr_jpeg_edit
 from JPEG_module.JPEG import JPEG
 from .base_model import BaseModel
 from .modules.loss import Latent_channels_desc_2_num_channels
@@ -148,8 +149,49 @@ class DecompCNNModel(BaseModel):
         return inconsostent_output
 
     def Enforce_pair_Consistency(self, compressed_im, desired_im):
-        raise NotImplementedError("Enforce_pair_Consistency: the reference's own version reads JPEG['compressor_Y_non_quantized'] and "
-                                  "JPEG['compressor_non_quantized'], keys its model never defines (only its GUI adds them); not part of this build")
+        """The image closest to desired_im, coefficient by coefficient, among those that compress to what compressed_im compresses to
+        (reference :316-334; what its JPEG GUI binds to imprinting): HWC RGB arrays in 0...1 -> HWC RGB array in 0...1, for the colour model.
+        Y: the 64 coefficients of every 8x8 block of the desired Y plane are clamped to within 0.5 of the compressed image's quantised ones
+        (esr_hip.jpeg_edit.consistent_plane); Cb, Cr: the low 8x8 of every 16x16 block likewise, the high frequencies stay the desired image's
+        (consistent_chroma).  Like the reference, it needs JPEG['compressor_Y_non_quantized'] and JPEG['compressor_non_quantized'], which the
+        model does not define (the reference's GUI adds them, GUI.py:2357-2360; their presence is all that is asked of them here: the modules'
+        arithmetic is esr_hip.jpeg's): without them it raises NotImplementedError.
+
+        What the reference computes, followed here as it computes it and pinned by tests/golden/jpeg_edit.npz:
+          * it hands data.util.rgb2ycbcr a 0...255 float image where that function expects 0...1, so the planes it works on are
+            255 (im M) + (16, 128, 128) / 255, not + (16, 128, 128): Y lies about 16 and Cb, Cr about 127.5 below their usual values (the matrix
+            product runs in float64 and the result is cast to float32);
+          * the compressed image is re-quantised on those shifted planes (only the DC coefficients differ from the usual ones);
+          * at the end it applies Tensor_YCbCR2RGB to the 0...255 planes and divides by 255 afterwards, so the conversion's offset enters
+            divided by 255 twice.  The two shifts cancel up to a constant of -2.4e-6 (R), -2.9e-6 (G), +1.1e-6 (B) in the 0...1 output,
+            -(254 / 255) (mat (16, 128, 128) + offset) / 255: an image that is consistent already comes back within 1e-6 of itself.
+          * one image at a time (the reference indexes image 0)."""
+        missing = [k for k in ('compressor_Y_non_quantized', 'compressor_non_quantized') if k not in self.JPEG]
+        if missing or not self.chroma_mode:
+            raise NotImplementedError("Enforce_pair_Consistency: the reference's own version reads JPEG['compressor_Y_non_quantized'] and "
+                                      "JPEG['compressor_non_quantized'], keys its model never defines (only its GUI adds them, GUI.py:2357-2360), on "
+                                      "the colour model: add both to model.JPEG of a chroma_mode model first (missing here: %s)" % (
+                                          missing or 'chroma_mode',))
+
+        def im_2_tensor(im):
+            # data.util.rgb2ycbcr(255 * im, only_y=False) on a float image: x 255 once more, the float64 product / 255 + offsets, then / 255
+            im = np.asarray(im)
+            if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] % 16 or im.shape[1] % 16:
+                raise ValueError('Enforce_pair_Consistency: HWC RGB images with H and W multiples of 16, got %s' % (im.shape,))
+            x = (255 * im.astype(np.float32)) * np.float32(255.)
+            ycc = (np.matmul(x, [[65.481, -37.797, 112.0], [128.553, -74.203, -93.786], [24.966, 112.0, -18.214]]) / 255.0 + [16, 128, 128]) / 255.
+            return torch.from_numpy(np.ascontiguousarray(ycc.astype(np.float32).transpose((2, 0, 1)))).unsqueeze(0).to(self.device)
+        compressed_im, desired_im = im_2_tensor(compressed_im), im_2_tensor(desired_im)
+        if compressed_im.shape != desired_im.shape:
+            raise ValueError('Enforce_pair_Consistency: images of %s and %s' % (tuple(compressed_im.shape[2:]), tuple(desired_im.shape[2:])))
+        with torch.no_grad():
+            compressed_Y_DCT = self.JPEG['compressor_Y'](compressed_im[:, :1])
+            Y = esr_jpeg_edit.consistent_plane(desired_im[:, :1], compressed_Y_DCT, self.JPEG['compressor_Y']._table_on(self.device))
+            compressed_chroma_DCT = self.JPEG['compressor'](compressed_im)
+            chroma = esr_jpeg_edit.consistent_chroma(desired_im, compressed_chroma_DCT, self.JPEG['compressor']._table_on(self.device))
+            # (the reference's final conversion, :334: the matrix on 0...255 values, its offset / 255, all of it / 255 again)
+            rgb = torch.clamp(esr_jpeg_edit.ycbcr_to_rgb(255 * torch.cat([Y, chroma], 1)) / 255, 0, 1)
+        return rgb[0].cpu().numpy().transpose((1, 2, 0))
 
     def _generate(self, G, extractor, chroma):
         """(generator's coefficients, their image) for the current model_input / var_Comp"""
@@ -198,6 +240,8 @@ class DecompCNNModel(BaseModel):
     def Output_Image_0_1(self):
         """the output before the clamp to [0, 1], as Output_Batch(within_0_1=True) clamps it: RGB for the colour model"""
         if self.output_image.size(1) == 3:
+            if self.output_image.is_cuda:            # one read and one write per value, no [B, 3, 3, H, W] broadcast (esr_ycbcr_rgb)
+                return esr_jpeg_edit.ycbcr_to_rgb(self.output_image)
             return Tensor_YCbCR2RGB(self.output_image / 255)
         return self.output_image / 255
 

@@ -713,6 +713,39 @@ int esr_jpeg16_extract_grad(const float* d_img, const float* y, int form, int B,
  *   is written (the rounded Cb and Cr planes have zero gradient, as torch.round's: the caller passes d_x zero-filled). */
 int esr_jpeg16_compress_grad(const float* d_coef, int mode, int B, int h, int w, const float* qtab, float* d_x, esr_stream_t stream);
 
+/* ---- the editing tools of the explorable JPEG decoder (codes/GUI.py imprinting; codes/models/DecompCNN_model.py:316-334) ----
+ * esr_ycbcr_rgb — util.Tensor_YCbCR2RGB(x / 255) (codes/utils/util.py:328-330; the colour model's Output_Batch(within_0_1=True),
+ *   DecompCNN_model.py:749-752) without its [B][3][3][H][W] broadcast: x fp32 [B][3][H][W] YCbCr in 0...255 -> rgb [B][3][H][W], un-clamped, in 0...1:
+ *   rgb[r] = sum_c (float)(255 M[c][r]) (x[c] / 255) + (float)o[r] / 255 with the reference's M and o, in fp32.  One read and one write per value,
+ *   16-byte accesses when H W is a multiple of 4 and both pointers are 16-byte aligned, element by element otherwise.  B up to 65535.
+ * esr_ycbcr_rgb_grad — its adjoint: d_x[c] = (sum_r (float)(255 M[c][r]) d_rgb[r]) / 255. */
+int esr_ycbcr_rgb(const float* x, int B, int H, int W, float* rgb, esr_stream_t stream);
+int esr_ycbcr_rgb_grad(const float* d_rgb, int B, int H, int W, float* d_x, esr_stream_t stream);
+/* esr_jpeg_violation — how far each of N candidate images leaves the set consistent with a compressed code (the imprint search,
+ *   codes/GUI.py:1019-1033, which materialises the [N][64][h][w] coefficients of ~1300 candidates and retries in chunks when memory runs out):
+ *   score[n] = sum over the 64 h w coefficients of max(0, |DCT(cand[n] - 128) / qtab - coef| - 0.5).  cand fp32 [N][1][H][W] (0...255, 16-byte
+ *   aligned, H and W multiples of 8), coef fp32 [coef_n][64][h][w] and qtab fp32 [qtab_n][64] with coef_n, qtab_n = 1 (one for all) or N.  Terms in
+ *   fp32, sums in fp64.  One workgroup owns 32 consecutive blocks (row-major over h w) of one candidate and writes one partial; `partial` is a
+ *   workspace of N esr_jpeg_violation_partials(H, W) doubles, added per candidate in a fixed order by a second launch, no atomics: two calls give
+ *   the same bits, and the coefficient tensor is never written.  Coefficients are read in 16-byte accesses when h w is a multiple of 4 and coef
+ *   is 16-byte aligned, element by element otherwise, with the same bits.  N x partials up to 2^31 - 1.  No gradient. */
+int64_t esr_jpeg_violation_partials(int H, int W);
+int esr_jpeg_violation(const float* cand, int N, int H, int W, const float* coef, int coef_n, const float* qtab, int qtab_n, double* partial,
+                       double* score, esr_stream_t stream);
+/* esr_jpeg_pair — DecompCNN_model.py:320-324 in one launch: out = 128 + iDCT(qtab (clamp(DCT(desired - 128) / qtab - coef, -0.5, 0.5) + coef)), the
+ *   image closest (per coefficient) to `desired` whose quantised code is coef.  desired, out fp32 [B][1][H][W] (16-byte aligned), coef fp32
+ *   [B][64][h][w], qtab fp32 [B][64].  Tiling and access forms of esr_jpeg_violation.  No gradient. */
+int esr_jpeg_pair(const float* desired, int B, int H, int W, const float* coef, const float* qtab, float* out, esr_stream_t stream);
+/* esr_jpeg16_pair — DecompCNN_model.py:325-333 in one launch, for the two chroma planes (the last two of the desired_C = 2 or 3 planes of
+ *   `desired`, fp32 [B][desired_C][H][W], H and W multiples of 16): all 256 frequencies of the 16x16 block DCT are divided by the padded table
+ *   and multiplied back (the extractor's 512-channel form), and the low 8x8 (u, v < 8) are clamped to within 0.5 of the plane's 64 quantised
+ *   coefficients in between, read at channel coef_c0 + 64 plane + 8u + v of a tensor of coef_C channels (the compressor's 384 channels with
+ *   coef_c0 = 256, or its last 128 with 0).  qtab fp32 [B][3][256] as for esr_jpeg16_compress.  out fp32 [B][2][H][W].  Tile of
+ *   esr_jpeg16_compress; coefficients in 16-byte accesses when w is a multiple of 4 and coef 16-byte aligned, with the same bits otherwise.
+ *   No gradient. */
+int esr_jpeg16_pair(const float* desired, int desired_C, int B, int H, int W, const float* coef, int coef_C, int coef_c0, const float* qtab,
+                    float* out, esr_stream_t stream);
+
 /* ---- scores of the SR output: PSNR, SSIM and the spread over Z samples (codes/utils/util.py:196-228, :340-391; codes/test.py:198-242) ----
  * esr_psnr_ssim — a and b are fp32 [B][C][H][W], C 1 or 3.  Every value becomes a pixel as util.tensor2img makes one, in fp32 and in this order:
  *   v = (clamp(x, lo, hi) - lo) / (hi - lo) (an IEEE division), p = 255 v, and with ESR_PIXELS_ROUND p = rint(p) (NumPy's .round(): half to

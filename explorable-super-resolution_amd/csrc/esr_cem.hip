@@ -8,7 +8,8 @@
 //   * fuses  x - D(g)  into the downscale and  g + U(.) / tanh / crop  into the upscale.
 // Index conventions (bit-exact with the reference): LR sample (i,j) sits at HR (sf*i+pre, sf*j+pre), pre = sf - floor(sf/2) - 1
 // (codes/CEM/imresize_CEM.py:99-101); filter centre = floor(k/2); the replicate pad of the zero-stuffed image replicates
-// whatever its first/last row is (a sample row only when pre == 0, i.e. sf == 2).
+// whatever its first/last row is: a sample row when pre == 0 (the first one: the shipped sf == 2) or pre == sf - 1 (the last one: no shipped
+// configuration, but the entry points take any pre in [0, sf)) — the upscale kernels fold the taps that reach past that edge onto it.
 // Forms (esr_cem_sep_form): general k^2 kernels (one output per thread; anisotropic taps), separable tile kernels (a workgroup stages a
 // window in LDS: small images), a streaming tile kernel (x8 downscale of small images) and — large images, where the tile kernels are bound by their own
 // instruction stream — separable WAVE-streaming kernels: a wave walks down a strip of the image with the vertical pass in registers.
@@ -219,6 +220,12 @@ __global__ void cem_upscale_kernel(const float* __restrict__ f, const float* __r
                 if (TWO) u2 = fmaf(tr[b], r2[0], u2);
             }
         }
+        if (pre == sf - 1) {   // ... and sample column w - 1 when that is the frame's last column: every tap right of the frame hits it
+            for (int b = Wh - X + p; b < k; ++b) {
+                u1 = fmaf(tr[b], r1[w - 1], u1);
+                if (TWO) u2 = fmaf(tr[b], r2[w - 1], u2);
+            }
+        }
     };
     for (int a = a0; a < k; a += sf) {
         const int yy = Y + a - p;
@@ -227,6 +234,8 @@ __global__ void cem_upscale_kernel(const float* __restrict__ f, const float* __r
     }
     if (pre == 0)
         for (int a = 0; Y + a - p < 0 && a < k; ++a) row_accum(a, 0);
+    if (pre == sf - 1)
+        for (int a = Hh - Y + p; a < k; ++a) row_accum(a, h - 1);
 
     const long long go = (bc * Hh + Y) * (long long)Wh + X;
     float r;
@@ -240,7 +249,7 @@ __global__ void cem_upscale_kernel(const float* __restrict__ f, const float* __r
 constexpr int UT_Y = 16, UT_X = 64;          // upscale output tile: 16 x 64 high-resolution pixels, 4 rows per wave, one pixel per thread
 
 // Same arithmetic and edge rules as cem_upscale_kernel (polyphase: only taps that land on a sample; the replicate pad of the
-// zero-stuffed image replicates a sample column only when pre == 0), with the low-resolution window and the taps staged in LDS and
+// zero-stuffed image replicates a sample column only when pre == 0 — the first — or pre == sf - 1 — the last), with the low-resolution window and the taps staged in LDS and
 // the per-tap index divisions replaced by increments.
 template <bool TWO>
 __global__ __launch_bounds__(256) void cem_upscale_tiled_kernel(const float* __restrict__ f, const float* __restrict__ f2, int h, int w, int sf, int pre,
@@ -294,6 +303,12 @@ __global__ __launch_bounds__(256) void cem_upscale_tiled_kernel(const float* __r
                     if (TWO) u2 = fmaf(tr[b], r2[-jb], u2);
                 }
             }
+            if (pre == sf - 1) {
+                for (int b = Wh - X + p; b < k; ++b) {             // (b >= 1: X < Wh; a tile with such taps holds sample column w - 1 in its window)
+                    u1 = fmaf(tr[b], r1[w - 1 - jb], u1);
+                    if (TWO) u2 = fmaf(tr[b], r2[w - 1 - jb], u2);
+                }
+            }
         };
         int il = (Y + a0 - p - pre) / sf - ib;
         for (int a = a0; a < k; a += sf, ++il) {
@@ -303,6 +318,8 @@ __global__ __launch_bounds__(256) void cem_upscale_tiled_kernel(const float* __r
         }
         if (pre == 0)
             for (int a = 0; Y + a - p < 0 && a < k; ++a) row_accum(a, -ib);
+        if (pre == sf - 1)
+            for (int a = Hh - Y + p; a < k; ++a) row_accum(a, h - 1 - ib);
         const long long go = (bc * Hh + Y) * (long long)Wh + X;
         const long long idx = (bc * Ho + yq) * (long long)Wo + xo;
         float r;
@@ -654,7 +671,7 @@ __global__ __launch_bounds__(256) void cem_downscale_stream_kernel(const float* 
 }
 
 // Polyphase upscale, separable: the vertical pass combines, for every output ROW of the tile, the <= ceil(k/sf) window rows whose taps land on
-// samples (plus the pre == 0 replicate rule) into one row of window-column values; the horizontal pass does the same along the row.
+// samples (plus the replicate rule of pre == 0 / pre == sf - 1) into one row of window-column values; the horizontal pass does the same along the row.
 // Tile of the separable upscale: 64 x 64 high-resolution pixels, a thread owns one quad of columns in FOUR rows (16 rows apart).  (16 x 64 with one
 // quad per thread until round 5: the polyphase index arithmetic of a quad — which taps hit samples, where they start in the window — depends on
 // the column only and is now formed once per thread and serves four rows; a workgroup's latency chain load -> pass -> pass -> store moves four
@@ -787,6 +804,11 @@ __global__ __launch_bounds__(256) void cem_upscale_sep_kernel(const float* __res
                     u1 = fmaf(tvs[a], w1[-ib * wc + c], u1);
                     if (TWO) u2 = fmaf(tvs[a], w2[-ib * wc + c], u2);
                 }
+            if (pre == sf - 1)                                       // the last row of the zero-stuffed image is sample row h - 1: taps below the image repeat it
+                for (int a = Hh - Y1 + p; a < k; ++a) {
+                    u1 = fmaf(tvs[a], w1[(h - 1 - ib) * wc + c], u1);
+                    if (TWO) u2 = fmaf(tvs[a], w2[(h - 1 - ib) * wc + c], u2);
+                }
         }
         v1[ry1 * vp + c] = u1;
         if (TWO) v2[ry1 * vp + c] = u2;
@@ -796,7 +818,7 @@ __global__ __launch_bounds__(256) void cem_upscale_sep_kernel(const float* __res
     // column it meets there and how many taps follow inside the image — once; then every row is that many multiply-adds out of its pass-1 row.
     // g comes in and the result goes out as 16-byte vectors when the rows are 16-byte aligned (else element by element).
     if (xo >= Wo) return;
-    int b0[4], jl0[4], nb[4], nrep[4];
+    int b0[4], jl0[4], nb[4], nrep[4], blast[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int X = xo + t + crop;
@@ -809,6 +831,7 @@ __global__ __launch_bounds__(256) void cem_upscale_sep_kernel(const float* __res
         int nr = 0;                                                  // pre == 0: the taps that reach left of the image replicate the first sample
         if (pre == 0) while (nr < k && X + nr - p < 0) ++nr;
         nrep[t] = nr;
+        blast[t] = pre == sf - 1 ? max(Wh - X + p, 0) : k;            // pre == sf - 1: the taps from here on reach right of the image and repeat the last sample
     }
 #pragma unroll
     for (int q = 0; q < US_RPT; ++q) {
@@ -830,6 +853,10 @@ __global__ __launch_bounds__(256) void cem_upscale_sep_kernel(const float* __res
             for (int b = 0; b < nrep[t]; ++b) {
                 u1 = fmaf(ths[b], r1[-jb], u1);
                 if (TWO) u2 = fmaf(ths[b], r2[-jb], u2);
+            }
+            for (int b = blast[t]; b < k; ++b) {
+                u1 = fmaf(ths[b], r1[w - 1 - jb], u1);
+                if (TWO) u2 = fmaf(ths[b], r2[w - 1 - jb], u2);
             }
             res2[t] = 0.f;
             if (mode == 0) res[t] = u1;
@@ -972,7 +999,7 @@ __global__ __launch_bounds__(256) void cem_downscale_wave_kernel(const float* __
     }
 }
 
-// Upscale (polyphase, zero-stuffed samples at sf i + pre, pre > 0): lane l owns 4 adjacent OUTPUT columns — one 16-byte load of g and one 16-byte store
+// Upscale (polyphase, zero-stuffed samples at sf i + pre, 0 < pre < sf - 1: a frame of zeros around the samples, nothing for the replicate pad to repeat): lane l owns 4 adjacent OUTPUT columns — one 16-byte load of g and one 16-byte store
 // per output row — and, for the vertical pass, low-resolution column jb + l (and jb + 64 + l where the wave's 256 output columns reach that far).
 //   vertical pass   output rows are walked in blocks of sf rows aligned to the sample grid: row r of a block uses the taps sf t (r = 0) or
 //                   sf - r + sf t (r > 0) on NA consecutive sample rows — a window of NA + 1 sample values per lane in registers, one new value per block
@@ -1249,9 +1276,9 @@ static bool downscale_wave_ok(int sf, int k, int h, int w) {
     return g_cem_wave && (sf == 2 || sf == 3 || sf == 4 || sf == 8) && na >= 4 && na <= 6 && (long long)h * w >= 4096;
 }
 static bool upscale_wave_ok(int sf, int k, int pre, int h, int w) {
-    // pre > 0: no sample on the first row / column of the zero-stuffed image (sf = 2 keeps the tile kernel and its replicate rule)
+    // 0 < pre < sf - 1: no sample on the first or last row / column of the zero-stuffed image (sf = 2 keeps the tile kernel and its replicate rule)
     const int na = (k + sf - 1) / sf;
-    return g_cem_wave && (sf == 3 || sf == 4 || sf == 8) && pre > 0 && na >= 4 && na <= 6 && (long long)h * w >= 4096;
+    return g_cem_wave && (sf == 3 || sf == 4 || sf == 8) && pre > 0 && pre < sf - 1 && na >= 4 && na <= 6 && (long long)h * w >= 4096;
 }
 static bool lrfilter_wave_ok(int k, int h, int w) { return g_cem_wave && (k == 27 || k == 35) && (long long)h * w >= 16384; }
 static bool downscale_stream_ok(int sf, int k, size_t* lds_out, int* qp_out, int* ring_out) {
@@ -1562,7 +1589,8 @@ extern "C" int esr_cem_filter_upscale_sep(const float* e, const float* e2, int B
 //     dx[n] = sum_q dy[q] * T[ry][rx][ iy(q_y) ][ ix(q_x) ],      n' = n*sn + on
 // where for an interior frame position the tap index is n' - m(q) + p, and for the first / last frame row (column) every tap
 // that the clamp folded onto it counts: T holds prefix / suffix sums of the taps along that axis (9 tables [3][3][k][k],
-// built on the host: 0 = prefix (first row), 1 = plain (interior), 2 = suffix (last row)).
+// built on the host: 0 = prefix (first row), 1 = plain (interior), 2 = suffix (last row)).  A frame of ONE row (column) has a position that is
+// first and last at once: every output's whole tap sum lands on it — the last entry of the prefix table.
 __global__ void cem_adjoint_kernel(const float* __restrict__ dy, int hq, int wq, int sq, int oq, int Ny, int Nx, const float* __restrict__ tabs, int k,
                                    int hn, int wn, int sn, int on, float* __restrict__ dx, int accumulate, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1580,16 +1608,15 @@ __global__ void cem_adjoint_kernel(const float* __restrict__ dy, int hq, int wq,
     auto range = [&](int f, int r, int N, int nq, int& q0, int& q1) {
         int lo = f + p - (k - 1) - oq, hi = f + p - oq;     // m(q) in [f+p-(k-1), f+p]
         if (r == 0) lo = -(1 << 28);                         // first row: also every q with m(q) - p < 0 ... m(q) <= p
-        if (r == 2) hi = (1 << 28);
+        if (r == 2 || N == 1) hi = (1 << 28);                // (a frame of one row: first and last at once)
         q0 = lo <= 0 ? 0 : (lo + sq - 1) / sq;
         q1 = hi < 0 ? -1 : hi / sq;
         if (q1 > nq - 1) q1 = nq - 1;
-        (void)N;
     };
     auto tap_index = [&](int f, int r, int N, int q) -> int {
         const int m = q * sq + oq;
         if (r == 1) return f - m + p;
-        if (r == 0) { const int a = p - m; return a > k - 1 ? k - 1 : a; }        // prefix table: all taps a' <= p - m
+        if (r == 0) { const int a = p - m; return (a > k - 1 || N == 1) ? k - 1 : a; }        // prefix table: all taps a' <= p - m; every tap on a one-row frame
         const int a = N - 1 - m + p; return a < 0 ? 0 : a;                         // suffix table: all taps a' >= N-1-m+p
     };
     int qy0, qy1, qx0, qx1;
@@ -1633,7 +1660,7 @@ __global__ void cem_adjoint_1d_kernel(const float* __restrict__ src, int hs, int
     const float* T = tab + r * k;
     int lo = f + p - (k - 1) - oq, hi = f + p - oq;              // m(q) = q*sq + oq in [f+p-(k-1), f+p]; first / last frame position: everything clamped onto it
     if (r == 0) lo = -(1 << 28);
-    if (r == 2) hi = (1 << 28);
+    if (r == 2 || N == 1) hi = (1 << 28);                        // (N == 1: the position is first and last at once and takes every tap of every output)
     int q0 = lo <= 0 ? 0 : (lo + sq - 1) / sq;
     int q1 = hi < 0 ? -1 : hi / sq;
     if (q1 > nq - 1) q1 = nq - 1;
@@ -1644,7 +1671,7 @@ __global__ void cem_adjoint_1d_kernel(const float* __restrict__ src, int hs, int
         const int m = q * sq + oq;
         int a;
         if (r == 1) a = f - m + p;
-        else if (r == 0) { a = p - m; a = a > k - 1 ? k - 1 : a; }
+        else if (r == 0) { a = p - m; a = (a > k - 1 || N == 1) ? k - 1 : a; }
         else { a = N - 1 - m + p; a = a < 0 ? 0 : a; }
         if (a < 0 || a >= k) continue;
         acc = fmaf(T[a], sp[q * stride], acc);

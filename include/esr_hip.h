@@ -276,7 +276,9 @@ int esr_cem_downscale(const float* y, int B, int C, int h, int w, int sf, int pr
 int esr_cem_lrfilter(const float* x, int B, int C, int h, int w, const float* taps, int k, float* out,
                      esr_stream_t stream);
 /* Upscale_OP (CEMnet.py:264-271): zero-stuff at (pre,pre), replicate-pad floor(k/2), correlate with taps
- * (= ds_kernel*sf^2).  f: [B][C][h][w] -> [B][C][sf*h][sf*w], restricted to the crop window
+ * (= ds_kernel*sf^2), any pre in [0, sf): the padding repeats the first row / column of the zero-stuffed image — samples
+ * when pre == 0 — and the last — samples when pre == sf-1 — and holds zeros otherwise.
+ * f: [B][C][h][w] -> [B][C][sf*h][sf*w], restricted to the crop window
  * [crop, sf*h-crop) x [crop, sf*w-crop) (HR_unpadder, CEMnet.py:311).
  *   mode 0: out = U(f)
  *   mode 1: out = g + U(f)                      (projection  g + U(K(x - D(g))), CEMnet.py:305-310)
@@ -308,8 +310,8 @@ int esr_cem_filter_upscale_sep(const float* e, const float* e2, int B, int C, in
 
 /* Which kernel form esr_cem_downscale_sep (op 0) / esr_cem_upscale_sep (op 1) / esr_cem_lrfilter_sep (op 2; k = its tap count, sf and pre unused) runs for an image geometry — decided from these arguments alone, never
  * from the batch, so that a batch and its chunks run the same arithmetic: 0 = tile kernel (a workgroup stages a window in LDS), 1 = streaming tile
- * kernel (x8 downscale of small images), 2 = wave-streaming kernel (low-resolution images of at least 64 x 64 pixels, sf 2 / 3 / 4 / 8 with
- * ceil(k / sf) in 4..6; the upscale also needs pre > 0; the LR filter k = 27 or 35 and 128 x 128 pixels): a wave walks down a strip with the vertical pass in registers.  The
+ * kernel (x8 downscale of small images; any sf whose tile window would crowd the chip), 2 = wave-streaming kernel (low-resolution images of h * w >= 4096 pixels, sf 2 / 3 / 4 / 8 with
+ * ceil(k / sf) in 4..6; the upscale: sf 3 / 4 / 8 and 0 < pre < sf - 1; the LR filter: k = 27 or 35 and h * w >= 16384 pixels): a wave walks down a strip with the vertical pass in registers.  The
  * upscale forms agree to the bit, the downscale and LR-filter forms to fp32 rounding (different order of the two passes).  For tests and documentation; < 0: ESR_E_ARG. */
 int esr_cem_sep_form(int op, int sf, int k, int pre, int h, int w);
 
@@ -332,7 +334,8 @@ int esr_unpack_grad_nchw(const esr_act_view* G, float* dst, int64_t dst_batch_st
 int esr_grad_absmax(const esr_act_view* v, int B, uint32_t* slot, esr_stream_t stream);
 int esr_grad_scale(const esr_act_view* src, const esr_act_view* dst, int B, const uint32_t* slot, int exp, const float* scale_in,
                    const float* scale_den, float* scale_out, esr_stream_t stream);
-/* Adjoint of a CEM filter (see csrc/esr_cem.hip): y[q] = sum taps * frame[clamp(q*sq+oq + a - p)], unknowns at n*sn+on.
+/* Adjoint of a CEM filter (see csrc/esr_cem.hip): y[q] = sum taps * frame[clamp(q*sq+oq + a - p)], unknowns at n*sn+on, on a frame of
+ * Ny x Nx >= 1 x 1 pixels (Ny == 1 / Nx == 1: the one position takes every tap).
  * tabs: device fp32 [3][3][k][k] prefix/plain/suffix tap tables (esr_hip/cem_ops.py builds them). */
 int esr_cem_adjoint(const float* dy, int B, int C, int hq, int wq, int sq, int oq, int Ny, int Nx, const float* tabs, int k,
                     int hn, int wn, int sn, int on, float* dx, int accumulate, esr_stream_t stream);

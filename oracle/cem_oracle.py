@@ -189,9 +189,10 @@ class CEMTaps:
 
 # ----------------------------------------------------------------------------- fixed filters (torch CPU fp32)
 def _dw(x, k):
-    """Depth-wise cross-correlation with one shared 2-D filter (Filter_Layer, CEMnet.py:243-252)."""
+    """Depth-wise cross-correlation with one shared 2-D filter (Filter_Layer, CEMnet.py:243-252), in x's precision (fp32 as the reference
+    runs it; float64 inputs keep the float64 taps: tests/test_host_cem_contract_ref.py)."""
     C = x.shape[1]
-    w = torch.from_numpy(np.ascontiguousarray(k)).to(torch.float32)[None, None].repeat(C, 1, 1, 1)
+    w = torch.from_numpy(np.ascontiguousarray(k)).to(x.dtype)[None, None].repeat(C, 1, 1, 1)
     return F.conv2d(x, w, groups=C)
 
 

@@ -10,9 +10,10 @@
 // (codes/CEM/imresize_CEM.py:99-101); filter centre = floor(k/2); the replicate pad of the zero-stuffed image replicates
 // whatever its first/last row is: a sample row when pre == 0 (the first one: the shipped sf == 2) or pre == sf - 1 (the last one: no shipped
 // configuration, but the entry points take any pre in [0, sf)) — the upscale kernels fold the taps that reach past that edge onto it.
-// Forms (esr_cem_sep_form): general k^2 kernels (one output per thread; anisotropic taps), separable tile kernels (a workgroup stages a
-// window in LDS: small images), a streaming tile kernel (x8 downscale of small images) and — large images, where the tile kernels are bound by their own
-// instruction stream — separable WAVE-streaming kernels: a wave walks down a strip of the image with the vertical pass in registers.
+// Forms: general k^2 kernels (one output per thread; anisotropic taps), separable tile kernels (a workgroup stages a window in LDS:
+// small images), a streaming tile kernel (x8 downscale of small images) and — large images, where the tile kernels are bound by their own instruction
+// stream — separable WAVE-streaming kernels: a wave walks down a strip of the image with the vertical pass in registers.  Which separable form an image
+// takes is the shape part of the op's launch plan (down_shape / filt_shape / up_shape); the launchers and esr_cem_sep_form read it from there.
 #include "esr_common.h"
 #include <type_traits>
 
@@ -1246,6 +1247,84 @@ __global__ __launch_bounds__(256) void cem_lrfilter_wave_kernel(const float* __r
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Host side.  An entry point = cem_check_* (the arguments) -> a plan -> one launch site per kernel family (pick).  A separable op's plan (SepPlan) has
+// a SHAPE part, from the image geometry alone (esr_cem_sep_form reports it), and a GRID part, which needs B * C and the wave forms' strip height.
+static int cdiv(int a, int b) { return (a + b - 1) / b; }
+static int cem_launched() { ESR_CHECK_LAUNCH(); return ESR_OK; }      // how an entry point ends: ESR_E_LAUNCH if the runtime refused its launch
+
+// ---- argument checks, shared by the 2-D and the separable entry point of an op (`ptrs`: every pointer the entry point always needs is there)
+static bool cem_geom_ok(int sf, int k, int h, int w) { return sf >= 1 && k >= 1 && (k & 1) && h > 0 && w > 0; }
+static int cem_check_down(bool ptrs, int B, int C, int h, int w, int sf, int k, int pre, const float* lr, int lr_pad) {
+    if (!ptrs || B <= 0 || C <= 0 || !cem_geom_ok(sf, k, h, w) || pre < 0 || pre >= sf) return ESR_E_ARG;
+    return lr && (h - 2 * lr_pad <= 0 || w - 2 * lr_pad <= 0 || lr_pad < 0) ? ESR_E_ARG : ESR_OK;
+}
+static int cem_check_filter(bool ptrs, int B, int C, int h, int w, int k) { return ptrs && B > 0 && C > 0 && cem_geom_ok(1, k, h, w) ? ESR_OK : ESR_E_ARG; }
+static int cem_check_up(bool ptrs, int B, int C, int h, int w, int sf, int k, int pre, int crop, int mode, const void* g, const void* f2, const void* out2) {
+    if (!ptrs || B <= 0 || C <= 0 || !cem_geom_ok(sf, k, h, w) || sf < 2 || pre < 0 || pre >= sf) return ESR_E_ARG;
+    if (mode < 0 || mode > 3 || crop < 0 || 2 * crop >= h * sf || 2 * crop >= w * sf) return ESR_E_ARG;
+    return (mode >= 1 && !g) || (mode >= 2 && !f2) || (mode == 3 && !out2) ? ESR_E_ARG : ESR_OK;
+}
+static int cem_check_adjoint(bool ptrs, int B, int C, int hq, int wq, int sq, int oq, int Ny, int Nx, int k, int hn, int wn, int sn, int on) {
+    if (!ptrs || B <= 0 || C <= 0 || hq <= 0 || wq <= 0 || hn <= 0 || wn <= 0 || sq < 1 || sn < 1 || k < 1 || !(k & 1)) return ESR_E_ARG;
+    return (hn - 1) * sn + on >= Ny || (wn - 1) * sn + on >= Nx || (hq - 1) * sq + oq >= Ny || (wq - 1) * sq + oq >= Nx ? ESR_E_ARG : ESR_OK;
+}
+
+// ---- run-time value -> template argument: f(std::integral_constant<int, V>) for the first V equal to v, for the last V otherwise.  Every kernel
+// family has ONE launch site, a generic lambda under the picks of its template arguments; the lists at the call sites are the instantiations built.
+template <int V0, int... Vs, class F>
+static void pick(int v, F&& f) {
+    if constexpr (sizeof...(Vs) > 0)
+        if (v != V0) return pick<Vs...>(v, f);
+    f(std::integral_constant<int, V0>{});
+}
+
+// ---- LDS row pitches, in floats.  pitch = 16 (mod 32): two rows of 16 lanes on disjoint halves of the 32 banks
+static int pitch_16_mod_32(int n) { return n + (16 - n % 32 + 32) % 32; }
+// the same for two rows sf apart, sf * pitch = 16 (mod 32): there is one in [n, n + 32) unless sf is a multiple of 32 — then an odd pitch
+static int pitch_sf_rows(int sf, int n) {
+    for (int p = n; p < n + 32; ++p)
+        if ((sf * p) % 32 == 16) return p;
+    return n | 1;
+}
+
+// ---- tile windows.  High-resolution window of a DT x DT downscale tile: rows a side, and columns in each of its sf phase planes
+static int down_rows(int sf, int k) { return (DT - 1) * sf + k; }
+static int down_qcols(int sf, int k) { return cdiv(down_rows(sf, k), sf) + 1; }
+// low-resolution window of `tile` output rows / columns of the upscale: every sample within +-p of it
+static int up_window(int tile, int sf, int k) { return (tile + 2 * (k / 2)) / sf + 3; }
+
+// ---- grids.  The tile kernels put the image planes in grid.z.  The 2-D entry points run their tiled kernel where its window fits in LDS and the planes fit
+// grid.z, else the flat kernel (one output per thread, any geometry); the separable ones return ESR_E_UNSUPPORTED.
+static bool planes_fit_grid_z(int B, int C) { return (long long)B * C <= 65535; }
+static dim3 tile_grid(int Ho, int Wo, int ty, int tx, int B, int C) { return dim3(cdiv(Wo, tx), cdiv(Ho, ty), B * C); }
+static dim3 flat_grid(long long total) { return dim3((unsigned)((total + 255) / 256)); }
+
+struct SepPlan {
+    // shape: from (sf, k, pre, h, w) — and kf, crop, mode for the upscale — alone, never from the batch: a batch and its chunks run the same arithmetic
+    int form;                       // 0 tile, 1 streaming tile, 2 wave-streaming: what esr_cem_sep_form returns
+    bool fits;                      // the form's LDS window fits on chip (else ESR_E_UNSUPPORTED: the caller uses the 2-D entry point)
+    size_t lds;                     // dynamic LDS bytes (the wave kernels: none)
+    int na;                         // down / upscale: taps per phase, ceil(k / sf) — the wave kernels' NA
+    int Ho, Wo, ty, tx;             // output image; tile and streaming forms: outputs per workgroup
+    int nout, nct;                  // wave: output columns per column tile (the upscale's tcols), column tiles
+    int rows, qpitch, hpp, ring;    // downscale: tile window rows, pitches of its planes and of the horizontal pass, streaming ring rows; LR-filter tile: qpitch
+    int wr, wc, vp, ep;             // upscale tile: window, pass-1 pitch; ep, hpp: pitches of the folded LR filter's window and horizontal pass
+    // grid (sep_grid): needs B * C, and wave_strips_target(kernel) for the wave LR filter and the wave upscale
+    int R, nst;                     // wave: strip height in output rows, strips per column tile
+    long long nitems;               // wave: strips x column tiles x planes, one-wave work items, four per workgroup
+    dim3 grid;
+};
+// The grid part.  Wave forms: strips of at most `rows` output rows (a multiple of `unit`), cut to equal height in whole units — one cut for the three
+// wave kernels, which differ in where `rows` comes from.  (nst needs no second look: R <= rows and R >= Ho / nst give ceil(Ho / R) = nst.)
+static void sep_grid(SepPlan& p, int B, int C, int rows, int unit = 1) {
+    if (p.form != 2) { p.grid = tile_grid(p.Ho, p.Wo, p.ty, p.tx, B, C); return; }
+    p.nst = cdiv(p.Ho, rows);
+    p.R = cdiv(cdiv(p.Ho, p.nst), unit) * unit;
+    p.nitems = (long long)B * C * p.nct * p.nst;
+    p.grid = dim3((unsigned)((p.nitems + 3) / 4));
+}
+
 // Strips (waves) of a wave-streaming launch: ONE resident round of the chip.  A strip count just above what the chip holds at once costs a second,
 // nearly empty round (configs[1] upscale: 4224 strips on 4096 wave slots 50 us, 3648 strips 39 us); fewer, longer strips lose memory parallelism
 // (2112: 46 us).  Slots = CUs x 4 workgroups-per-CU-by-occupancy x 4 waves, asked once per kernel; the launch aims at 0.9 of them.
@@ -1269,303 +1348,220 @@ static int wave_strips_target(const void* kernel) {
     next = (next + 1) % 8;
     return slots;
 }
+// strip height that gives the launch that many strips over all column tiles and planes
+static int rows_for_target(const SepPlan& p, int B, int C, const void* kernel) {
+    const int nst = (int)(wave_strips_target(kernel) / ((long long)B * C * p.nct));
+    return cdiv(p.Ho, nst < 1 ? 1 : nst);
+}
 
-// which form of the separable kernels an image geometry takes (esr_cem_sep_form): decided from (sf, k, pre, h, w) alone, never from the batch
-static bool downscale_wave_ok(int sf, int k, int h, int w) {
-    const int na = (k + sf - 1) / sf;
-    return g_cem_wave && (sf == 2 || sf == 3 || sf == 4 || sf == 8) && na >= 4 && na <= 6 && (long long)h * w >= 4096;
-}
-static bool upscale_wave_ok(int sf, int k, int pre, int h, int w) {
-    // 0 < pre < sf - 1: no sample on the first or last row / column of the zero-stuffed image (sf = 2 keeps the tile kernel and its replicate rule)
-    const int na = (k + sf - 1) / sf;
-    return g_cem_wave && (sf == 3 || sf == 4 || sf == 8) && pre > 0 && pre < sf - 1 && na >= 4 && na <= 6 && (long long)h * w >= 4096;
-}
-static bool lrfilter_wave_ok(int k, int h, int w) { return g_cem_wave && (k == 27 || k == 35) && (long long)h * w >= 16384; }
-static bool downscale_stream_ok(int sf, int k, size_t* lds_out, int* qp_out, int* ring_out) {
-    const int cols = (DS_COLS - 1) * sf + k;
+static SepPlan down_shape(int sf, int k, int h, int w) {
+    SepPlan p{};
+    p.Ho = h, p.Wo = w, p.fits = true;
+    p.na = cdiv(k, sf);
+    // wave-streaming kernel: images large enough to give every CU several waves
+    if (g_cem_wave && (sf == 2 || sf == 3 || sf == 4 || sf == 8) && p.na >= 4 && p.na <= 6 && (long long)h * w >= 4096) {
+        p.form = 2;
+        const int nout = (252 - (k - 1)) / sf + 1;              // a lane's four columns start up to 3 columns left of the window
+        p.nct = cdiv(w, nout > WV_LANES ? WV_LANES : nout);
+        p.nout = cdiv(w, p.nct);                                // equal tiles
+        return p;
+    }
+    // streaming kernel: strips of DS_COLS x DS_ROWS outputs, DS_STEP window rows per step
+    const int rows = down_rows(sf, k), qcols = down_qcols(sf, k), cols = (DS_COLS - 1) * sf + k;
     int ring = 16;
-    while (ring < k + 2 * DS_STEP + sf) ring <<= 1;       // rows an un-emitted output still needs + the step being written
-    int qp = (cols + sf - 1) / sf + 1;
-    qp |= 1;
+    while (ring < k + 2 * DS_STEP + sf) ring <<= 1;             // rows an un-emitted output still needs + the step being written
+    const int qp = (cdiv(cols, sf) + 1) | 1;
     const size_t lds_s = ((size_t)sf * DS_STEP * qp + (size_t)ring * (DS_COLS + 1) + 2 * (size_t)k) * 4;
-    const bool fits = DS_STEP * ((cols + 6) / 4 + 1) <= 256 * DS_SB && lds_s <= 64 * 1024;
     // measured: configs[4] (sf 8, k 45: 109 KB tile window, one workgroup per CU) 1.88 -> 1.05 ms; configs[1] (sf 4, k 17: 24 KB)
     // 111 -> 135 us — the streaming kernel pays ~1 us of barriers and LDS round trips per 8 rows, the tile kernel only loses where its
-    // window crowds the CU
-    const int rows_t = (DT - 1) * sf + k;
-    const size_t lds_tile = ((size_t)sf * rows_t * ((rows_t + sf - 1) / sf + 2) + (size_t)rows_t * (DT + 1)) * 4;
-    if (lds_out) *lds_out = lds_s;
-    if (qp_out) *qp_out = qp;
-    if (ring_out) *ring_out = ring;
-    return fits && lds_tile > 64 * 1024;
-}
-
-extern "C" int esr_cem_sep_form(int op, int sf, int k, int pre, int h, int w) {
-    if (sf < 1 || k < 1 || !(k & 1) || h <= 0 || w <= 0) return ESR_E_ARG;
-    if (op == 0) return downscale_wave_ok(sf, k, h, w) ? 2 : (downscale_stream_ok(sf, k, nullptr, nullptr, nullptr) ? 1 : 0);
-    if (op == 1) return upscale_wave_ok(sf, k, pre, h, w) ? 2 : 0;
-    if (op == 2) return lrfilter_wave_ok(k, h, w) ? 2 : 0;
-    return ESR_E_ARG;
+    // window (sized here with pitches qcols + 1 and DT + 1) crowds the CU
+    const size_t lds_crowd = ((size_t)sf * rows * (qcols + 1) + (size_t)rows * (DT + 1)) * 4;
+    if (DS_STEP * ((cols + 6) / 4 + 1) <= 256 * DS_SB && lds_s <= 64 * 1024 && lds_crowd > 64 * 1024) {
+        p.form = 1, p.ty = DS_ROWS, p.tx = DS_COLS, p.qpitch = qp, p.ring = ring, p.lds = lds_s;
+        return p;
+    }
+    // tile kernel: rows sf apart of the window planes and of the horizontal pass's output on disjoint halves of the banks (see the kernel's horizontal pass)
+    p.ty = p.tx = DT, p.rows = rows, p.qpitch = pitch_sf_rows(sf, qcols), p.hpp = pitch_sf_rows(sf, DT);
+    p.lds = ((size_t)sf * p.rows * p.qpitch + (size_t)p.rows * p.hpp) * 4;
+    p.fits = p.lds <= 150 * 1024;
+    return p;
 }
 
 extern "C" int esr_cem_downscale(const float* y, int B, int C, int h, int w, int sf, int pre, const float* taps, int k, const float* lr,
                                  int lr_pad, float* d, esr_stream_t stream) {
-    if (!y || !taps || !d || B <= 0 || C <= 0 || h <= 0 || w <= 0 || sf < 1 || k < 1 || !(k & 1) || pre < 0 || pre >= sf) return ESR_E_ARG;
-    if (lr && (h - 2 * lr_pad <= 0 || w - 2 * lr_pad <= 0 || lr_pad < 0)) return ESR_E_ARG;
+    if (int rc = cem_check_down(y && taps && d, B, C, h, w, sf, k, pre, lr, lr_pad)) return rc;
+    const int rows = down_rows(sf, k), qpitch = pitch_sf_rows(sf, down_qcols(sf, k));
+    const size_t lds = (size_t)sf * rows * qpitch * 4;
     const long long total = (long long)B * C * h * w;
     ESR_CLEAR_ERR();
-    {
-        const int rows = (DT - 1) * sf + k, qcols = (rows + sf - 1) / sf + 1;
-        int qpitch = qcols;
-        while ((sf * qpitch) % 32 != 16 && qpitch < qcols + 32) ++qpitch;      // rows of 16 lanes on disjoint banks (possible for sf = 2^n <= 16)
-        if ((sf * qpitch) % 32 != 16) qpitch = qcols | 1;
-        const size_t lds = (size_t)sf * rows * qpitch * 4;
-        if (lds <= 150 * 1024 && (long long)B * C <= 65535) {
-            ESR_ALLOW_160K_LDS(cem_downscale_tiled_kernel);
-            hipLaunchKernelGGL(cem_downscale_tiled_kernel, dim3((w + DT - 1) / DT, (h + DT - 1) / DT, B * C), dim3(256), lds, (hipStream_t)stream, y, h, w,
-                               sf, pre, taps, k, lr, lr_pad, d, qpitch, rows);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
-        }
+    if (lds <= 150 * 1024 && planes_fit_grid_z(B, C)) {
+        ESR_ALLOW_160K_LDS(cem_downscale_tiled_kernel);
+        hipLaunchKernelGGL(cem_downscale_tiled_kernel, tile_grid(h, w, DT, DT, B, C), dim3(256), lds, (hipStream_t)stream, y, h, w, sf, pre, taps, k, lr,
+                           lr_pad, d, qpitch, rows);
+    } else {
+        hipLaunchKernelGGL(cem_downscale_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, y, h, w, sf, pre, taps, k, lr, lr_pad, d, total);
     }
-    hipLaunchKernelGGL(cem_downscale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, h, w, sf, pre, taps, k,
-                       lr, lr_pad, d, total);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
+    return cem_launched();
+}
+
+// ---- separable variants: taps[a][b] = tv[a] * th[b] (device arrays of k floats each).  Same arguments and results as the 2-D entry points up to
+// fp32 rounding of the tap products; ESR_E_UNSUPPORTED when the tile does not fit (the caller then uses the 2-D entry point).
+extern "C" int esr_cem_downscale_sep(const float* y, int B, int C, int h, int w, int sf, int pre, const float* tv, const float* th, int k, const float* lr,
+                                     int lr_pad, float* d, esr_stream_t stream) {
+    if (int rc = cem_check_down(y && tv && th && d, B, C, h, w, sf, k, pre, lr, lr_pad)) return rc;
+    SepPlan p = down_shape(sf, k, h, w);
+    // planes: refused for every form, as this entry point always has — the wave form's grid is 1-D and would not need it
+    if (!p.fits || !planes_fit_grid_z(B, C)) return ESR_E_UNSUPPORTED;
+    // wave form: strips of 12-14 output rows, cut by the image height ALONE: odd strips walk up (their outputs sum the vertical taps in the other
+    // order), so the cut must not depend on the batch
+    // (configs[1], h = 148: 10 / 12 / 14 / 16 / 20 rows 45 / 34.5 / 37 / 35 / 42 us; configs[4], h = 280: 275 / 289 / 270 / 285 / 273 us)
+    sep_grid(p, B, C, g_cem_wave_rmin > 0 ? g_cem_wave_rmin : (h < 256 ? 12 : 14));
+    const hipStream_t s = (hipStream_t)stream;
+    ESR_CLEAR_ERR();
+    pick<2, 3, 4, 8, 0>(sf, [&](auto SF) {                          // (0: sf at run time; the wave form has no such kernel)
+        constexpr int S = decltype(SF)::value;
+        if (p.form == 2) {
+            if constexpr (S != 0)
+                pick<4, 5, 6>(p.na, [&](auto NA) {
+                    hipLaunchKernelGGL((cem_downscale_wave_kernel<S, decltype(NA)::value>), p.grid, dim3(256), 0, s, y, h, w, pre, tv, th, k, lr, lr_pad, d,
+                                       p.nout, p.R, p.nct, p.nst, p.nitems);
+                });
+        } else if (p.form == 1) {
+            hipLaunchKernelGGL(cem_downscale_stream_kernel<S>, p.grid, dim3(256), p.lds, s, y, h, w, sf, pre, tv, th, k, lr, lr_pad, d, p.qpitch, p.ring);
+        } else {
+            ESR_ALLOW_160K_LDS(cem_downscale_sep_kernel<S>);         // (the macro's static is this instantiation's own: the kernel is a constant here)
+            hipLaunchKernelGGL(cem_downscale_sep_kernel<S>, p.grid, dim3(256), p.lds, s, y, h, w, sf, pre, tv, th, k, lr, lr_pad, d, p.qpitch, p.rows, p.hpp);
+        }
+    });
+    return cem_launched();
+}
+
+static SepPlan filt_shape(int k, int h, int w) {
+    SepPlan p{};
+    p.Ho = h, p.Wo = w, p.ty = LT_TY, p.tx = LT_TX, p.fits = true;
+    if (g_cem_wave && (k == 27 || k == 35) && (long long)h * w >= 16384) {
+        p.form = 2;
+        p.nct = cdiv(w, 128 - (k - 1));
+        p.nout = (cdiv(w, p.nct) + 1) & ~1;                     // equal tiles, whole column pairs
+        return p;
+    }
+    p.qpitch = pitch_16_mod_32(LT_TX + k - 1);
+    p.lds = ((size_t)(LT_TY + k - 1) * p.qpitch + (size_t)(LT_TY + k - 1) * (LT_TX + 1)) * 4;
+    p.fits = p.lds <= 150 * 1024;
+    return p;
 }
 
 extern "C" int esr_cem_lrfilter(const float* x, int B, int C, int h, int w, const float* taps, int k, float* out, esr_stream_t stream) {
-    if (!x || !taps || !out || B <= 0 || C <= 0 || h <= 0 || w <= 0 || k < 1 || !(k & 1)) return ESR_E_ARG;
+    if (int rc = cem_check_filter(x && taps && out, B, C, h, w, k)) return rc;
+    const int pitch = pitch_16_mod_32(LT_TX + k - 1);
+    const size_t lds = (size_t)(LT_TY + k - 1) * pitch * 4;
     const long long total = (long long)B * C * h * w;
     ESR_CLEAR_ERR();
-    {
-        int pitch = LT_TX + k - 1;
-        pitch += (16 - pitch % 32 + 32) % 32;                                   // pitch % 32 == 16
-        const size_t lds = (size_t)(LT_TY + k - 1) * pitch * 4;
-        if (lds <= 150 * 1024 && (long long)B * C <= 65535) {
-            ESR_ALLOW_160K_LDS(cem_lrfilter_tiled_kernel);
-            hipLaunchKernelGGL(cem_lrfilter_tiled_kernel, dim3((w + LT_TX - 1) / LT_TX, (h + LT_TY - 1) / LT_TY, B * C), dim3(256), lds, (hipStream_t)stream,
-                               x, h, w, taps, k, out, pitch);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
-        }
+    if (lds <= 150 * 1024 && planes_fit_grid_z(B, C)) {
+        ESR_ALLOW_160K_LDS(cem_lrfilter_tiled_kernel);
+        hipLaunchKernelGGL(cem_lrfilter_tiled_kernel, tile_grid(h, w, LT_TY, LT_TX, B, C), dim3(256), lds, (hipStream_t)stream, x, h, w, taps, k, out, pitch);
+    } else {
+        hipLaunchKernelGGL(cem_lrfilter_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, h, w, taps, k, out, total);
     }
-    hipLaunchKernelGGL(cem_lrfilter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, h, w, taps, k, out,
-                       total);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
+    return cem_launched();
+}
+
+extern "C" int esr_cem_lrfilter_sep(const float* x, int B, int C, int h, int w, const float* tv, const float* th, int k, float* out, esr_stream_t stream) {
+    if (int rc = cem_check_filter(x && tv && th && out, B, C, h, w, k)) return rc;
+    SepPlan p = filt_shape(k, h, w);
+    // planes: the tile form needs them in grid.z, and the wave form takes only what the tile form could have taken
+    if (!p.fits || !planes_fit_grid_z(B, C)) return ESR_E_UNSUPPORTED;
+    ESR_CLEAR_ERR();                                                // (wave_strips_target leaves no error behind)
+    if (p.form == 2) {
+        pick<27, 35>(k, [&](auto K) {
+            const auto kern = cem_lrfilter_wave_kernel<decltype(K)::value>;
+            int rows = rows_for_target(p, B, C, (const void*)kern);
+            if (rows < g_cem_filt_rmin) rows = g_cem_filt_rmin;     // (every strip runs k - 1 rows before its first output)
+            sep_grid(p, B, C, rows > h ? h : rows);
+            hipLaunchKernelGGL(kern, p.grid, dim3(256), 0, (hipStream_t)stream, x, h, w, tv, th, out, p.nout, p.R, p.nct, p.nst, p.nitems);
+        });
+    } else {
+        sep_grid(p, B, C, 0);
+        ESR_ALLOW_160K_LDS(cem_lrfilter_sep_kernel);
+        hipLaunchKernelGGL(cem_lrfilter_sep_kernel, p.grid, dim3(256), p.lds, (hipStream_t)stream, x, h, w, tv, th, k, out, p.qpitch);
+    }
+    return cem_launched();
+}
+
+// kf: taps of the LR filter folded in front of the upscale (esr_cem_filter_upscale_sep), or 0
+static SepPlan up_shape(int sf, int k, int pre, int h, int w, int kf, int crop, int mode) {
+    SepPlan p{};
+    p.Ho = h * sf - 2 * crop, p.Wo = w * sf - 2 * crop, p.ty = US_Y, p.tx = US_X, p.fits = true;
+    p.na = cdiv(k, sf);
+    // wave form.  0 < pre < sf - 1: no sample on the first or last row / column of the zero-stuffed image (sf = 2 keeps the tile kernel and its replicate rule)
+    if (kf == 0 && g_cem_wave && (sf == 3 || sf == 4 || sf == 8) && pre > 0 && pre < sf - 1 && p.na >= 4 && p.na <= 6 && (long long)h * w >= 4096) {
+        p.form = 2;
+        p.nct = cdiv(p.Wo, 256);
+        p.nout = (cdiv(p.Wo, p.nct) + 3) & ~3;                  // equal column tiles, whole quads
+        return p;
+    }
+    p.wr = up_window(US_Y, sf, k), p.wc = up_window(US_X, sf, k), p.vp = pitch_16_mod_32(p.wc);
+    const int two = mode >= 2 ? 2 : 1, er = p.wr + kf - 1, ec = p.wc + kf - 1;
+    p.ep = ec | 1, p.hpp = p.wc | 1;                            // odd pitches: a column walk down the rows touches every bank once
+    p.lds = ((size_t)two * p.wr * p.wc + (size_t)two * US_Y * p.vp + 2 * (size_t)k + (kf > 0 ? (size_t)er * p.ep + (size_t)er * p.hpp : 0)) * 4;
+    p.fits = p.lds <= 64 * 1024;
+    return p;
 }
 
 extern "C" int esr_cem_upscale(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* taps, int k,
                                const float* g, int crop, int mode, float range, float* out, float* out2, esr_stream_t stream) {
-    if (!f || !taps || !out || B <= 0 || C <= 0 || h <= 0 || w <= 0 || sf < 2 || k < 1 || !(k & 1) || pre < 0 || pre >= sf) return ESR_E_ARG;
-    if (mode < 0 || mode > 3 || crop < 0 || 2 * crop >= h * sf || 2 * crop >= w * sf) return ESR_E_ARG;
-    if (mode >= 1 && !g) return ESR_E_ARG;
-    if (mode >= 2 && !f2) return ESR_E_ARG;
-    if (mode == 3 && !out2) return ESR_E_ARG;
-    const long long total = (long long)B * C * (h * sf - 2 * crop) * (w * sf - 2 * crop);
-    const dim3 grid((unsigned)((total + 255) / 256));
+    if (int rc = cem_check_up(f && taps && out, B, C, h, w, sf, k, pre, crop, mode, g, f2, out2)) return rc;
+    const int Ho = h * sf - 2 * crop, Wo = w * sf - 2 * crop;
+    const int wr = up_window(UT_Y, sf, k), wc = up_window(UT_X, sf, k);
+    const size_t lds = ((size_t)k * k + 2 * (size_t)wr * wc) * 4;       // the taps and two windows, in every mode
+    const long long total = (long long)B * C * Ho * Wo;
     ESR_CLEAR_ERR();
-    {
-        // low-resolution window of one 16 x 64 output tile: every sample within +-p of it
-        const int wr = (UT_Y + 2 * (k / 2)) / sf + 3, wc = (UT_X + 2 * (k / 2)) / sf + 3;
-        const size_t lds = ((size_t)k * k + (size_t)(mode >= 2 ? 2 : 1) * wr * wc + (mode >= 2 ? 0 : 0)) * 4 + (mode >= 2 ? 0 : (size_t)wr * wc * 4);
-        const int Ho = h * sf - 2 * crop, Wo = w * sf - 2 * crop;
-        if (lds <= 60 * 1024 && (long long)B * C <= 65535) {
-            const dim3 tg((Wo + UT_X - 1) / UT_X, (Ho + UT_Y - 1) / UT_Y, B * C);
-            if (mode >= 2)
-                hipLaunchKernelGGL(cem_upscale_tiled_kernel<true>, tg, dim3(256), lds, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode,
-                                   range, out, out2, wr, wc);
-            else
-                hipLaunchKernelGGL(cem_upscale_tiled_kernel<false>, tg, dim3(256), lds, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode,
-                                   range, out, out2, wr, wc);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
-        }
-    }
-    if (mode >= 2)
-        hipLaunchKernelGGL(cem_upscale_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode, range,
-                           out, out2, total);
-    else
-        hipLaunchKernelGGL(cem_upscale_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode, range,
-                           out, out2, total);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
-}
-
-
-// ---- separable variants: taps[a][b] = tv[a] * th[b] (device arrays of k floats each).  Same arguments and results as the 2-D entry points
-// above up to fp32 rounding of the tap products; ESR_E_UNSUPPORTED when the tile does not fit (the caller then uses the 2-D entry point).
-extern "C" int esr_cem_downscale_sep(const float* y, int B, int C, int h, int w, int sf, int pre, const float* tv, const float* th, int k, const float* lr,
-                                     int lr_pad, float* d, esr_stream_t stream) {
-    if (!y || !tv || !th || !d || B <= 0 || C <= 0 || h <= 0 || w <= 0 || sf < 1 || k < 1 || !(k & 1) || pre < 0 || pre >= sf) return ESR_E_ARG;
-    if (lr && (h - 2 * lr_pad <= 0 || w - 2 * lr_pad <= 0 || lr_pad < 0)) return ESR_E_ARG;
-    if ((long long)B * C > 65535) return ESR_E_UNSUPPORTED;
-    {
-        // wave-streaming kernel (round 6): images large enough to give every CU several waves; chosen from the image geometry alone, so that a batch
-        // and its chunks run the same arithmetic
-        const int na = (k + sf - 1) / sf;
-        if (downscale_wave_ok(sf, k, h, w)) {
-            int nout = (252 - (k - 1)) / sf + 1;                // a lane's four columns start up to 3 columns left of the window
-            if (nout > WV_LANES) nout = WV_LANES;
-            const int nct = (w + nout - 1) / nout;
-            nout = (w + nct - 1) / nct;                         // equal tiles
-            typedef void (*wk_t)(const float*, int, int, int, const float*, const float*, int, const float*, int, float*, int, int, int, int, long long);
-#define ESR_DW_PICK(SF_) (na == 4 ? cem_downscale_wave_kernel<SF_, 4> : na == 5 ? cem_downscale_wave_kernel<SF_, 5> : cem_downscale_wave_kernel<SF_, 6>)
-            const wk_t wk = sf == 2 ? ESR_DW_PICK(2) : sf == 3 ? ESR_DW_PICK(3) : sf == 4 ? ESR_DW_PICK(4) : ESR_DW_PICK(8);
-#undef ESR_DW_PICK
-            // strips of 12-14 output rows, cut by the image height ALONE: odd strips walk up (their outputs sum the vertical taps in the other
-            // order), so the cut must not depend on the batch
-            const long long cols_total = (long long)B * C * nct;
-            // (configs[1], h = 148: 10 / 12 / 14 / 16 / 20 rows 45 / 34.5 / 37 / 35 / 42 us; configs[4], h = 280: 275 / 289 / 270 / 285 / 273 us)
-            const int rows = g_cem_wave_rmin > 0 ? g_cem_wave_rmin : (h < 256 ? 12 : 14);
-            int nst = (h + rows - 1) / rows;
-            const int R = (h + nst - 1) / nst;
-            nst = (h + R - 1) / R;
-            const long long nitems = cols_total * nst;
-            const unsigned nwg = (unsigned)((nitems + 3) / 4);
-            ESR_CLEAR_ERR();
-            hipLaunchKernelGGL(wk, dim3(nwg), dim3(256), 0, (hipStream_t)stream, y, h, w, pre, tv, th, k, lr, lr_pad, d, nout, R, nct, nst, nitems);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
-        }
-    }
-    {
-        // streaming kernel: strips of DS_COLS x DS_ROWS outputs, DS_STEP window rows per step
-        size_t lds_s = 0;
-        int qp = 0, ring = 0;
-        if (downscale_stream_ok(sf, k, &lds_s, &qp, &ring)) {
-            ESR_CLEAR_ERR();
-            void (*ks)(const float*, int, int, int, int, const float*, const float*, int, const float*, int, float*, int, int) =
-                sf == 2 ? cem_downscale_stream_kernel<2> : sf == 3 ? cem_downscale_stream_kernel<3> : sf == 4 ? cem_downscale_stream_kernel<4>
-                : sf == 8 ? cem_downscale_stream_kernel<8> : cem_downscale_stream_kernel<0>;
-            hipLaunchKernelGGL(ks, dim3((w + DS_COLS - 1) / DS_COLS, (h + DS_ROWS - 1) / DS_ROWS, B * C), dim3(256), lds_s, (hipStream_t)stream, y, h, w, sf, pre, tv,
-                               th, k, lr, lr_pad, d, qp, ring);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
-        }
-    }
-    const int rows = (DT - 1) * sf + k, qcols = (rows + sf - 1) / sf + 1;
-    // pitches of the window planes and of the horizontal pass's output: rows sf apart on disjoint halves of the 32 banks (possible for sf = 2^n
-    // and 3; see the kernel's horizontal pass)
-    int qpitch = qcols, hpp = DT;
-    while ((sf * qpitch) % 32 != 16 && qpitch < qcols + 32) ++qpitch;
-    if ((sf * qpitch) % 32 != 16) qpitch = qcols | 1;
-    while ((sf * hpp) % 32 != 16 && hpp < DT + 32) ++hpp;
-    if ((sf * hpp) % 32 != 16) hpp = DT + 1;
-    const size_t lds = ((size_t)sf * rows * qpitch + (size_t)rows * hpp) * 4;
-    if (lds > 150 * 1024 || (long long)B * C > 65535) return ESR_E_UNSUPPORTED;
-    ESR_CLEAR_ERR();
-    void (*kern)(const float*, int, int, int, int, const float*, const float*, int, const float*, int, float*, int, int, int) =
-        sf == 2 ? cem_downscale_sep_kernel<2> : sf == 3 ? cem_downscale_sep_kernel<3> : sf == 4 ? cem_downscale_sep_kernel<4> : sf == 8 ? cem_downscale_sep_kernel<8>
-                                                                                                                              : cem_downscale_sep_kernel<0>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3((w + DT - 1) / DT, (h + DT - 1) / DT, B * C), dim3(256), lds, (hipStream_t)stream, y, h, w, sf, pre, tv, th, k, lr, lr_pad, d,
-                       qpitch, rows, hpp);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
-}
-
-extern "C" int esr_cem_lrfilter_sep(const float* x, int B, int C, int h, int w, const float* tv, const float* th, int k, float* out, esr_stream_t stream) {
-    if (!x || !tv || !th || !out || B <= 0 || C <= 0 || h <= 0 || w <= 0 || k < 1 || !(k & 1)) return ESR_E_ARG;
-    if (lrfilter_wave_ok(k, h, w) && (long long)B * C <= 65535) {
-        typedef void (*fk_t)(const float*, int, int, const float*, const float*, float*, int, int, int, int, long long);
-        const fk_t fk = k == 27 ? cem_lrfilter_wave_kernel<27> : cem_lrfilter_wave_kernel<35>;
-        int nout = 128 - (k - 1);
-        const int nct = (w + nout - 1) / nout;
-        nout = ((w + nct - 1) / nct + 1) & ~1;                  // equal tiles, whole column pairs
-        const long long cols_total = (long long)B * C * nct;
-        int nst = (int)(wave_strips_target((const void*)fk) / cols_total);
-        if (nst < 1) nst = 1;
-        int R = (h + nst - 1) / nst;
-        if (R < g_cem_filt_rmin) R = g_cem_filt_rmin;            // (every strip runs k - 1 rows before its first output)
-        if (R > h) R = h;
-        nst = (h + R - 1) / R;
-        R = (h + nst - 1) / nst;
-        const long long nitems = cols_total * nst;
-        ESR_CLEAR_ERR();
-        hipLaunchKernelGGL(fk, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, h, w, tv, th, out, nout, R, nct, nst, nitems);
-        ESR_CHECK_LAUNCH();
-        return ESR_OK;
-    }
-    int pitch = LT_TX + k - 1;
-    pitch += (16 - pitch % 32 + 32) % 32;
-    const size_t lds = ((size_t)(LT_TY + k - 1) * pitch + (size_t)(LT_TY + k - 1) * (LT_TX + 1)) * 4;
-    if (lds > 150 * 1024 || (long long)B * C > 65535) return ESR_E_UNSUPPORTED;
-    ESR_CLEAR_ERR();
-    ESR_ALLOW_160K_LDS(cem_lrfilter_sep_kernel);
-    hipLaunchKernelGGL(cem_lrfilter_sep_kernel, dim3((w + LT_TX - 1) / LT_TX, (h + LT_TY - 1) / LT_TY, B * C), dim3(256), lds, (hipStream_t)stream, x, h, w, tv, th,
-                       k, out, pitch);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
+    pick<1, 0>(mode >= 2, [&](auto TWO) {
+        constexpr bool T = decltype(TWO)::value != 0;
+        if (lds <= 60 * 1024 && planes_fit_grid_z(B, C))
+            hipLaunchKernelGGL(cem_upscale_tiled_kernel<T>, tile_grid(Ho, Wo, UT_Y, UT_X, B, C), dim3(256), lds, (hipStream_t)stream, f, f2, h, w, sf, pre, taps,
+                               k, g, crop, mode, range, out, out2, wr, wc);
+        else
+            hipLaunchKernelGGL(cem_upscale_kernel<T>, flat_grid(total), dim3(256), 0, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode, range,
+                               out, out2, total);
+    });
+    return cem_launched();
 }
 
 // tvf / thf / kf: the LR filter folded in front of the upscale (esr_cem_filter_upscale_sep), or NULL / 0
 static int upscale_sep_launch(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* tvf, const float* thf, int kf,
                               const float* tv, const float* th, int k, const float* g, int crop, int mode, float range, float* out, float* out2,
                               esr_stream_t stream) {
-    if (!f || !tv || !th || !out || B <= 0 || C <= 0 || h <= 0 || w <= 0 || sf < 2 || k < 1 || !(k & 1) || pre < 0 || pre >= sf) return ESR_E_ARG;
-    if (mode < 0 || mode > 3 || crop < 0 || 2 * crop >= h * sf || 2 * crop >= w * sf) return ESR_E_ARG;
-    if ((mode >= 1 && !g) || (mode >= 2 && !f2) || (mode == 3 && !out2)) return ESR_E_ARG;
-    const bool filt = kf > 0;
-    if (filt && (!tvf || !thf || !(kf & 1))) return ESR_E_ARG;
-    {
-        // wave-streaming kernel (round 6): chosen from the image geometry alone (a batch and its chunks run the same arithmetic)
-        const int na = (k + sf - 1) / sf;
-        if (!filt && upscale_wave_ok(sf, k, pre, h, w)) {
-            const int Ho = h * sf - 2 * crop, Wo = w * sf - 2 * crop;
-            const int nct = (Wo + 255) / 256;
-            const int tcols = ((Wo + nct - 1) / nct + 3) & ~3;          // equal column tiles, whole quads
-            typedef void (*uk_t)(const float*, const float*, int, int, int, const float*, const float*, int, const float*, int, int, float, float*, float*, int, int, int,
-                                 int, long long);
-            uk_t uk;
-#define ESR_UW_PICK(TWO_)                                                                                                                                   \
-    (sf == 3 ? (na == 4 ? cem_upscale_wave_kernel<TWO_, 3, 4> : na == 5 ? cem_upscale_wave_kernel<TWO_, 3, 5> : cem_upscale_wave_kernel<TWO_, 3, 6>)              \
-     : sf == 4 ? (na == 4 ? cem_upscale_wave_kernel<TWO_, 4, 4> : na == 5 ? cem_upscale_wave_kernel<TWO_, 4, 5> : cem_upscale_wave_kernel<TWO_, 4, 6>)            \
-               : (na == 4 ? cem_upscale_wave_kernel<TWO_, 8, 4> : na == 5 ? cem_upscale_wave_kernel<TWO_, 8, 5> : cem_upscale_wave_kernel<TWO_, 8, 6>))
-            uk = mode >= 2 ? ESR_UW_PICK(true) : ESR_UW_PICK(false);
-#undef ESR_UW_PICK
-            const long long cols_total = (long long)B * C * nct;
-            int nst = (int)(wave_strips_target((const void*)uk) / cols_total);
-            if (nst < 1) nst = 1;
-            int S = (Ho + nst - 1) / nst;
-            S = (S + sf - 1) / sf * sf;                                  // whole blocks of sf rows
-            if (S < 4 * sf) S = 4 * sf;
-            nst = (Ho + S - 1) / S;
-            S = ((Ho + nst - 1) / nst + sf - 1) / sf * sf;              // strips of equal height
-            nst = (Ho + S - 1) / S;
-            const long long nitems = cols_total * nst;
-            const unsigned nwg = (unsigned)((nitems + 3) / 4);
-            ESR_CLEAR_ERR();
-            hipLaunchKernelGGL(uk, dim3(nwg), dim3(256), 0, (hipStream_t)stream, f, f2, h, w, pre, tv, th, k, g, crop, mode, range, out, out2, S, tcols, nct, nst,
-                               nitems);
-            ESR_CHECK_LAUNCH();
-            return ESR_OK;
+    if (int rc = cem_check_up(f && tv && th && out, B, C, h, w, sf, k, pre, crop, mode, g, f2, out2)) return rc;
+    if (kf > 0 && (!tvf || !thf || !(kf & 1))) return ESR_E_ARG;
+    SepPlan p = up_shape(sf, k, pre, h, w, kf, crop, mode);
+    // planes: the tile form needs them in grid.z; the wave form's grid is 1-D and takes any number
+    if (p.form != 2 && (!p.fits || !planes_fit_grid_z(B, C))) return ESR_E_UNSUPPORTED;
+    const hipStream_t s = (hipStream_t)stream;
+    ESR_CLEAR_ERR();                                                // (wave_strips_target leaves no error behind)
+    pick<1, 0>(mode >= 2, [&](auto TWO) {
+        constexpr bool T = decltype(TWO)::value != 0;
+        if (p.form == 2) {
+            pick<3, 4, 8>(sf, [&](auto SF) {
+                pick<4, 5, 6>(p.na, [&](auto NA) {
+                    const auto kern = cem_upscale_wave_kernel<T, decltype(SF)::value, decltype(NA)::value>;
+                    const int rows = cdiv(rows_for_target(p, B, C, (const void*)kern), sf) * sf;        // whole blocks of sf rows
+                    sep_grid(p, B, C, rows < 4 * sf ? 4 * sf : rows, sf);
+                    hipLaunchKernelGGL(kern, p.grid, dim3(256), 0, s, f, f2, h, w, pre, tv, th, k, g, crop, mode, range, out, out2, p.R, p.nout, p.nct,
+                                       p.nst, p.nitems);
+                });
+            });
+        } else {
+            sep_grid(p, B, C, 0);
+            pick<2, 3, 4, 8, 0>(sf, [&](auto SF) {                  // (0: sf at run time)
+                pick<1, 0>(kf > 0, [&](auto FILT) {
+                    hipLaunchKernelGGL((cem_upscale_sep_kernel<T, decltype(SF)::value, decltype(FILT)::value != 0>), p.grid, dim3(256), p.lds, s, f, f2, h,
+                                       w, sf, pre, tv, th, k, g, crop, mode, range, out, out2, p.wr, p.wc, p.vp, tvf, thf, kf, p.ep, p.hpp);
+                });
+            });
         }
-    }
-    const int wr = (US_Y + 2 * (k / 2)) / sf + 3, wc = (US_X + 2 * (k / 2)) / sf + 3;
-    const int two = mode >= 2 ? 2 : 1;
-    const int vp = wc + (16 - wc % 32 + 32) % 32;                       // pass-1 row pitch = 16 (mod 32)
-    const int er = wr + kf - 1, ec = wc + kf - 1;
-    const int ep = ec | 1, hpp = wc | 1;                                // odd pitches: a column walk down the rows touches every bank once
-    const size_t lds = ((size_t)two * wr * wc + (size_t)two * US_Y * vp + 2 * (size_t)k + (filt ? (size_t)er * ep + (size_t)er * hpp : 0)) * 4;
-    if (lds > 64 * 1024 || (long long)B * C > 65535) return ESR_E_UNSUPPORTED;
-    const int Ho = h * sf - 2 * crop, Wo = w * sf - 2 * crop;
-    const dim3 tg((Wo + US_X - 1) / US_X, (Ho + US_Y - 1) / US_Y, B * C);
-    ESR_CLEAR_ERR();
-    typedef void (*up_t)(const float*, const float*, int, int, int, int, const float*, const float*, int, const float*, int, int, float, float*, float*, int, int, int,
-                         const float*, const float*, int, int, int);
-    up_t kern;
-#define ESR_UP_PICK(TWO_, FILT_)                                                                                                                   \
-    (sf == 2 ? cem_upscale_sep_kernel<TWO_, 2, FILT_> : sf == 3 ? cem_upscale_sep_kernel<TWO_, 3, FILT_> : sf == 4 ? cem_upscale_sep_kernel<TWO_, 4, FILT_> \
-     : sf == 8 ? cem_upscale_sep_kernel<TWO_, 8, FILT_> : cem_upscale_sep_kernel<TWO_, 0, FILT_>)
-    if (filt) kern = mode >= 2 ? ESR_UP_PICK(true, true) : ESR_UP_PICK(false, true);
-    else kern = mode >= 2 ? ESR_UP_PICK(true, false) : ESR_UP_PICK(false, false);
-#undef ESR_UP_PICK
-    hipLaunchKernelGGL(kern, tg, dim3(256), lds, (hipStream_t)stream, f, f2, h, w, sf, pre, tv, th, k, g, crop, mode, range, out, out2, wr, wc, vp, tvf, thf, kf,
-                       ep, hpp);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
+    });
+    return cem_launched();
 }
 
 extern "C" int esr_cem_upscale_sep(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* tv, const float* th, int k,
@@ -1578,6 +1574,12 @@ extern "C" int esr_cem_filter_upscale_sep(const float* e, const float* e2, int B
                                           float* out2, esr_stream_t stream) {
     if (kf < 1) return ESR_E_ARG;
     return upscale_sep_launch(e, e2, B, C, h, w, sf, pre, tvf, thf, kf, tv, th, k, g, crop, mode, range, out, out2, stream);
+}
+
+// which form of the separable kernels an image geometry takes: the shape part of the op's plan, nothing of its own
+extern "C" int esr_cem_sep_form(int op, int sf, int k, int pre, int h, int w) {
+    if (!cem_geom_ok(sf, k, h, w) || op < 0 || op > 2) return ESR_E_ARG;
+    return (op == 0 ? down_shape(sf, k, h, w) : op == 1 ? up_shape(sf, k, pre, h, w, 0, 0, 0) : filt_shape(k, h, w)).form;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1682,28 +1684,24 @@ __global__ void cem_adjoint_1d_kernel(const float* __restrict__ src, int hs, int
 // tabs_v / tabs_h: [3][k] prefix / plain / suffix sums of the vertical / horizontal factor; tmp: B*C*hq*wn floats of scratch
 extern "C" int esr_cem_adjoint_sep(const float* dy, int B, int C, int hq, int wq, int sq, int oq, int Ny, int Nx, const float* tabs_v, const float* tabs_h,
                                    int k, int hn, int wn, int sn, int on, float* tmp, const float* base, float alpha, float* dx, esr_stream_t stream) {
-    if (!dy || !tabs_v || !tabs_h || !tmp || !dx || B <= 0 || C <= 0 || hq <= 0 || wq <= 0 || hn <= 0 || wn <= 0 || sq < 1 || sn < 1 || k < 1 || !(k & 1)) return ESR_E_ARG;
-    if ((hn - 1) * sn + on >= Ny || (wn - 1) * sn + on >= Nx || (hq - 1) * sq + oq >= Ny || (wq - 1) * sq + oq >= Nx) return ESR_E_ARG;
+    if (int rc = cem_check_adjoint(dy && tabs_v && tabs_h && tmp && dx, B, C, hq, wq, sq, oq, Ny, Nx, k, hn, wn, sn, on)) return rc;
     const long long t1 = (long long)B * C * hq * wn, t2 = (long long)B * C * hn * wn;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(cem_adjoint_1d_kernel<0>, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, hq, wq, sq, oq, Nx, tabs_h, k, wn, sn, on,
                        (const float*)nullptr, 1.f, tmp, t1);
     hipLaunchKernelGGL(cem_adjoint_1d_kernel<1>, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, hq, wn, sq, oq, Ny, tabs_v, k,
                        hn, sn, on, base, alpha, dx, t2);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
+    return cem_launched();
 }
 
 extern "C" int esr_cem_adjoint(const float* dy, int B, int C, int hq, int wq, int sq, int oq, int Ny, int Nx, const float* tabs, int k,
                                int hn, int wn, int sn, int on, float* dx, int accumulate, esr_stream_t stream) {
-    if (!dy || !tabs || !dx || B <= 0 || C <= 0 || hq <= 0 || wq <= 0 || hn <= 0 || wn <= 0 || sq < 1 || sn < 1 || k < 1 || !(k & 1)) return ESR_E_ARG;
-    if ((hn - 1) * sn + on >= Ny || (wn - 1) * sn + on >= Nx || (hq - 1) * sq + oq >= Ny || (wq - 1) * sq + oq >= Nx) return ESR_E_ARG;
+    if (int rc = cem_check_adjoint(dy && tabs && dx, B, C, hq, wq, sq, oq, Ny, Nx, k, hn, wn, sn, on)) return rc;
     const long long total = (long long)B * C * hn * wn;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(cem_adjoint_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, hq, wq, sq, oq, Ny, Nx, tabs, k,
                        hn, wn, sn, on, dx, accumulate, total);
-    ESR_CHECK_LAUNCH();
-    return ESR_OK;
+    return cem_launched();
 }
 
 #ifdef ESR_TRACE

@@ -367,7 +367,16 @@ int fill_common(BnArgs& a, const esr_bn_desc* d) {
     if (d->s2d && (a.H % 2 || a.W % 2)) return ESR_E_UNSUPPORTED;
     return ESR_OK;
 }
-bool s2d_view_ok(const CView& v, const BnArgs& a, bool s2d) { return v.hi && (s2d ? (v.H == a.H / 2 && v.W == a.W / 2) : (v.H == a.H && v.W == a.W)); }
+// scale == NULL is "no normalisation", a constant map of y: with const_stats == 0 the gradient modes would take the branch of an identity map
+// and the value of gamma*rstd.  (esr_bn_finalize_apply derives its own affine and never reads d->scale.)
+bool affine_ok(const esr_bn_desc* d) { return d->scale || d->const_stats; }
+// A view other than y: present, of the launch's (plain or space-to-depth) pixel size, and declaring every group the launch addresses in it —
+// groups [0, ncg) of a plain view; of a space-to-depth one up to the index voff<true> gives the last group at parity 3
+bool view_ok(const esr_act_view& v, const BnArgs& a, bool s2d) {
+    if (!v.hi) return false;
+    if (s2d) return v.H == a.H / 2 && v.W == a.W / 2 && v.ncg >= 16 * ((a.ncg - 1) / 4) + 12 + (a.ncg - 1) % 4 + 1;
+    return v.H == a.H && v.W == a.W && v.ncg >= a.ncg;
+}
 
 }  // namespace
 
@@ -391,9 +400,9 @@ extern "C" int esr_bn_reduce(const esr_bn_desc* d, int mode, double* sums, esr_s
     BnArgs a{};
     const int rc = fill_common(a, d);
     if (rc != ESR_OK) return rc;
-    if (!sums || mode < 0 || mode > 2) return ESR_E_ARG;
-    if (mode >= 1 && (!s2d_view_ok(a.dz, a, d->s2d != 0) || (!a.const_stats && (!a.mean || !a.rstd)))) return ESR_E_ARG;
-    if (mode == 2 && !s2d_view_ok(a.u, a, false)) return ESR_E_ARG;
+    if (!sums || mode < 0 || mode > 2 || !affine_ok(d)) return ESR_E_ARG;
+    if (mode >= 1 && (!view_ok(d->dz, a, d->s2d != 0) || (!a.const_stats && (!a.mean || !a.rstd)))) return ESR_E_ARG;
+    if (mode == 2 && !view_ok(d->u, a, false)) return ESR_E_ARG;
     a.sums = sums;
     const long long grid = (long long)a.ncg * a.groups * a.nsplit;
     if (mode == 0) ESR_LAUNCH2(bn_reduce_kernel, 0, false, grid, a);
@@ -406,12 +415,12 @@ extern "C" int esr_bn_apply(const esr_bn_desc* d, int mode, esr_stream_t stream)
     BnArgs a{};
     const int rc = fill_common(a, d);
     if (rc != ESR_OK) return rc;
-    if (mode < 0 || mode > 2) return ESR_E_ARG;
+    if (mode < 0 || mode > 2 || !affine_ok(d)) return ESR_E_ARG;
     const bool s2d = d->s2d != 0;
-    if (mode == 0 && !s2d_view_ok(a.out0, a, s2d)) return ESR_E_ARG;
-    if (mode >= 1 && !s2d_view_ok(a.dz, a, s2d)) return ESR_E_ARG;
-    if (mode == 1 && !s2d_view_ok(a.out0, a, false)) return ESR_E_ARG;
-    if (mode == 2 && (!s2d_view_ok(a.u, a, false) || !s2d_view_ok(a.out0, a, s2d) || !s2d_view_ok(a.out1, a, false))) return ESR_E_ARG;
+    if (mode == 0 && !view_ok(d->out0, a, s2d)) return ESR_E_ARG;
+    if (mode >= 1 && !view_ok(d->dz, a, s2d)) return ESR_E_ARG;
+    if (mode == 1 && !view_ok(d->out0, a, false)) return ESR_E_ARG;
+    if (mode == 2 && (!view_ok(d->u, a, false) || !view_ok(d->out0, a, s2d) || !view_ok(d->out1, a, false))) return ESR_E_ARG;
     if (mode >= 1 && !a.const_stats && (!a.mean || !a.rstd || !a.s2 || (mode == 2 && !a.s3))) return ESR_E_ARG;
     // pixels per thread: 4 (2 for the three-operand double backward: registers) on planes that fill such blocks, else 1
     const long long hw = (long long)a.H * a.W;
@@ -432,7 +441,7 @@ extern "C" int esr_bn_finalize_apply(const esr_bn_desc* d, const esr_cmd_bn_fina
     if (!f || !f->sums || !f->mean || !f->rstd || !f->scale || !f->shift || f->groups != d->groups || f->C != d->C || d->const_stats) return ESR_E_ARG;
     if (f->n_per_group != a.npg) return ESR_E_ARG;
     const bool s2d = d->s2d != 0;
-    if (!s2d_view_ok(a.out0, a, s2d)) return ESR_E_ARG;
+    if (!view_ok(d->out0, a, s2d)) return ESR_E_ARG;
     a.fin_sums = f->sums; a.eps = f->eps; a.momentum = f->momentum; a.gamma = f->gamma; a.beta = f->beta;
     a.o_mean = f->mean; a.o_rstd = f->rstd; a.o_scale = f->scale; a.o_shift = f->shift; a.run_mean = f->running_mean; a.run_var = f->running_var;
     const long long hw = (long long)a.H * a.W;

@@ -568,10 +568,13 @@ int esr_pairmin_grad(const float* x, int Bg, int C, int H, int W, int lo, int hi
  *                                                                                          esr_bn_param_grads
  * groups: the B images are `groups` runs of B/groups consecutive images, each normalised with its OWN batch statistics (the critic's
  * separate calls on the real, fake and interpolated batches executed as one launch); all per-channel arrays are [groups][C] except gamma /
- * beta / running_* ([C]).  scale == NULL: no normalisation (the first conv block has none) — then const_stats must be 1.  const_stats: the
- * affine map does not depend on y (eval-mode BatchNorm with running statistics, or no norm).  s2d: dz (modes 1, 2), out0 of mode 0 and out0 of
- * mode 2 are stored space-to-depth: logical pixel (y, x) of group cg at pixel (y/2, x/2) of group 4*cg + 2*(y&1) + (x&1) of a view with
- * H/2 x W/2 pixels — the input layout in which the next block's 4x4 stride-2 conv is a 3x3 stride-1 conv over 4x the channels.
+ * beta / running_* ([C]).  scale == NULL: no normalisation (the first conv block has none) — then const_stats must be 1 (esr_bn_reduce and
+ * esr_bn_apply return ESR_E_ARG otherwise).  const_stats: the affine map does not depend on y (eval-mode BatchNorm with running statistics,
+ * or no norm).  s2d: dz (modes 1, 2), out0 of mode 0 and out0 of mode 2 are stored space-to-depth: logical pixel (y, x) of group cg at pixel
+ * (y/2, x/2) of group 16*(cg/4) + 4*s + cg%4, s = 2*(y&1) + (x&1), of a view with H/2 x W/2 pixels (four consecutive groups share a parity) —
+ * the input layout in which the next block's 4x4 stride-2 conv is a 3x3 stride-1 conv over 4x the channels.
+ * View sizes: with n = ceil(C/8), y and every plain view must declare ncg >= n and H x W pixels; a space-to-depth view H/2 x W/2 pixels and
+ * ncg >= 16*((n-1)/4) + (n-1)%4 + 13, one more than the largest group index above (4*n when n is a multiple of 4); ESR_E_ARG otherwise.
  * `sums` targets must be zeroed by the caller (the kernels add); sums2 / sums3: completed results of mode 1 / mode 2. */
 typedef struct {
     esr_act_view y;          /* the conv's output (pre-normalisation); defines B x C x H x W */

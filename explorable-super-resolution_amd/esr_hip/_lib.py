@@ -159,6 +159,7 @@ _SIGS = {
     'esr_adam_table': (C.c_int64, [C.POINTER(AdamTensor), C.c_int, C.c_void_p, C.c_int64]),
     'esr_adam_run': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     'esr_run': (C.c_int, [C.POINTER(Cmd), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    'esr_run_lanes': (C.c_int, [C.POINTER(C.POINTER(Cmd)), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     'esr_cmd_bytes': (C.c_int64, []),
     'esr_version': (C.c_int, []),
     'esr_conv3x3': (C.c_int, [C.POINTER(Conv3x3Desc), C.c_void_p]),

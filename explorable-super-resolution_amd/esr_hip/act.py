@@ -89,6 +89,15 @@ class Recorder:
                 return name, ptr - base
         return None
 
+    def append(self, other):
+        """The items of `other` (a recording of the same pass over other images, same externals) joined to this one's, segment by segment:
+        one lane that runs several sub-batches one after the other.  The host ops stay this recording's."""
+        assert [k for k, _ in other.items] == [k for k, _ in self.items], 'sub-batches of one pass have the same segments'
+        for (kind, mine), (_, theirs) in zip(self.items, other.items):
+            if kind == 'cmds':
+                mine.extend(theirs)
+        self.keep.extend(other.keep)
+
     def finish(self):
         plan = Plan()
         plan.keep = self.keep
@@ -111,17 +120,45 @@ class Recorder:
 
 
 class Plan:
+    """Recorded launch lists.  `side`: the plans of lanes 1.. of a pass recorded as independent lanes (with_lanes) — the same sequence of
+    segments and host ops over other images; run() then replays every segment with one esr_run_lanes call, this plan's commands on the
+    caller's stream and the side lanes' on the library's side streams, and calls this plan's host ops between the segments, on the caller's
+    stream (behind one segment's join, in front of the next one's fork)."""
+
     def __init__(self):
         self.items, self.patches, self.keep, self.n_cmds = [], [], [], 0
-        self._failed = C.c_int(-1)
+        self.side = []
+        self._failed, self._failed_lane = C.c_int(-1), C.c_int(-1)
+        self._lane_args = None
+
+    def with_lanes(self, side):
+        for p in side:
+            assert [callable(i) for i in p.items] == [callable(i) for i in self.items], 'lanes of one pass have the same segments'
+        self.side = list(side)
+        self._lane_args = {}
+        for k, item in enumerate(self.items):
+            if not callable(item):
+                arrs = [item] + [p.items[k] for p in self.side]
+                self._lane_args[k] = (arrs, (C.POINTER(_lib.Cmd) * len(arrs))(*[C.cast(a, C.POINTER(_lib.Cmd)) for a in arrs]),
+                                      (C.c_int * len(arrs))(*[len(a) for a in arrs]))
+        return self
 
     def run(self, externals, ctx=None):
-        for member, field, name, off in self.patches:
-            setattr(member, field, externals[name].data_ptr() + off)
+        for plan in [self] + self.side:
+            for member, field, name, off in plan.patches:
+                setattr(member, field, externals[name].data_ptr() + off)
         s = stream_ptr()
-        for item in self.items:
+        for k, item in enumerate(self.items):
             if callable(item):
                 item(ctx)
+                continue
+            if self.side:
+                arrs, ptrs, ns = self._lane_args[k]
+                rc = _lib.lib.esr_run_lanes(ptrs, ns, len(arrs), C.byref(self._failed_lane), C.byref(self._failed), s)
+                if rc != 0:
+                    lane, i = self._failed_lane.value, self._failed.value
+                    op = arrs[lane][i].op if 0 <= lane < len(arrs) and 0 <= i < len(arrs[lane]) else -1
+                    check(rc, 'esr_run_lanes: lane %d, command %d (%s)' % (lane, i, _lib.CMD_MEMBER.get(op, '?')))
                 continue
             rc = _lib.lib.esr_run(item, len(item), C.byref(self._failed), s)
             if rc != 0:
@@ -219,6 +256,23 @@ class ActBuf:
         v = self.view(cg0, (nc + 7) // 8)
         check(_lib.lib.esr_unpack_nchw(C.byref(v), self.B, nc, out.data_ptr(), stream_ptr()), 'esr_unpack_nchw')
         return out
+
+
+class LaneBuf:
+    """Images [b0, ..) of an ActBuf, for a pass over a sub-batch of the same buffer set: ActBuf's views with the base moved by
+    b0 * batch_stride (a view has no batch size: the launch says how many images)."""
+
+    def __init__(self, buf, b0):
+        self.buf, self.off = buf, b0 * buf.batch_stride * 16
+        self._views = {}
+
+    def view(self, cg0=0, ncg=None, with_lo=True):
+        key = (cg0, ncg, with_lo)
+        v = self._views.get(key)
+        if v is None:
+            w = self.buf.view(cg0, ncg, with_lo)
+            v = self._views[key] = ActView(w.hi + self.off, (w.lo + self.off) if w.lo else None, w.ncg, w.H, w.W, w.batch_stride, w.cg_stride, w.fmt)
+        return v
 
 
 NO_VIEW = ActView(None, None, 0, 0, 0, 0, 0, 0)
@@ -584,6 +638,57 @@ class PackedSum(_Pack):
 
 _launch_parity = 0
 LDS_STAGES = 0              # esr_conv3x3_desc.lds_stages of every launch built here: 0 = the library picks by launch size, 1 / 2 = that form
+
+
+# ---- which inference forwards run as half-batch lanes on two streams (Plan.with_lanes, esr_run_lanes) ----
+# A conv launch of T tiles over S = 2 * CUs resident workgroup slots ends in a part-empty round, and the next launch of the chain cannot
+# start before its last tile is done; a second, independent chain over the other half of the images fills those tails and the launch ramps.
+# Measured on the configs[1] forward in 'split' (32 x 148^2: 1920 tiles per dense-block launch, 3.75 rounds of 512 slots), fresh processes
+# alternating, 20 steps each, ms per step (profiles/r08_lanes_ab.log):
+#     whole batch 67.97 .. 68.08 | 2 x 16 images on two streams 66.38 .. 66.55 | 4 x 8 round-robin on two streams 66.03 .. 66.42
+# 2 x 16 is the form taken: the same gain within the spread of 4 x 8 for half the launches (702 against 1404 per forward, which is what the
+# host has to stay ahead of), and lanes of 960 tiles keep both workgroups of every CU busy while 8 images (480 tiles) do not.
+#   * precisions not in the table stay single-lane: 'mixed' lost 20 % in the two-stream experiment of profiles/r04_exp_two_stream_lanes_ab.log
+#     and was not measured again, the one-plane modes were never measured;
+#   * a lane with fewer tiles than slots stays single-lane: such launches do not fill the device once, halving them only adds launches
+#     (configs[2]'s 32 x 52^2, single images, configs[0]);
+#   * beyond LANE_MAX_ROUNDS rounds per whole-batch launch nothing was measured (the measured launch has 3.75), and the part-empty round
+#     that lanes fill is a smaller share of a longer launch: single-lane until somebody measures it.
+LANE_TABLE = {'split': 2}
+LANE_MAX_ROUNDS = 4
+
+
+def forward_lane_count(precision, lane_tiles, cus):
+    """Lanes (1: none) for an inference forward in `precision` whose dense-block launch would have `lane_tiles` tiles in its SMALLEST lane
+    if it ran as LANE_TABLE[precision] lanes, on a device of `cus` compute units."""
+    lanes = LANE_TABLE.get(precision, 1)
+    slots = 2 * cus
+    if lanes < 2 or lane_tiles < slots or lane_tiles * lanes > LANE_MAX_ROUNDS * slots:
+        return 1
+    return lanes
+
+
+def dense_conv_tiles(H, W, planes):
+    """Tiles per image of a dense-block conv launch (32 output channels) over H x W pixels, as the library cuts them (esr_conv3x3_tiling: a
+    host-only query; the operand addresses are never read)."""
+    d = _lib.Conv3x3Desc()
+    d.in1 = ActView(16, 16 if planes == 2 else None, 8, H, W, 8 * (H + 2) * (W + 2), (H + 2) * (W + 2), 0)
+    d.cout, d.B, d.H, d.W = 32, 1, H, W
+    t = (C.c_int32 * 4)()
+    check(_lib.lib.esr_conv3x3_tiling(C.byref(d), t), 'esr_conv3x3_tiling')
+    return t[0] * t[1]
+
+
+def lane_batches(B, lanes, subs=None):
+    """[[(b0, nb), ...] per lane]: B images cut into `subs` sub-batches (default: one per lane) of sizes that differ by at most one, the larger
+    first, dealt round-robin over the lanes."""
+    subs = min(B, subs or lanes)
+    out, b0 = [[] for _ in range(min(lanes, subs))], 0
+    for j in range(subs):
+        nb = B // subs + (1 if j < B % subs else 0)
+        out[j % len(out)].append((b0, nb))
+        b0 += nb
+    return out
 
 
 def reset_launch_parity():

@@ -56,6 +56,10 @@ class RRDBEngine:
         self._ptr_fp, self._ptr_epoch = None, 0   # parameter storages the recorded descriptors point into; epoch moves when any changes
         self.generation = 0  # bumped by invalidate(): consumers that cache derived state (GraphedForward) compare it
         self._ev = None      # optional (start, end) torch.cuda.Event pair bracketing the conv launches of one forward (bench.py)
+        # inference forwards as two half-batch lanes on two streams (_lane_layout): None = where A.forward_lane_count measured it faster,
+        # 1 = never, 2 = always (tests, A/Bs); forward_sub_batches: with forced lanes, the sub-batches dealt round-robin over them
+        self.forward_lanes, self.forward_sub_batches = None, None
+        self._layouts = {}
         # fp16 range watch (precisions 'f16', 'f16x2', 'mixed'): the forward's conv launches report the first layer whose stored activations
         # reach 2^15 or are not finite into one device word (A.RangeWatch); it is copied to pinned host memory behind every forward and looked at
         # without synchronising at the start of the next one — or, synchronising, by check_range().  The reference's fp32 path has no such cliff
@@ -407,18 +411,63 @@ class RRDBEngine:
                 self._forward_launches(x, pad, keep, bufs, g)
             self._post_range()
             return g, bufs
-        key = self._plan_key('fwd', tuple(x.shape), pad, keep)
+        layout = self._lane_layout(B, h0 + 2 * pad, w0 + 2 * pad, x.device, keep)
+        key = self._plan_key('fwd', tuple(x.shape), pad, keep, layout)
         plan = bufs['_plans'].get(key)
         if plan is None:
-            rec = A.Recorder({'x': x, 'g': g})
-            if watch is not None:
-                watch.names = []              # (every forward of this network issues the same launches in the same order: one name list serves all plans)
-            with A.recording(rec), A.watching(watch):
-                self._forward_launches(x, pad, keep, bufs, g)
-            plan = bufs['_plans'][key] = rec.finish()
+            # one recording per sub-batch ((0, B): the whole batch), each over its own images of the same buffer set, x and g
+            recs = []
+            for subs in layout or (((0, B),),):
+                for j, (b0, nb) in enumerate(subs):
+                    rec = A.Recorder({'x': x, 'g': g})
+                    if watch is not None:
+                        watch.names = []          # (every forward of this network issues the same launches in the same order: one name list serves all plans)
+                    sub_bufs = bufs if nb == B else self._lane_bufs(bufs, b0)
+                    with A.recording(rec), A.watching(watch):
+                        self._forward_launches(x[b0:b0 + nb], pad, keep, sub_bufs, g[b0:b0 + nb])
+                    if j:
+                        recs[-1].append(rec)
+                    else:
+                        recs.append(rec)
+            plans = [rec.finish() for rec in recs]
+            plan = bufs['_plans'][key] = plans[0].with_lanes(plans[1:]) if len(plans) > 1 else plans[0]
         plan.run({'x': x, 'g': g})
         self._post_range()
         return g, bufs
+
+    # ---- inference forwards as lanes
+    def _lane_layout(self, B, h, w, dev, keep):
+        """How a recorded forward over B images of h x w is cut into lanes: None (one list on the caller's stream) or a tuple of lanes, each a
+        tuple of (first image, images) sub-batches that the lane runs one after the other (Plan.with_lanes).  Only forwards that keep nothing for a
+        backward pass, outside a graph capture; forward_lanes = None asks A.forward_lane_count (the measured rule), an integer forces that many
+        lanes (1: none) and forward_sub_batches then how many sub-batches they share (default: one each)."""
+        if keep is not False or B < 2 or torch.cuda.is_current_stream_capturing():
+            return None
+        key = (B, h, w, dev, self.split, self.forward_lanes, self.forward_sub_batches)
+        if key in self._layouts:
+            return self._layouts[key]
+        lanes = self.forward_lanes
+        if lanes is None:
+            precision = self.split if isinstance(self.split, str) else ('split' if self.split else 'bf16')
+            n = A.LANE_TABLE.get(precision, 1)
+            cus = torch.cuda.get_device_properties(dev).multi_processor_count
+            lanes = A.forward_lane_count(precision, (B // n) * A.dense_conv_tiles(h, w, A.act_planes(self.split)[0]), cus)
+        layout = None
+        if lanes >= 2:      # (never more than two streams for a forward: three and four measured slower, DESIGN_HISTORY 5.10)
+            layout = tuple(tuple(subs) for subs in A.lane_batches(B, 2, self.forward_sub_batches if self.forward_lanes else None))
+        if len(self._layouts) > 16:
+            self._layouts.clear()
+        self._layouts[key] = layout
+        return layout
+
+    @staticmethod
+    def _lane_bufs(bufs, b0):
+        """The buffer set seen from image b0 on (A.LaneBuf): what a sub-batch's launches are recorded over."""
+        def lane(v):
+            if isinstance(v, A.ActBuf):
+                return A.LaneBuf(v, b0)
+            return [lane(e) for e in v] if isinstance(v, list) else v
+        return {k: lane(v) for k, v in bufs.items()}
 
     def _forward_launches(self, x, pad, keep, bufs, g):
         """The launch sequence of one forward pass over `bufs` into `g` (issued directly, or collected by an active A.Recorder)."""

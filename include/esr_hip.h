@@ -656,6 +656,18 @@ typedef struct {
     } u;
 } esr_cmd;
 int esr_run(const esr_cmd* cmds, int n, int* failed, esr_stream_t stream);
+/* `lanes` (1 .. ESR_MAX_LANES) INDEPENDENT launch lists side by side: lists that touch disjoint data (the sub-batches of an inference
+ * forward), so that one list's launches fill the part-empty last tile round and the ramp of the other's.  cmds[l] / n[l] is lane l's list.
+ * Lane 0 is enqueued on `main`, lanes 1.. on side streams the library owns (created once per device at first use, non-blocking, kept for
+ * the life of the process; at most ESR_MAX_LANES - 1, so that with the caller's stream a process stays within HIP's default four hardware
+ * queues).  The commands are issued interleaved — command i of every lane, then command i + 1 of every lane — not lane by lane.  The side
+ * lanes start behind everything `main` held at the call (fork event) and `main` continues behind their last commands (join events): to the
+ * caller the call is ordered on `main` like esr_run.  lanes == 1 is esr_run.  A failing command ends the issue with its ESR_E_* code,
+ * *failed_lane / *failed (if given) its lane and index; the join is enqueued all the same.  ESR_E_ARG: lanes out of range, cmds or n NULL,
+ * n[l] < 0, n[l] > 0 with cmds[l] NULL.  ESR_E_UNSUPPORTED: lanes > 1 while `main` is being captured into a graph.  Calls are serialised
+ * inside the library (the side streams are shared by all callers of a device). */
+#define ESR_MAX_LANES 4
+int esr_run_lanes(const esr_cmd* const* cmds, const int* n, int lanes, int* failed_lane, int* failed, esr_stream_t main);
 int64_t esr_cmd_bytes(void);       /* sizeof(esr_cmd): lets a binding check its struct layout */
 
 /* ---- explorable JPEG decoding: the 8x8 block DCT consistency layer (codes/JPEG_module/JPEG.py, Y channel, block size 8) ----

@@ -60,6 +60,17 @@ class AdamTensor(C.Structure):
     _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('n', C.c_int64)]
 
 
+class DataItem(C.Structure):
+    """esr_data_item (include/esr_hip.h)."""
+    _fields_ = [('hr', C.c_void_p), ('lr', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('stride', C.c_int32), ('channels', C.c_int32),
+                ('y0', C.c_int32), ('x0', C.c_int32), ('flags', C.c_int32), ('lr_H', C.c_int32), ('lr_W', C.c_int32), ('lr_stride', C.c_int32)]
+
+
+class DataChannelMap(C.Structure):
+    """esr_data_channel_map (include/esr_hip.h)."""
+    _fields_ = [('mode', C.c_int32), ('reserved', C.c_int32), ('w', C.c_double * 3), ('b', C.c_double), ('scale', C.c_double)]
+
+
 # ---- launch lists (esr_cmd / esr_run, include/esr_hip.h)
 OP_CONV3X3, OP_PACK_NCHW, OP_UNPACK_GRAD_NCHW, OP_ACT_COMBINE, OP_PIXEL_UNSHUFFLE, OP_GRAD_ABSMAX, OP_GRAD_SCALE, OP_WGRAD_BATCH_RUN, \
     OP_PACK_BATCH_RUN, OP_ZERO, OP_UNPACK_NCHW, OP_WGRAD, OP_BN_REDUCE, OP_BN_APPLY, OP_BN_FINALIZE, OP_BN_PARAM_GRADS, \
@@ -265,6 +276,9 @@ _SIGS = {
                                 C.c_void_p]),
     'esr_sample_std_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     'esr_sample_std': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'esr_data_lrhr_plan': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    'esr_data_lrhr_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(DataChannelMap), C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -314,6 +328,8 @@ lib = _LazyLib()
 
 ESR_OK, ESR_E_ARG, ESR_E_UNSUPPORTED, ESR_E_LAUNCH = 0, -1, -2, -3
 PIXELS_FLOAT, PIXELS_ROUND, PIXELS_RAW = 0, 1, 2     # esr_psnr_ssim `quantize`
+DATA_HFLIP, DATA_VFLIP, DATA_TRANSPOSE = 1, 2, 4      # esr_data_item `flags`
+DATA_MAP_RGB, DATA_MAP_MIX = 0, 1                     # esr_data_channel_map `mode`
 PACK_FOLD2 = 2              # esr_pack_conv_weights / esr_pack_desc `transposed` = PACK_FOLD2 + first phase: the folded pack of a phase launch
 _ERR = {-1: 'ESR_E_ARG (bad argument)', -2: 'ESR_E_UNSUPPORTED (unsupported shape)', -3: 'ESR_E_LAUNCH (HIP launch error)'}
 

@@ -788,6 +788,53 @@ int esr_psnr_ssim(const float* a, const float* b, int B, int C, int H, int W, fl
 int64_t esr_sample_std_partials(int C, int H, int W);
 int esr_sample_std(const float* x, int S, int B, int C, int H, int W, float* map, double* partial, double* sums, esr_stream_t stream);
 
+/* ---- LR/HR training batches from images resident on the device (codes/data/LRHR_dataset.py:48-131, codes/data/util.py:95-130) ----
+ * One item of a batch: where its decoded image lies and which crop and augmentation were drawn for it.  Images are HWC uint8, 3 channels in BGR
+ * order (cv2.imread's) or 1 channel.  H and W are the LOGICAL size: they may be smaller than what is stored (util.modcrop of the validation phase is
+ * expressed this way) and every replicate-padding clamp uses them; `stride` is the stored row length in pixels.  (y0, x0) is the origin of the
+ * ph x pw HR crop, both multiples of sf.  flags: util.augment's decisions, applied hflip, then vflip, then transpose.  lr != NULL: the LR image is
+ * supplied (dataroot_LR), same channel count, lr_H x lr_W with row stride lr_stride, and is cropped at (y0 / sf, x0 / sf) instead of synthesised. */
+#define ESR_DATA_HFLIP 1
+#define ESR_DATA_VFLIP 2
+#define ESR_DATA_TRANSPOSE 4       /* needs ph == pw */
+typedef struct {
+    const uint8_t* hr;
+    const uint8_t* lr;
+    int32_t H, W, stride, channels;
+    int32_t y0, x0;
+    int32_t flags;
+    int32_t lr_H, lr_W, lr_stride;
+} esr_data_item;
+/* What a source pixel becomes (host struct, read during the call).
+ *   ESR_DATA_MAP_RGB: every byte v becomes float(v) / 255 (an IEEE fp32 division: bit-identical to u8.astype(float32) / 255.); 3 channels are
+ *     re-ordered BGR -> RGB; w, b, scale are not read.
+ *   ESR_DATA_MAP_MIX: a 3-channel pixel becomes the ONE value ((w . (scale x)) / scale + b) / scale with x = float(bgr) / 255 and scale x in fp32,
+ *     the rest in fp64, rounded to fp32 once — util.bgr2ycbcr(only_y=True) on a float32 image with w = (24.966, 128.553, 65.481), b = 16,
+ *     scale = 255 (color 'y'); w = (0.114, 0.587, 0.299), b = 0, scale = 1 is a plain dot product (color 'gray').  1-channel sources pass through
+ *     as v / 255.  The map is applied per source pixel, before the LR filter, as the reference converts img_HR before imresize. */
+#define ESR_DATA_MAP_RGB 0
+#define ESR_DATA_MAP_MIX 1
+typedef struct { int32_t mode, reserved; double w[3]; double b; double scale; } esr_data_channel_map;
+/* esr_data_lrhr_batch — hr fp32 [B][Co][ph][pw] and lr fp32 [B][Co][ph/sf][pw/sf] of B items in ONE launch; Co = 1 under ESR_DATA_MAP_MIX, else
+ *   the items' channel count (the same for all).  Before augmentation, hr is the crop of the mapped image x and, with i0 = y0 / sf, j0 = x0 / sf,
+ *   half = k / 2,
+ *     lr[i][j] = sum_{u,v} taps[u][v] x[clamp(pre + sf (i0 + i) + half - u, 0, H - 1)][clamp(pre + sf (j0 + j) + half - v, 0, W - 1)]
+ *   — CEM.imresize_CEM.imresize(x, [1 / sf]) of the WHOLE image (replicate padding at the IMAGE border, never at the crop's), cropped afterwards,
+ *   for taps = rot90(upscale kernel / sf^2, 2), device fp32 [k][k], any 2-D kernel (k odd, <= 63), and pre = calc_strides' (in [0, sf)); fp32
+ *   accumulation, u outer and v inner.  Items with an LR image get its plain crop through the same map; taps may be NULL when all have one.
+ *   `items` is the HOST copy of the table (read during the call: the arguments are checked against it), `items_dev` the same B structs in device
+ *   memory, which the kernel reads — the caller copies them on `stream` before the call (one pinned, asynchronous copy).
+ *   ESR_E_ARG, with nothing written: a NULL pointer; sf < 1; ph or pw no multiple of sf; k even or > 63; pre outside [0, sf); an origin that
+ *   is negative or no multiple of sf; a crop that leaves the logical image (or the LR image); channels other than 1 / 3 or differing Co;
+ *   transpose with ph != pw; stride < W.  ESR_E_UNSUPPORTED: no tile fits on chip for (sf, k), or B > 65535.
+ * esr_data_lrhr_plan — the launch plan, decided from (sf, k, pre) alone: tile_lo_win[0] = T, the LR tile side of a workgroup (T sf HR pixels),
+ *   [1] = window pixels staged before the HR tile's first row / column, [2] = the window's side in source pixels.  T is the largest power of two
+ *   up to 8 whose window fits 64 KiB of LDS at 4 bytes per pixel (at least two workgroups per CU): 8 for (sf 4, k 17) and for (sf 8, k 45), 4 for
+ *   (sf 16, k 63).  Small tiles on purpose: a training batch is then some 1500 short workgroups, six or more resident per CU. */
+int esr_data_lrhr_plan(int sf, int k, int pre, int32_t* tile_lo_win);
+int esr_data_lrhr_batch(const esr_data_item* items, const esr_data_item* items_dev, int B, int sf, const float* taps, int k, int pre, int ph, int pw,
+                        const esr_data_channel_map* map, float* hr, float* lr, esr_stream_t stream);
+
 int esr_version(void);
 
 #ifdef __cplusplus

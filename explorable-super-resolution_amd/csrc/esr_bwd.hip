@@ -8,6 +8,8 @@
 //   ReplicationPad2d            codes/CEM/CEMnet.py:70-71,286-295                           -> fold the pad ring into the edge pixels
 //   bilinear /sf of the latent  codes/models/modules/architecture.py:284                    -> spread each LR gradient over its taps
 #include "esr_common.h"
+#include <cstring>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -444,6 +446,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, const int group, 
     // workgroup (relative offset + row / column inside the haloed tile) — so that a tile costs per slot two compares against the tile's distance
     // to the image edge, one add and one select, and the copy takes a uniform base + a 32-bit lane offset.  (The general macro above spends
     // ~12 VALU per slot and a 64-bit add per plane: 4.8 VALU per MFMA in this kernel's counters, profiles/r04_wgrad_pmc.json.)
+    // (the host states the same rule as WgradPlan.fast_copy, for ESR_WGRAD_FORM_FAST_COPY: keep the two in step)
     const bool fast_issue = NPL == 1 && a.ups == 1;      // (one-plane operands: the hi+lo kernels sit at the 256-register limit and would spill)
     // only the LAST tile column / row of an image can be partial: per slot two precomputed bits — "inside the image when the tile is in the last
     // column" / "... last row" — packed into one register (slot j: bits 2j, 2j + 1; X slots first, then the dY slots)
@@ -786,48 +789,131 @@ __global__ void wgrad_reduce_batch_kernel(const WgradArgs* __restrict__ table) {
     if (a.nslices > 1) wgrad_reduce_body(a, (long long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
-// grid decomposition shared by the workspace query and the launch
-struct WgradPlan { int tiles_x, tiles_y, ncit_main, ncit, ngroups, nslices, mt, shape; };
-// A MAIN input of <= 3 channels and no latent segment (the critic's first conv on RGB, codes/models/modules/architecture.py:452): its one input
-// tile is run in the latent tile's form — the 27 (tap, channel) columns as ONE MFMA tile (wgrad_body<..., LATK>) — instead of nine 32-wide tiles
-// that are 3/32 full: the layer is presented to the kernel as "no main tiles + a latent tile of cin_main channels".
-static bool main_as_latk(const esr_wgrad_desc* d) { return !d->xlat.hi && d->cin_main <= 3 && d->upsample <= 1; }
-// a latent segment of <= 3 channels: its tile runs the 27-column form too
-static bool lat_as_latk(const esr_wgrad_desc* d) { return d->xlat.hi && d->lat > 0 && d->lat <= 3; }
-static bool desc_is_s2d(const esr_wgrad_desc* d) {
-    return d->tap_masks[0] == 432 && d->tap_masks[1] == 216 && d->tap_masks[2] == 54 && d->tap_masks[3] == 27 && d->cin_main % 128 == 0 &&
-           d->dy.fmt != ESR_FMT_F16;
+// ---- host side: esr_conv3x3_wgrad = wgrad_validate -> wgrad_plan + wgrad_cut -> wgrad_args -> wgrad_launch.  The tiling and workspace queries and
+// the batch entry points (one plan per layer) read the same plan and keep no rule of their own.
+
+// The instantiation that runs (template key) and its LDS.  One-plane operands (bf16 / f16): two stages AND two workgroups per CU (2 x 2 x 38 KB +
+// nothing else = the 160 KB; four tiles of copies in flight per CU): generator launch 6.57 -> 6.14 ms, critic launches 675 -> 575 us at the
+// configs[2] shapes.  hi+lo operands: one stage, two workgroups (two stages would leave one workgroup per CU: measured slower).
+struct WgradKey { int npl, nst, fmt; bool s2d; size_t lds; };
+// `s2d_wanted`: a layer carries the space-to-depth hint or takes the 16x16 / 32x8 tiles.  The space-to-depth kernels exist for bf16 only — the one
+// place where that exception is made: an fp16 layer with the hint keeps tapmode == 1 in its WgradArgs and runs the plain kernel, which ignores it.
+static WgradKey wgrad_key(bool split, bool f16, bool s2d_wanted) {
+    const int npl = split ? 2 : 1, nst = split ? 1 : 2;         // fp16 operands: single plane only (wgrad_validate)
+    const size_t stages = (size_t)nst * npl * (WG_X_BYTES + WG_Y_BYTES), red = (size_t)4 * 5 * 1024 * 4;
+    return {npl, nst, f16 ? ESR_FMT_F16 : ESR_FMT_BF16, s2d_wanted && !f16, stages > red ? stages : red};
 }
+// The one list of instantiations: conv3x3_wgrad_kernel (WG_SINGLE) and conv3x3_wgrad_batch_kernel (WG_BATCH) for every key — bf16 in all forms,
+// fp16 one plane without space-to-depth; the SIDE instantiation (WG_SIDE) for one-plane operands, two stages, no space-to-depth.
+enum { WG_SINGLE, WG_BATCH, WG_SIDE };
+template <int NPL, int NST, int FMT, bool S2D>
+const void* wgrad_pick(int entry) {
+    if constexpr (FMT == ESR_FMT_BF16 || (NPL == 1 && !S2D)) {
+        if (entry == WG_SINGLE) return (const void*)conv3x3_wgrad_kernel<NPL, NST, FMT, S2D>;
+        if (entry == WG_BATCH) return (const void*)conv3x3_wgrad_batch_kernel<NPL, NST, FMT, S2D>;
+        if constexpr (NPL == 1 && NST == 2 && !S2D)
+            if (entry == WG_SIDE) return (const void*)conv3x3_wgrad_batch_kernel<NPL, NST, FMT, false, true>;
+    }
+    return nullptr;
+}
+template <int... I>
+const void* wgrad_walk(int code, int entry, std::integer_sequence<int, I...>) {
+    const void* k = nullptr;
+    ((code == I ? void(k = wgrad_pick<(I & 1) + 1, ((I >> 1) & 1) + 1, (I >> 2) & 1, ((I >> 3) & 1) != 0>(entry)) : void()), ...);
+    return k;
+}
+static const void* wgrad_kernel(const WgradKey& k, int entry) {
+    return wgrad_walk((k.npl - 1) | (k.nst - 1) << 1 | k.fmt << 2 | (k.s2d ? 8 : 0), entry, std::make_integer_sequence<int, 16>{});
+}
+static hipError_t wgrad_allow_lds(const void* k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }   // k varies per call: no caching
+// The one launch site: `kernel` over `grid` workgroups, then — when there are partial sums — `fold` over fold_threads x fold_rows threads.
+// args: the kernel's arguments; the fold kernel takes the first of them.
+static int wgrad_launch(const void* kernel, unsigned grid, size_t lds, const void* fold, int64_t fold_threads, int fold_rows, void** args, hipStream_t s) {
+    if (!kernel) return ESR_E_UNSUPPORTED;
+    (void)wgrad_allow_lds(kernel);
+    ESR_CLEAR_ERR();
+    (void)hipLaunchKernel(kernel, dim3(grid), dim3(256), args, lds, s);
+    ESR_CHECK_LAUNCH();
+    if (fold_threads > 0) {
+        (void)hipLaunchKernel(fold, dim3((unsigned)((fold_threads + 255) / 256), (unsigned)fold_rows), dim3(256), args, 0, s);
+        ESR_CHECK_LAUNCH();
+    }
+    return ESR_OK;
+}
+
+// Everything a weight-gradient launch decides, as plain host arithmetic: wgrad_plan fills the layer's part, wgrad_cut the slices of its pixel sum
+struct WgradPlan {
+    int tiles_x, tiles_y, shape;        // pixel tiles per image and their shape (WgradArgs.shape)
+    int64_t ntiles;                     // ... of all B images
+    int mt, ncit_main, ncit, ngroups;   // 32-channel output tiles; main / all input tiles as the kernel walks them; (input, output) tile pairs
+    int ups, lat, cin_main;             // upsample factor (>= 1); channels of the latent (or 27-column) tile and of the main tiles, as the kernel sees them
+    bool lat27, main27, fast_copy;      // ESR_WGRAD_FORM_LAT27 / _MAIN27 / _FAST_COPY
+    int tapmode;                        // WgradArgs.tapmode: the descriptor carries the space-to-depth hint, whatever its operand format
+    WgradKey key;                       // key.s2d = ESR_WGRAD_FORM_S2D: the space-to-depth kernel runs
+    int nslices;                        // slices of the pixel sum (1: the workgroups add straight into dw / db)
+    unsigned grid;                      // ngroups * nslices workgroups
+    int64_t fold_threads, partial_floats;   // partial sums: the fold kernel's threads (one per element of dw's tiles and of db), floats; 0 with one slice
+};
+
+static bool wgrad_sizes_ok(const esr_wgrad_desc* d) { return d && d->B > 0 && d->H > 0 && d->W > 0 && d->cout > 0 && d->cin_main > 0; }
+// the hint that has a kernel (esr_wgrad_desc.tap_masks): any other mask pattern accumulates all nine taps — zeros where the weights are structurally zero
+static bool s2d_hint(const esr_wgrad_desc* d) { return !memcmp(d->tap_masks, S2D_TAPS, sizeof S2D_TAPS) && d->cin_main % 128 == 0; }
+// the layer runs the space-to-depth kernel on its own; a batch that has such a layer runs it for all its layers
+static bool layer_is_s2d(const esr_wgrad_desc* d) { return wgrad_key(false, d->dy.fmt == ESR_FMT_F16, s2d_hint(d)).s2d; }
+
 // shapes: the launch runs the kernel flavour that has the 16x16 / 32x8 pixel tiles (the space-to-depth one): take the shape with the fewest tiles.
 // Not for upsampled layers, fp16 operands (no such kernel) or layers with a 27-column tile: that form exists for the 8 x 32 tiles only and walks
 // the layer's tiles_x / tiles_y as 8 x 32 tiles.
-static WgradPlan wgrad_plan(const esr_wgrad_desc* d, int target_wgs = 512, bool shapes = false) {
-    WgradPlan p;
+static WgradPlan wgrad_plan(const esr_wgrad_desc* d, bool shapes) {
+    WgradPlan p{};
+    const bool f16 = d->dy.fmt == ESR_FMT_F16;
+    p.ups = d->upsample <= 0 ? 1 : d->upsample;
+    p.lat = d->xlat.hi ? d->lat : 0;
+    p.cin_main = d->cin_main;
+    p.lat27 = p.lat > 0 && p.lat <= 3;                           // a latent segment of <= 3 channels: its tile runs the 27-column form
     p.mt = (d->cout + 31) / 32;
-    p.shape = 0;
+    p.ncit_main = (d->cin_main + 31) / 32;
+    p.ncit = p.ncit_main + (p.lat ? 1 : 0);
+    // A MAIN input of <= 3 channels and no latent segment (the critic's first conv on RGB, codes/models/modules/architecture.py:452): its one input
+    // tile is run in the latent tile's form — the 27 (tap, channel) columns as ONE MFMA tile (wgrad_body<..., LATK>) — instead of nine 32-wide tiles
+    // that are 3/32 full: the layer is presented to the kernel as "no main tiles + a latent tile of cin_main channels" (wgrad_args: of the view x).
+    p.main27 = !d->xlat.hi && d->cin_main <= 3 && p.ups == 1;
+    if (p.main27) { p.ncit_main = 0; p.ncit = 1; p.lat = d->cin_main; p.cin_main = 0; }
+    p.ngroups = p.ncit * p.mt;
     p.tiles_x = (d->W + WG_TW - 1) / WG_TW;
     p.tiles_y = (d->H + WG_TH - 1) / WG_TH;
-    if (shapes && (d->upsample <= 1) && d->dy.fmt != ESR_FMT_F16 && !main_as_latk(d) && !lat_as_latk(d))
+    if (shapes && p.ups == 1 && !f16 && !p.main27 && !p.lat27)
         for (int sh = 1; sh <= 2; ++sh) {
             const int tw = WG_TW >> sh, th = WG_TH << sh;
             const int tx = (d->W + tw - 1) / tw, ty = (d->H + th - 1) / th;
             if ((long long)tx * ty < (long long)p.tiles_x * p.tiles_y) { p.tiles_x = tx; p.tiles_y = ty; p.shape = sh; }
         }
-    p.ncit_main = (d->cin_main + 31) / 32;
-    const int lat = d->xlat.hi ? d->lat : 0;
-    p.ncit = p.ncit_main + (lat ? 1 : 0);
-    if (main_as_latk(d)) { p.ncit_main = 0; p.ncit = 1; }
-    p.ngroups = p.ncit * p.mt;
-    const int ntiles = p.tiles_x * p.tiles_y * d->B;
-    int ns = (target_wgs + p.ngroups - 1) / p.ngroups;   // single launch: ~2 workgroups per CU in total (one resident at a time)
-    if (ns > ntiles) ns = ntiles;
+    p.ntiles = (int64_t)p.tiles_x * p.tiles_y * d->B;
+    p.tapmode = s2d_hint(d) ? 1 : 0;
+    p.key = wgrad_key(d->dy.lo != nullptr, f16, p.tapmode == 1 || p.shape != 0);
+    p.fast_copy = p.key.npl == 1 && p.ups == 1;                  // = wgrad_body's fast_issue (a shared helper changes the hi+lo kernels' code)
+    return p;
+}
+// The pixel sum in `ns` slices, at most one per tile — the one clamp; with it the grid and the partial sums ([group][slice][9*1024], then the bias
+// partials [cout tile][slice][32]).
+static void wgrad_cut(WgradPlan& p, int64_t ns) {
+    if (ns > p.ntiles) ns = p.ntiles;
     if (ns < 1) ns = 1;
-    p.nslices = ns;
+    p.nslices = (int)ns;
+    p.grid = (unsigned)(p.ngroups * p.nslices);
+    p.fold_threads = ns == 1 ? 0 : (int64_t)p.ngroups * 9 * 1024 + p.mt * 32;
+    p.partial_floats = p.fold_threads * ns;
+}
+// the single launch: ~2 workgroups per CU in total (one resident at a time)
+constexpr int WGRAD_SINGLE_WGS = 512;
+static WgradPlan wgrad_plan_single(const esr_wgrad_desc* d) {
+    WgradPlan p = wgrad_plan(d, layer_is_s2d(d));
+    wgrad_cut(p, (WGRAD_SINGLE_WGS + p.ngroups - 1) / p.ngroups);
     return p;
 }
 
 static int wgrad_validate(const esr_wgrad_desc* d) {
-    if (!d || !d->dy.hi || !d->x.hi || !d->dw || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || d->cin_main <= 0) return ESR_E_ARG;
+    if (!wgrad_sizes_ok(d) || !d->dy.hi || !d->x.hi || !d->dw) return ESR_E_ARG;
     const int ups = d->upsample <= 0 ? 1 : d->upsample;
     if (d->x.H * ups != d->H || d->x.W * ups != d->W || d->dy.H != d->H || d->dy.W != d->W) return ESR_E_ARG;
     if (d->xlat.hi && (ups != 1 || d->xlat.H != d->H || d->xlat.W != d->W || d->lat <= 0 || d->lat > 8)) return ESR_E_ARG;
@@ -841,105 +927,64 @@ static int wgrad_validate(const esr_wgrad_desc* d) {
     return ESR_OK;
 }
 
+// the kernel arguments: the descriptor's pointers and sizes and the plan's decisions (nothing is decided here)
 static WgradArgs wgrad_args(const esr_wgrad_desc* d, const WgradPlan& p, float* ws) {
     WgradArgs a{};
-    a.shape = p.shape;
-    a.latk = lat_as_latk(d) ? 1 : 0;
     a.dy = to_dview(d->dy);
     a.x = to_dview(d->x);
-    a.xlat = to_dview(d->xlat);
-    a.lat = d->xlat.hi ? d->lat : 0;
-    a.ups = d->upsample <= 0 ? 1 : d->upsample;
-    a.cout = d->cout;
-    a.cin_main = d->cin_main;
-    a.cin_total = d->cin_main + a.lat;
-    a.B = d->B; a.H = d->H; a.W = d->W;
-    a.Wx_p = d->x.W + 2;
-    a.tiles_x = p.tiles_x;
-    a.tiles_y = p.tiles_y;
-    a.ncit_main = p.ncit_main;
-    a.ncit = p.ncit;
-    a.mt = p.mt;
-    a.ngroups = p.ngroups;
-    a.nslices = p.nslices;
-    a.alpha = d->alpha;
-    a.dw = d->dw;
-    a.db = d->db;
-    a.ws = ws;
-    // (a hint: any other mask pattern accumulates all nine taps — zeros where the weights are structurally zero)
-    a.tapmode = (d->tap_masks[0] == 432 && d->tap_masks[1] == 216 && d->tap_masks[2] == 54 && d->tap_masks[3] == 27 && d->cin_main % 128 == 0) ? 1 : 0;
-    if (main_as_latk(d)) {
-        a.xlat = a.x;
-        a.lat = d->cin_main;
-        a.cin_main = 0;
-        a.latk = 1;
-    }
-
+    a.xlat = to_dview(p.main27 ? d->x : d->xlat);
+    a.lat = p.lat; a.ups = p.ups; a.cout = d->cout; a.cin_main = p.cin_main; a.cin_total = p.cin_main + p.lat;
+    a.B = d->B; a.H = d->H; a.W = d->W; a.Wx_p = d->x.W + 2;
+    a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.nslices = p.nslices;
+    a.ncit_main = p.ncit_main; a.ncit = p.ncit; a.mt = p.mt; a.ngroups = p.ngroups;
+    a.alpha = d->alpha; a.dw = d->dw; a.db = d->db; a.ws = ws;
+    a.tapmode = p.tapmode; a.latk = p.lat27 || p.main27; a.shape = p.shape;
     return a;
-}
-
-static inline int64_t wgrad_partial_floats(const WgradPlan& p) {
-    return p.nslices == 1 ? 0 : (int64_t)p.ngroups * p.nslices * (9 * 1024) + (int64_t)p.mt * p.nslices * 32;
-}
-
-// LDS stages of the tile loop.  One-plane operands (bf16 / f16): two stages AND two workgroups per CU (2 x 2 x 38 KB + nothing else = the
-// 160 KB; four tiles of copies in flight per CU): generator launch 6.57 -> 6.14 ms, critic launches 675 -> 575 us at the configs[2] shapes.
-// hi+lo operands: one stage, two workgroups (two stages would leave one workgroup per CU: measured slower).
-static int wgrad_stages(bool one_plane) { return one_plane ? 2 : 1; }
-static size_t wgrad_lds(int npl, int nst) {
-    const size_t stages = (size_t)nst * npl * (WG_X_BYTES + WG_Y_BYTES), red = (size_t)4 * 5 * 1024 * 4;
-    return stages > red ? stages : red;
 }
 
 // batch layout inside the caller's workspace: [WgradArgs table][int4 workgroup map][fp32 partial sums]
 // Work unit = one (layer, input tile, output tile) block over one image tile.  Every layer's pixel sum is cut into as many slices as
 // it takes to keep a workgroup's share near total / 768 (three waves of workgroups over the chip): with hundreds of equal layers
 // that is one slice each (no partial sums at all), a few big high-resolution layers get several, a small net gets many.
-struct BatchPlan { int64_t unit, nwg, table_bytes, map_bytes, partial_floats; bool shapes; };
+struct BatchPlan {
+    int64_t unit, nwg, table_bytes, map_bytes, partial_floats;
+    bool shapes;
+    std::vector<WgradPlan> layers;                               // every layer planned once, cut by `unit`
+    int64_t bytes() const { return table_bytes + map_bytes + (partial_floats + 1) * 4; }
+};
 // esr_conv3x3_wgrad_batch_unit's answer = the slicing granule | this bit when the whole set runs the 16x16 / 32x8 tile shapes (it has a
 // space-to-depth layer): a part without one must still tile its layers as the one launch does
 constexpr int64_t UNIT_SHAPES = (int64_t)1 << 48;
-static WgradPlan batch_entry_plan(const esr_wgrad_desc* d, int64_t unit, bool shapes) {
-    WgradPlan p = wgrad_plan(d, 1, shapes);
-    const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y * d->B;
-    int64_t ns = (ntiles + unit - 1) / unit;
-    if (ns > ntiles) ns = ntiles;
-    if (ns < 1) ns = 1;
-    p.nslices = (int)ns;
-    return p;
-}
-static bool batch_is_s2d(const esr_wgrad_desc* descs, int n) {
-    for (int i = 0; i < n; ++i)
-        if (desc_is_s2d(&descs[i])) return true;
-    return false;
-}
-// The work items of one layer, slice-major so that co-running workgroups of one layer read different images
-static void entry_work(int i, const WgradPlan& p, std::vector<int4>& pairs) {
-    for (int sl = 0; sl < p.nslices; ++sl)
-        for (int g = 0; g < p.ngroups; ++g) pairs.push_back(make_int4(i, g, sl, 0));
-}
-static BatchPlan batch_plan(const esr_wgrad_desc* descs, int n, int64_t unit_override = 0) {
-    BatchPlan b{};
-    int64_t work = 0;
-    // the tile shapes and slicing of a LARGER set this one is a part of (esr_conv3x3_wgrad_batch_unit)
-    const bool shapes = b.shapes = unit_override > 0 ? (unit_override & UNIT_SHAPES) != 0 : batch_is_s2d(descs, n);
+// unit_override > 0: the tile shapes and slicing of a LARGER set this one is a part of (esr_conv3x3_wgrad_batch_unit)
+static int batch_plan(const esr_wgrad_desc* descs, int n, int64_t unit_override, BatchPlan& b) {
+    if (!descs || n <= 0 || unit_override < 0) return ESR_E_ARG;
+    b = BatchPlan{};
     for (int i = 0; i < n; ++i) {
-        const WgradPlan p = wgrad_plan(&descs[i], 1, shapes);
-        work += (int64_t)p.ngroups * p.tiles_x * p.tiles_y * descs[i].B;
+        if (!wgrad_sizes_ok(&descs[i])) return ESR_E_ARG;
+        b.shapes = b.shapes || layer_is_s2d(&descs[i]);
+    }
+    if (unit_override > 0) b.shapes = (unit_override & UNIT_SHAPES) != 0;
+    int64_t work = 0;
+    for (int i = 0; i < n; ++i) {
+        b.layers.push_back(wgrad_plan(&descs[i], b.shapes));
+        work += b.layers[i].ngroups * b.layers[i].ntiles;
     }
     b.unit = work / 768 > 0 ? work / 768 : 1;
     if (unit_override > 0) b.unit = unit_override & (UNIT_SHAPES - 1);
     if (b.unit < 1) b.unit = 1;
-    for (int i = 0; i < n; ++i) {
-        const WgradPlan p = batch_entry_plan(&descs[i], b.unit, shapes);
+    for (WgradPlan& p : b.layers) {
+        wgrad_cut(p, (p.ntiles + b.unit - 1) / b.unit);
         b.nwg += (int64_t)p.ngroups * p.nslices;
-        b.partial_floats += wgrad_partial_floats(p);
+        b.partial_floats += p.partial_floats;
     }
     b.nwg = (b.nwg + 1023) / 1024 * 1024;                       // map entries: the work items padded to whole rounds of the XCD-aware order
     b.table_bytes = (((int64_t)n * sizeof(WgradArgs)) + 255) / 256 * 256;
     b.map_bytes = ((b.nwg * (int64_t)sizeof(int4)) + 255) / 256 * 256;
-    return b;
+    return ESR_OK;
 }
+// _run_side takes the SIDE instantiation for one-plane sets whose plan has s2d == 0.  plan->s2d records the hint and the tile shapes, not the kernel
+// (wgrad_key decides that): an fp16 set that carries the hint runs the plain kernel under _run and under _run_side alike, never the side one.
+static bool side_kernel_runs(const esr_wgrad_batch_plan* plan) { return !plan->split && !plan->s2d; }
 
 }  // namespace
 
@@ -947,104 +992,68 @@ static BatchPlan batch_plan(const esr_wgrad_desc* descs, int n, int64_t unit_ove
 extern "C" void esr_debug_trace_wgrad(void* buf) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wtrace), &buf, sizeof(buf)); }
 #endif
 extern "C" int64_t esr_conv3x3_wgrad_workspace_floats(const esr_wgrad_desc* d) {
-    if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || d->cin_main <= 0) return ESR_E_ARG;
-    const int64_t n = wgrad_partial_floats(wgrad_plan(d, 512, desc_is_s2d(d)));
+    if (!wgrad_sizes_ok(d)) return ESR_E_ARG;
+    const int64_t n = wgrad_plan_single(d).partial_floats;
     return n > 0 ? n : 1;
 }
 
 extern "C" int esr_conv3x3_wgrad_tiling(const esr_wgrad_desc* d, int32_t* out) {
     if (!out) return ESR_E_ARG;
-    const int rc = wgrad_validate(d);
-    if (rc != ESR_OK) return rc;
-    const WgradPlan p = wgrad_plan(d, 512, desc_is_s2d(d));
-    const WgradArgs a = wgrad_args(d, p, nullptr);
-    const bool f16 = d->dy.fmt == ESR_FMT_F16, split = d->dy.lo != nullptr;
-    out[0] = p.tiles_x;
-    out[1] = p.tiles_y;
-    out[2] = p.shape;
-    out[3] = p.nslices;
-    // the kernel forms, as esr_conv3x3_wgrad picks them (wgrad_dispatch, the `fast_issue` copies of wgrad_body)
-    out[4] = (lat_as_latk(d) ? ESR_WGRAD_FORM_LAT27 : 0) | (main_as_latk(d) ? ESR_WGRAD_FORM_MAIN27 : 0) |
-             (a.tapmode == 1 && !f16 ? ESR_WGRAD_FORM_S2D : 0) | (!split && a.ups == 1 ? ESR_WGRAD_FORM_FAST_COPY : 0);
+    if (int rc = wgrad_validate(d)) return rc;
+    const WgradPlan p = wgrad_plan_single(d);
+    out[0] = p.tiles_x; out[1] = p.tiles_y; out[2] = p.shape; out[3] = p.nslices;
+    out[4] = (p.lat27 ? ESR_WGRAD_FORM_LAT27 : 0) | (p.main27 ? ESR_WGRAD_FORM_MAIN27 : 0) | (p.key.s2d ? ESR_WGRAD_FORM_S2D : 0) |
+             (p.fast_copy ? ESR_WGRAD_FORM_FAST_COPY : 0);
     return ESR_OK;
 }
 
 extern "C" int esr_conv3x3_wgrad(const esr_wgrad_desc* d, esr_stream_t stream) {
-    const int rc = wgrad_validate(d);
-    if (rc != ESR_OK) return rc;
-    if (!d->workspace || d->workspace_floats < esr_conv3x3_wgrad_workspace_floats(d)) return ESR_E_ARG;
-    const WgradPlan p = wgrad_plan(d, 512, desc_is_s2d(d));
-    const WgradArgs a = wgrad_args(d, p, d->workspace);
-    const bool split = d->dy.lo != nullptr;
-    const bool f16 = d->dy.fmt == ESR_FMT_F16;
-    const int nst = wgrad_stages(!split);                    // fp16 operands: single plane only (wgrad_validate)
-    void (*k)(const WgradArgs) = f16 ? (nst == 2 ? conv3x3_wgrad_kernel<1, 2, 1> : conv3x3_wgrad_kernel<1, 1, 1>)
-                               : split ? (nst == 2 ? conv3x3_wgrad_kernel<2, 2, 0> : conv3x3_wgrad_kernel<2, 1, 0>)
-                                       : (nst == 2 ? conv3x3_wgrad_kernel<1, 2, 0> : conv3x3_wgrad_kernel<1, 1, 0>);
-    if (a.tapmode == 1 && !f16)
-        k = split ? (nst == 2 ? conv3x3_wgrad_kernel<2, 2, 0, true> : conv3x3_wgrad_kernel<2, 1, 0, true>)
-                  : (nst == 2 ? conv3x3_wgrad_kernel<1, 2, 0, true> : conv3x3_wgrad_kernel<1, 1, 0, true>);
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // k varies per call: no caching
-    ESR_CLEAR_ERR();
-    hipLaunchKernelGGL(k, dim3(p.ngroups * p.nslices), dim3(256), wgrad_lds(split ? 2 : 1, nst), (hipStream_t)stream, a);
-    ESR_CHECK_LAUNCH();
-    if (p.nslices > 1) {
-        const long long nred = (long long)p.ngroups * 9 * 1024 + p.mt * 32;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-        ESR_CHECK_LAUNCH();
-    }
-    return ESR_OK;
+    if (int rc = wgrad_validate(d)) return rc;
+    const WgradPlan p = wgrad_plan_single(d);
+    if (!d->workspace || d->workspace_floats < (p.partial_floats > 0 ? p.partial_floats : 1)) return ESR_E_ARG;
+    WgradArgs a = wgrad_args(d, p, d->workspace);
+    void* args[] = {&a};
+    return wgrad_launch(wgrad_kernel(p.key, WG_SINGLE), p.grid, p.key.lds, (const void*)wgrad_reduce_kernel, p.fold_threads, 1, args, (hipStream_t)stream);
 }
 
-static int64_t batch_workspace_bytes(const esr_wgrad_desc* descs, int n, int64_t unit) {
-    if (!descs || n <= 0 || unit < 0) return ESR_E_ARG;
-    for (int i = 0; i < n; ++i)
-        if (descs[i].B <= 0 || descs[i].H <= 0 || descs[i].W <= 0 || descs[i].cout <= 0 || descs[i].cin_main <= 0) return ESR_E_ARG;
-    const BatchPlan b = batch_plan(descs, n, unit);
-    return b.table_bytes + b.map_bytes + (b.partial_floats + 1) * 4;
+extern "C" int64_t esr_conv3x3_wgrad_batch_part_workspace_bytes(const esr_wgrad_desc* descs, int n, int64_t unit) {
+    BatchPlan b;
+    if (int rc = batch_plan(descs, n, unit, b)) return rc;
+    return b.bytes();
 }
-extern "C" int64_t esr_conv3x3_wgrad_batch_workspace_bytes(const esr_wgrad_desc* descs, int n) { return batch_workspace_bytes(descs, n, 0); }
-extern "C" int64_t esr_conv3x3_wgrad_batch_part_workspace_bytes(const esr_wgrad_desc* descs, int n, int64_t unit) { return batch_workspace_bytes(descs, n, unit); }
+extern "C" int64_t esr_conv3x3_wgrad_batch_workspace_bytes(const esr_wgrad_desc* descs, int n) { return esr_conv3x3_wgrad_batch_part_workspace_bytes(descs, n, 0); }
 extern "C" int64_t esr_conv3x3_wgrad_batch_unit(const esr_wgrad_desc* descs, int n) {
-    if (!descs || n <= 0) return ESR_E_ARG;
-    for (int i = 0; i < n; ++i)
-        if (descs[i].B <= 0 || descs[i].H <= 0 || descs[i].W <= 0 || descs[i].cout <= 0 || descs[i].cin_main <= 0) return ESR_E_ARG;
-    const BatchPlan b = batch_plan(descs, n);
+    BatchPlan b;
+    if (int rc = batch_plan(descs, n, 0, b)) return rc;
     return b.unit | (b.shapes ? UNIT_SHAPES : 0);
 }
 
-static int batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan, int64_t unit, esr_stream_t stream);
-extern "C" int esr_conv3x3_wgrad_batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan,
-                                              esr_stream_t stream) {
-    return batch_upload(descs, n, workspace, workspace_bytes, plan, 0, stream);
-}
-extern "C" int esr_conv3x3_wgrad_batch_part_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan,
-                                                   int64_t unit, esr_stream_t stream) {
-    return unit > 0 ? batch_upload(descs, n, workspace, workspace_bytes, plan, unit, stream) : ESR_E_ARG;
-}
 static int batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan, int64_t unit, esr_stream_t stream) {
     if (!descs || n <= 0 || !workspace || !plan) return ESR_E_ARG;
     const bool split = descs[0].dy.lo != nullptr;
     for (int i = 0; i < n; ++i) {
-        const int rc = wgrad_validate(&descs[i]);
-        if (rc != ESR_OK) return rc;
+        if (int rc = wgrad_validate(&descs[i])) return rc;
         if ((descs[i].dy.lo != nullptr) != split || descs[i].dy.fmt != descs[0].dy.fmt) return ESR_E_ARG;      // one operand format per batch
     }
-    if (workspace_bytes < batch_workspace_bytes(descs, n, unit)) return ESR_E_ARG;
-    const BatchPlan b = batch_plan(descs, n, unit);
+    BatchPlan b;
+    if (int rc = batch_plan(descs, n, unit, b)) return rc;
+    if (workspace_bytes < b.bytes()) return ESR_E_ARG;
     std::vector<WgradArgs> table(n);
     std::vector<int4> work;                                      // the work list in its natural order (layer, slice, group)
     work.reserve((size_t)b.nwg);
-    const bool shapes = b.shapes;
     float* partials = (float*)((char*)workspace + b.table_bytes + b.map_bytes);
     int64_t pf = 0;
-    int max_red = 0;
+    // the library's bookkeeping between _upload and _run, filled here and nowhere else.  s2d: some layer carries the space-to-depth hint or takes
+    // the 16x16 / 32x8 tiles (wgrad_batch_launch makes the kernel of it); max_red: the most fold threads any layer with partial sums needs
+    *plan = esr_wgrad_batch_plan{b.nwg, b.table_bytes, n, 0, split ? 1 : 0, descs[0].dy.fmt == ESR_FMT_F16 ? 1 : 0, 0, 0};
     for (int i = 0; i < n; ++i) {
-        const WgradPlan p = batch_entry_plan(&descs[i], b.unit, shapes);
+        const WgradPlan& p = b.layers[i];
         table[i] = wgrad_args(&descs[i], p, partials + pf);
-        pf += wgrad_partial_floats(p);
-        entry_work(i, p, work);
-        if (p.nslices > 1 && p.ngroups * 9 * 1024 + p.mt * 32 > max_red) max_red = p.ngroups * 9 * 1024 + p.mt * 32;
+        pf += p.partial_floats;
+        for (int sl = 0; sl < p.nslices; ++sl)                   // slice-major, so that co-running workgroups of one layer read different images
+            for (int g = 0; g < p.ngroups; ++g) work.push_back(make_int4(i, g, sl, 0));
+        if (p.fold_threads > plan->max_red) plan->max_red = (int)p.fold_threads;
+        plan->s2d |= (p.tapmode == 1 || p.shape != 0) ? 1 : 0;
     }
     // Order of the work list over the XCDs.  The hardware deals workgroup b to XCD b % 8, so the groups of one layer (same dY tiles for a cot, same
     // X tiles for a cit: neighbours in the list) run on eight different L2s: 25 GB of L2 misses per configs[2] launch (bf16) for 1.9 GB of distinct
@@ -1067,56 +1076,40 @@ static int batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int
     if (hipMemcpyAsync(workspace, table.data(), (size_t)n * sizeof(WgradArgs), hipMemcpyHostToDevice, s) != hipSuccess) return ESR_E_LAUNCH;
     if (hipMemcpyAsync((char*)workspace + b.table_bytes, map.data(), (size_t)b.nwg * sizeof(int4), hipMemcpyHostToDevice, s) != hipSuccess)
         return ESR_E_LAUNCH;
-    plan->nwg = npair;
-    plan->table_bytes = b.table_bytes;
-    plan->n = n;
-    plan->max_red = max_red;
-    plan->split = split ? 1 : 0;
-    plan->f16 = descs[0].dy.fmt == ESR_FMT_F16 ? 1 : 0;
-    plan->s2d = 0;                                               // the space-to-depth kernel: tap-skipping layers, or the 16x16 / 32x8 tiles
-    for (const WgradArgs& t : table) plan->s2d |= (t.tapmode == 1 || t.shape != 0) ? 1 : 0;
-    plan->reserved = 0;
     return ESR_OK;
 }
+extern "C" int esr_conv3x3_wgrad_batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan,
+                                              esr_stream_t stream) {
+    return batch_upload(descs, n, workspace, workspace_bytes, plan, 0, stream);
+}
+extern "C" int esr_conv3x3_wgrad_batch_part_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan,
+                                                   int64_t unit, esr_stream_t stream) {
+    return unit > 0 ? batch_upload(descs, n, workspace, workspace_bytes, plan, unit, stream) : ESR_E_ARG;
+}
 
-static int wgrad_batch_launch(const void* workspace, const esr_wgrad_batch_plan* plan, esr_stream_t stream, bool side);
+extern "C" int esr_conv3x3_wgrad_side_occupancy(int f16) {
+    const WgradKey key = wgrad_key(false, f16 != 0, false);
+    const void* k = wgrad_kernel(key, WG_SIDE);
+    if (wgrad_allow_lds(k) != hipSuccess) { (void)hipGetLastError(); return ESR_E_LAUNCH; }
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 256, key.lds) != hipSuccess) { (void)hipGetLastError(); return ESR_E_LAUNCH; }
+    return nb;
+}
+static int wgrad_batch_launch(const void* workspace, const esr_wgrad_batch_plan* plan, esr_stream_t stream, bool side) {
+    if (!workspace || !plan || plan->n <= 0 || plan->nwg <= 0) return ESR_E_ARG;
+    // (plan->s2d: some layers are space-to-depth embedded stride-2 convs, or take its tiles: the variant that skips their zero blocks)
+    const WgradKey key = wgrad_key(plan->split != 0, plan->f16 != 0, plan->s2d != 0);
+    const void* table = workspace;
+    const void* map = (const char*)workspace + plan->table_bytes;
+    void* args[] = {&table, &map};
+    return wgrad_launch(wgrad_kernel(key, side && side_kernel_runs(plan) ? WG_SIDE : WG_BATCH), (unsigned)plan->nwg, key.lds,
+                        (const void*)wgrad_reduce_batch_kernel, plan->max_red, plan->n, args, (hipStream_t)stream);
+}
 extern "C" int esr_conv3x3_wgrad_batch_run(const void* workspace, const esr_wgrad_batch_plan* plan, esr_stream_t stream) {
     return wgrad_batch_launch(workspace, plan, stream, false);
 }
 extern "C" int esr_conv3x3_wgrad_batch_run_side(const void* workspace, const esr_wgrad_batch_plan* plan, esr_stream_t stream) {
     return wgrad_batch_launch(workspace, plan, stream, true);
-}
-extern "C" int esr_conv3x3_wgrad_side_occupancy(int f16) {
-    void (*k)(const WgradArgs*, const int4*) = f16 ? conv3x3_wgrad_batch_kernel<1, 2, 1, false, true> : conv3x3_wgrad_batch_kernel<1, 2, 0, false, true>;
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); return ESR_E_LAUNCH; }
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 256, wgrad_lds(1, 2)) != hipSuccess) { (void)hipGetLastError(); return ESR_E_LAUNCH; }
-    return nb;
-}
-static int wgrad_batch_launch(const void* workspace, const esr_wgrad_batch_plan* plan, esr_stream_t stream, bool side) {
-    if (!workspace || !plan || plan->n <= 0 || plan->nwg <= 0) return ESR_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const bool f16 = plan->f16 != 0, split = plan->split != 0;
-    const int nst = wgrad_stages(!split);
-    void (*k)(const WgradArgs*, const int4*) = f16 ? (nst == 2 ? conv3x3_wgrad_batch_kernel<1, 2, 1> : conv3x3_wgrad_batch_kernel<1, 1, 1>)
-                                             : split ? (nst == 2 ? conv3x3_wgrad_batch_kernel<2, 2, 0> : conv3x3_wgrad_batch_kernel<2, 1, 0>)
-                                                     : (nst == 2 ? conv3x3_wgrad_batch_kernel<1, 2, 0> : conv3x3_wgrad_batch_kernel<1, 1, 0>);
-    if (plan->s2d && !f16)        // some layers are space-to-depth embedded stride-2 convs: the variant that skips their zero blocks
-        k = split ? (nst == 2 ? conv3x3_wgrad_batch_kernel<2, 2, 0, true> : conv3x3_wgrad_batch_kernel<2, 1, 0, true>)
-                  : (nst == 2 ? conv3x3_wgrad_batch_kernel<1, 2, 0, true> : conv3x3_wgrad_batch_kernel<1, 1, 0, true>);
-    if (side && !split && !plan->s2d)          // one-plane operands only: the hi+lo and space-to-depth forms run as they are
-        k = f16 ? conv3x3_wgrad_batch_kernel<1, 2, 1, false, true> : conv3x3_wgrad_batch_kernel<1, 2, 0, false, true>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // k varies per call: no caching
-    ESR_CLEAR_ERR();
-    hipLaunchKernelGGL(k, dim3((unsigned)plan->nwg), dim3(256), wgrad_lds(split ? 2 : 1, nst), s, (const WgradArgs*)workspace,
-                       (const int4*)((const char*)workspace + plan->table_bytes));
-    ESR_CHECK_LAUNCH();
-    if (plan->max_red > 0) {
-        hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)((plan->max_red + 255) / 256), (unsigned)plan->n), dim3(256), 0, s,
-                           (const WgradArgs*)workspace);
-        ESR_CHECK_LAUNCH();
-    }
-    return ESR_OK;
 }
 
 namespace {

@@ -377,7 +377,10 @@ typedef struct {
      * (any other pattern, fp16 operands, cin_main % 128 != 0) adds the true gradient there, as without the hint. */
     int32_t tap_masks[4];
 } esr_wgrad_desc;
-int64_t esr_conv3x3_wgrad_workspace_floats(const esr_wgrad_desc* d);   /* depends on B, H, W, cout, cin_main, lat only; <0: bad argument */
+/* Depends on everything that shapes the launch: B, H, W, cout, cin_main; xlat (given or not) and lat; upsample; the operand format and planes;
+ * tap_masks (the space-to-depth tiles change the tile count, the 27-column forms the group count) — ask with the descriptor the launch will get.
+ * <0: bad argument (a size <= 0; nothing else is checked here). */
+int64_t esr_conv3x3_wgrad_workspace_floats(const esr_wgrad_desc* d);
 int esr_conv3x3_wgrad(const esr_wgrad_desc* d, esr_stream_t stream);
 /* Host-only query (no device access, nothing launched), for tests and documentation: how esr_conv3x3_wgrad runs the launch `d` describes.
  * out[0] / [1] = pixel tiles per image along x / y, [2] = tile shape (0: 8 rows x 32 columns, 1: 16 x 16, 2: 32 x 8 — the latter two only
@@ -400,7 +403,7 @@ int esr_conv3x3_wgrad_batch(const esr_wgrad_desc* descs, int n, void* workspace,
  * memory: NOT capturable in a HIP graph) and fills `plan`; _run enqueues the launch from the table already on the device (capturable; no
  * host traffic).  esr_conv3x3_wgrad_batch == _upload followed by _run. */
 /* (plan fields are the library's own bookkeeping between _upload and _run — opaque to callers: nwg = workgroups of the per-pair launch, `reserved` =
- * block-form items | their LDS KiB << 23 when the experimental block decomposition is enabled, 0 otherwise) */
+ * always 0) */
 typedef struct { int64_t nwg, table_bytes; int32_t n, max_red, split, f16, s2d, reserved; } esr_wgrad_batch_plan;
 int esr_conv3x3_wgrad_batch_upload(const esr_wgrad_desc* descs, int n, void* workspace, int64_t workspace_bytes, esr_wgrad_batch_plan* plan,
                                    esr_stream_t stream);

@@ -113,7 +113,7 @@ def test_backward_and_double_backward_kernels_match_float64_autograd():
 @pytest.mark.parametrize('precision,tol', [('split', 2e-5), ('bf16', 1e-4)])
 def test_first_layer_weight_gradient_runs_the_gathered_tile_form(precision, tol):
     """The critic's first conv has a 3-channel MAIN input: its weight gradient runs the 27 (tap, channel) columns as one MFMA tile (csrc/esr_bwd.hip,
-    main_as_latk) and the same workgroups own the bias gradient.  Against float64 autograd, as a single launch (partial sums + fold) and inside
+    WgradPlan.main27) and the same workgroups own the bias gradient.  Against float64 autograd, as a single launch (partial sums + fold) and inside
     the batched launch of all layers' gradients (which takes the space-to-depth kernel flavour)."""
     import torch.nn.functional as F
     from esr_hip import critic as K

@@ -68,6 +68,7 @@ __global__ void zero_kernel(uint4* p, long long n) {
 extern "C" int esr_pack_nchw(const float* src, int64_t src_batch_stride, int B, int C, int h, int w, int c0, int nc, int pad, int down, const esr_act_view* dst,
                              esr_stream_t stream) {
     if (!src || !dst || !dst->hi || B <= 0 || nc <= 0 || c0 < 0 || c0 + nc > C || pad < 0 || down < 1) return ESR_E_ARG;
+    if (h < 1 || w < 1) return ESR_E_ARG;   // nothing to replicate: the clamp would read src[-1]
     if ((h + 2 * pad) % down || (w + 2 * pad) % down) return ESR_E_ARG;
     const int Hd = (h + 2 * pad) / down, Wd = (w + 2 * pad) / down;
     if (dst->H != Hd || dst->W != Wd || dst->ncg * 8 < nc) return ESR_E_ARG;
@@ -82,6 +83,7 @@ extern "C" int esr_pack_nchw(const float* src, int64_t src_batch_stride, int B, 
 
 extern "C" int esr_unpack_nchw(const esr_act_view* src, int B, int nc, float* dst, esr_stream_t stream) {
     if (!src || !src->hi || !dst || B <= 0 || nc <= 0 || src->ncg * 8 < nc) return ESR_E_ARG;
+    if (src->H < 1 || src->W < 1) return ESR_E_ARG;   // an empty grid is a launch error, not a no-op
     const long long total = (long long)B * ((nc + 7) / 8) * src->H * src->W;
     ESR_CLEAR_ERR();
     hipLaunchKernelGGL(unpack_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)src->hi,

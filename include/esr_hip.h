@@ -231,17 +231,26 @@ int esr_pack_batch_run(const void* workspace, int n, int64_t nblocks, esr_stream
 /* ---- layout conversion at the module boundary ----
  * fp32 NCHW -> act view.  Writes channels [c0, c0+nc) of `src` ([B][C][h][w]; image b starts at
  * src + b*src_batch_stride floats, 0 = C*h*w — lets the HR-resolution latent be read through the raw
- * `view` the reference applies to it, SRRaGAN_model.py:233 / architecture.py:283) into group 0.. of `dst`
- * (zero-filling unused lanes of the last group and the 1-px border), with
+ * `view` the reference applies to it, SRRaGAN_model.py:233 / architecture.py:283) into group 0.. of `dst`, with
  *   pad  : replicate padding by `pad` pixels on every side (CEM_PyTorch.forward eval-mode LR_padder /
  *          HR_padder, codes/CEM/CEMnet.py:286-295), dst interior = (h+2*pad)/down x (w+2*pad)/down
  *   down : 1, or the bilinear /down of architecture.py:284 (F.interpolate(scale_factor=1/sf,'bilinear',
- *          align_corners=False)) applied AFTER the padding (down divides h+2*pad). */
+ *          align_corners=False)) applied AFTER the padding (down divides h+2*pad): source coordinate
+ *          max((y + 0.5)*down - 0.5, 0), taps (y0, min(y0 + 1, h + 2*pad - 1)), the same along x.
+ * What is written: every vector of the (H+2) x (W+2) frame of EVERY group of dst->ncg, both planes of a two-plane view, for B images and
+ * nothing else.  Stored element = hi: the value rounded to nearest even in dst->fmt, lo: the fp32 residual value - hi rounded the same way.
+ * The 1-px border, the lanes >= nc of the last group and whole groups past ceil(nc / 8) are zero.  Channels of src outside [c0, c0+nc)
+ * and the floats between two images (src_batch_stride > C*h*w) are not read.
+ * ESR_E_ARG, before anything is launched: NULL src / dst / dst->hi; B <= 0; nc <= 0; c0 < 0; c0 + nc > C; pad < 0; down < 1; h < 1 or
+ * w < 1; down not dividing h + 2*pad or w + 2*pad; dst->H, dst->W other than the interior size above; dst->ncg * 8 < nc. */
 int esr_pack_nchw(const float* src, int64_t src_batch_stride, int B, int C, int h, int w, int c0, int nc, int pad, int down,
                   const esr_act_view* dst, esr_stream_t stream);
-/* act view -> fp32 NCHW [B][nc][H][W] (hi + lo); used by tests and by callers that want features. */
+/* act view -> fp32 NCHW [B][nc][H][W] (hi + lo as one fp32 addition, an absent lo counting as +0); used by tests and by callers that want
+ * features.  Reads the interior of groups 0 .. ceil(nc / 8) - 1 only; lanes >= nc of the last group go nowhere.
+ * ESR_E_ARG, before anything is launched: NULL src / src->hi / dst; B <= 0; nc <= 0; src->ncg * 8 < nc; src->H < 1 or src->W < 1. */
 int esr_unpack_nchw(const esr_act_view* src, int B, int nc, float* dst, esr_stream_t stream);
-/* zero `n16` 16-byte vectors (border initialisation of freshly allocated activation buffers) */
+/* zero `n16` 16-byte vectors (border initialisation of freshly allocated activation buffers); n16 == 0 is ESR_OK and launches nothing,
+ * p == NULL or n16 < 0 ESR_E_ARG */
 int esr_zero(void* p, int64_t n16, esr_stream_t stream);
 
 /* ---- VGG feature extractor glue (the perceptual loss's network: codes/models/modules/architecture.py:658-705, VGGFeatureExtractor on
@@ -249,8 +258,11 @@ int esr_zero(void* p, int64_t n16, esr_stream_t stream);
  * launches with act_slope = 0, their data gradients esr_conv3x3 on transposed packs with mask_slope = 0).
  * esr_pack_nchw_norm: fp32 NCHW [B][C][h][w] -> act view (h x w, zero border) of (x - mean[c]) / std[c] — VGGFeatureExtractor.forward's
  *   input normalisation (architecture.py:705-709) applied BEFORE conv1_1's zero padding, so the border stays 0.  mean / std: device fp32 [C],
- *   both NULL = no normalisation (use_input_norm = False).
+ *   both NULL = no normalisation (use_input_norm = False).  As esr_pack_nchw, every group of dst->ncg is written whole: the border, the
+ *   lanes >= C and the groups past ceil(C / 8) are zero (not (0 - mean) / std).  ESR_E_ARG: a NULL src / dst / dst->hi; B, C, h or w <= 0;
+ *   one of mean / std without the other; dst->H != h or dst->W != w; dst->ncg * 8 < C.
  * esr_unpack_grad_nchw_norm: its adjoint — act-layout gradient (hi + lo) -> fp32 NCHW [B][C][G->H][G->W], divided by std[c] (NULL: copied).
+ *   Groups past ceil(C / 8) are not read; lanes >= C of the last group go nowhere.  ESR_E_ARG: a NULL G / G->hi / dst; B or C <= 0; G->ncg * 8 < C; G->H or G->W <= 0.
  * esr_maxpool2x2: nn.MaxPool2d(kernel_size=2, stride=2) — y->H = floor(x->H / 2), y->W = floor(x->W / 2) (F.max_pool2d floors); the window
  *   value is hi + lo; the output is the element at torch's argmax (the first maximum in row-major window order; a NaN propagates), copied
  *   bit for bit, and y's one-pixel zero border is written (y is the next conv's input).  Same format and planes in x and y.

@@ -51,6 +51,8 @@ constexpr int EPI_RES1 = 1, EPI_RES2 = 2, EPI_MASK = 4, EPI_NCHW = 8, EPI_OUT2 =
 constexpr int EPI_RESIN = 32;
 // pixel-shuffle store (esr_conv3x3_desc.pixel_shuffle): its own instantiations, so that the plain store carries none of its index arithmetic
 constexpr int EPI_PS = 64;
+// what a K chunk does for EPI_RESIN (conv3x3_tile_kernel's `step`); values >= 0 name the chunk of an unrolled residual range
+constexpr int RES_PLAIN = -2, RES_LOOP = -1;
 
 struct ConvArgs {
     // ---- what the prologue decodes before it can issue the first copy (one kernarg batch): the tile space, the tile geometry and the
@@ -294,8 +296,33 @@ __device__ __forceinline__ void res_unpack(const ResRaw& q, bool has_lo, f32x2 (
     }
 }
 
-// EPI_RESIN: the two input groups of chunk cp are in the LDS stage right now; if they belong to the residual slice, add this lane's 4
-// channels of the centre-tap pixel (exactly hi + lo, in fp32) to the matching accumulator rows.
+// EPI_RESIN: the two input groups of a residual chunk are in the LDS stage right now; the ones that belong to the residual slice add this lane's
+// 4 channels of the centre-tap pixel (exactly hi + lo, in fp32) to the accumulator rows of the output group they feed.
+// resin_load: the pixel values of input group `sgrp` of the staged chunk, per column tile.
+template <int NPL, int R, int FMT>
+__device__ __forceinline__ void resin_load(float (&x)[R][4], const unsigned char* stage, int sgrp, bool xlo, int P, int plane_bytes, int wave, int lane) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const unsigned char* const pr = stage + sgrp * NPL * plane_bytes + ((wave + r * NW) * 32 + (lane & 31) + P + 1) * 16 + (lane >> 5) * 8;
+        const uint2 h = *(const uint2*)pr;
+        x[r][0] = e2f<FMT>(h.x & 0xFFFF); x[r][1] = e2f<FMT>(h.x >> 16); x[r][2] = e2f<FMT>(h.y & 0xFFFF); x[r][3] = e2f<FMT>(h.y >> 16);
+        if (NPL == 2 && xlo) {
+            const uint2 l = *(const uint2*)(pr + plane_bytes);
+            x[r][0] += e2f<FMT>(l.x & 0xFFFF); x[r][1] += e2f<FMT>(l.x >> 16); x[r][2] += e2f<FMT>(l.y & 0xFFFF); x[r][3] += e2f<FMT>(l.y >> 16);
+        }
+    }
+}
+// resin_fma: acc rows of output group OG += scale * x.  OG is a template argument because accumulator rows are register indices.
+template <int MT, int R, int OG>
+__device__ __forceinline__ void resin_fma(f32x16 (&acc)[MT][R], float scale, const float (&x)[R][4]) {
+    if constexpr (OG >= 0 && OG < MT * 4) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[OG / 4][r][(OG % 4) * 4 + i] = fmaf(scale, x[r][i], acc[OG / 4][r][(OG % 4) * 4 + i]);
+    }
+}
+// Chunk cp of a loop over the residual range (the lone-workgroup forms, NST >= 2): the output group is known at run time only.
 template <int NPL, int MT, int R, int FMT>
 __device__ __forceinline__ void resin_accumulate(f32x16 (&acc)[MT][R], const ConvArgs& a, const unsigned char* stage, int cp, bool xlo, int P,
                                                  int plane_bytes, int wave, int lane) {
@@ -304,36 +331,39 @@ __device__ __forceinline__ void resin_accumulate(f32x16 (&acc)[MT][R], const Con
         const int og = 2 * cp + sgrp - a.resin_g0;              // output group fed by this input group (uniform)
         if (og < 0 || og * 8 >= a.cout) continue;
         float x[R][4];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const unsigned char* const pr = stage + sgrp * NPL * plane_bytes + ((wave + r * NW) * 32 + (lane & 31) + P + 1) * 16 + (lane >> 5) * 8;
-            const uint2 h = *(const uint2*)pr;
-            x[r][0] = e2f<FMT>(h.x & 0xFFFF); x[r][1] = e2f<FMT>(h.x >> 16); x[r][2] = e2f<FMT>(h.y & 0xFFFF); x[r][3] = e2f<FMT>(h.y >> 16);
-            if (NPL == 2 && xlo) {
-                const uint2 l = *(const uint2*)(pr + plane_bytes);
-                x[r][0] += e2f<FMT>(l.x & 0xFFFF); x[r][1] += e2f<FMT>(l.x >> 16); x[r][2] += e2f<FMT>(l.y & 0xFFFF); x[r][3] += e2f<FMT>(l.y >> 16);
-            }
-        }
-        // (uniform switch with the row group as a compile-time constant per case: accumulator rows are register indices — an if-chain over an
-        // unrolled index gets re-rolled into a run-time index, which sends the whole accumulator array to scratch)
-        auto add = [&](auto MG) {
-            constexpr int mg = decltype(MG)::value;
-            if constexpr (mg < MT * 4) {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[mg / 4][r][(mg % 4) * 4 + i] = fmaf(a.resin_scale, x[r][i], acc[mg / 4][r][(mg % 4) * 4 + i]);
-            }
-        };
+        resin_load<NPL, R, FMT>(x, stage, sgrp, xlo, P, plane_bytes, wave, lane);
+        // (uniform switch with the row group as a compile-time constant per case: an if-chain over an unrolled index gets re-rolled into a
+        // run-time index, which sends the whole accumulator array to scratch.  The price: the accumulators are values merged across the
+        // arms, and the allocator copies them — some 100 moves on the way past the switch, as many again in each arm taken)
         switch (og) {
-            case 0: add(std::integral_constant<int, 0>{}); break;
-            case 1: add(std::integral_constant<int, 1>{}); break;
-            case 2: add(std::integral_constant<int, 2>{}); break;
-            case 3: add(std::integral_constant<int, 3>{}); break;
-            case 4: add(std::integral_constant<int, 4>{}); break;
-            case 5: add(std::integral_constant<int, 5>{}); break;
-            case 6: add(std::integral_constant<int, 6>{}); break;
-            default: add(std::integral_constant<int, 7>{}); break;
+            case 0: resin_fma<MT, R, 0>(acc, a.resin_scale, x); break;
+            case 1: resin_fma<MT, R, 1>(acc, a.resin_scale, x); break;
+            case 2: resin_fma<MT, R, 2>(acc, a.resin_scale, x); break;
+            case 3: resin_fma<MT, R, 3>(acc, a.resin_scale, x); break;
+            case 4: resin_fma<MT, R, 4>(acc, a.resin_scale, x); break;
+            case 5: resin_fma<MT, R, 5>(acc, a.resin_scale, x); break;
+            case 6: resin_fma<MT, R, 6>(acc, a.resin_scale, x); break;
+            default: resin_fma<MT, R, 7>(acc, a.resin_scale, x); break;
+        }
+    }
+}
+// The k-th chunk of an UNROLLED residual range (the large-launch forms, NST == 1): its input groups feed output groups OG0 and OG0 + 1, both
+// compile-time (OG0 = -1: the first group lies in front of the slice) — straight-line code on fixed registers, no accumulator is copied.
+template <int NPL, int MT, int R, int FMT, int OG0>
+__device__ __forceinline__ void resin_accumulate_at(f32x16 (&acc)[MT][R], const ConvArgs& a, const unsigned char* stage, bool xlo, int P, int plane_bytes,
+                                                    int wave, int lane) {
+    if constexpr (OG0 >= 0 && OG0 < MT * 4) {
+        if (OG0 * 8 < a.cout) {                                 // uniform
+            float x[R][4];
+            resin_load<NPL, R, FMT>(x, stage, 0, xlo, P, plane_bytes, wave, lane);
+            resin_fma<MT, R, OG0>(acc, a.resin_scale, x);
+        }
+    }
+    if constexpr (OG0 + 1 >= 0 && OG0 + 1 < MT * 4) {
+        if ((OG0 + 1) * 8 < a.cout) {
+            float x[R][4];
+            resin_load<NPL, R, FMT>(x, stage, 1, xlo, P, plane_bytes, wave, lane);
+            resin_fma<MT, R, OG0 + 1>(acc, a.resin_scale, x);
         }
     }
 }
@@ -797,7 +827,12 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
     // One chunk: DMA (or prefetch of the next chunk), barrier, MFMAs, barrier.  XLO (compile time): this chunk's activations have a lo
     // plane.  The chunks with a lo plane come first, so the K loop is two loops over the same step with XLO = true / false: a run-time
     // branch between the two MFMA bodies inside ONE loop made the register allocator spill (vgpr_spill 200-500 in the 64-channel kernels).
-    auto step = [&](auto XLO_T, const int cp) {
+    // RES (compile time, EPI_RESIN kernels): RES_PLAIN = this chunk's input groups do not touch the residual slice — it executes nothing for the
+    // residual; RES_LOOP = a chunk of the residual range, output groups found at run time (resin_accumulate); k >= 0 = the k-th chunk of the
+    // residual range, output groups known here (resin_accumulate_at).  (resin_accumulate's switch over accumulator rows, placed in EVERY
+    // chunk of one loop, made all 96 accumulators values merged across its arms: 116 register moves behind the last MFMA of every chunk,
+    // in front of the closing barrier, and a residual chunk took 2.2 times a plain one — profiles/r10_resin_ranges_ab.log.)
+    auto step = [&](auto XLO_T, auto RES_T, const int cp) __attribute__((always_inline)) {
         constexpr bool xlo = decltype(XLO_T)::value;
         const int st = NST == 4 ? (cp & 3) : (NST >= 2 ? (cp & 1) : 0);
         const unsigned char* const sb = sb0 + st * stage_bytes;
@@ -846,14 +881,63 @@ __global__ __launch_bounds__(NTHREADS, NST >= 2 ? 1 : (MT == 1 ? WGS_MT1 : WGS_M
         } else {
             chunk_mfma<NPL, MT, R, NPW, FMT, xlo, NTERM_CAP>(acc, sa, sb, P, plane_bytes);
         }
-        if constexpr ((EPI & EPI_RESIN) != 0) resin_accumulate<NPL, MT, R, FMT>(acc, a, smem + st * stage_bytes, cp, xlo, P, plane_bytes, wave, lane);
+        if constexpr (decltype(RES_T)::value == RES_LOOP) {
+            resin_accumulate<NPL, MT, R, FMT>(acc, a, smem + st * stage_bytes, cp, xlo, P, plane_bytes, wave, lane);
+        } else if constexpr (decltype(RES_T)::value >= 0) {
+            // chunk k's groups feed output groups 2k, 2k + 1 — one less when the slice starts at an odd group.  (The empty asm statements
+            // differ on purpose: identical arms would have their common tail — the same fma on rows one group apart — merged into one with a
+            // run-time row index, and an accumulator row indexed at run time lives in scratch.)
+            constexpr int k = decltype(RES_T)::value;
+            if (a.resin_g0 & 1) {
+                asm volatile("; residual chunk, odd first group");
+                resin_accumulate_at<NPL, MT, R, FMT, 2 * k - 1>(acc, a, smem + st * stage_bytes, xlo, P, plane_bytes, wave, lane);
+                asm volatile("; residual chunk, odd first group: end");
+            } else {
+                asm volatile("; residual chunk, even first group");
+                resin_accumulate_at<NPL, MT, R, FMT, 2 * k>(acc, a, smem + st * stage_bytes, xlo, P, plane_bytes, wave, lane);
+                asm volatile("; residual chunk, even first group: end");
+            }
+        }
         ESR_TR();
         __syncthreads();
     };
+    // The chunks [c0, c1) of one XLO form.  EPI_RESIN: the residual slice is the input groups [resin_g0, resin_g0 + ceil(cout / 8)), i.e. the
+    // chunks [rc0, rc1) (uniform; clamped into the span, so that a range cut by lo_chunks or longer than the input ends with the span) — plain
+    // chunks in front of them, residual chunks, plain chunks behind them: bodies chosen at compile time, like the XLO pair.
+    //   NST == 1 (large launches, two workgroups per CU on 256 registers each): the residual chunks are unrolled, MT * 4 output groups = MT * 2
+    //   chunks and one more when the slice starts at an odd group, each with its output groups as constants.
+    //   NST >= 2 (a lone workgroup per CU): one loop over the residual chunks.  Unrolled, the 64-channel forms come to 17-19 thousand instructions
+    //   with 2380 SGPR spill moves and, with RES2, scratch.
+    constexpr std::integral_constant<int, RES_PLAIN> PLAIN{};
+    auto span = [&](auto XLO_T, const int c0, const int c1) {
+        if constexpr ((EPI & EPI_RESIN) != 0) {
+            const int rc0 = a.resin_g0 >> 1, rc1 = (a.resin_g0 + ((a.cout + 7) >> 3) + 1) >> 1;
+            const int r0 = rc0 < c0 ? c0 : (rc0 > c1 ? c1 : rc0), r1 = rc1 < r0 ? r0 : (rc1 > c1 ? c1 : rc1);
+            for (int cp = c0; cp < r0; ++cp) step(XLO_T, PLAIN, cp);
+            if constexpr (NST == 1) {
+                auto res_chunk = [&](auto KC) __attribute__((always_inline)) {
+                    if constexpr (decltype(KC)::value < MT * 2 + 1) {
+                        const int cp = rc0 + decltype(KC)::value;
+                        if (cp >= r0 && cp < r1) step(XLO_T, KC, cp);
+                    }
+                };
+                res_chunk(std::integral_constant<int, 0>{}); res_chunk(std::integral_constant<int, 1>{}); res_chunk(std::integral_constant<int, 2>{});
+                res_chunk(std::integral_constant<int, 3>{}); res_chunk(std::integral_constant<int, 4>{});
+            } else {
+                for (int cp = r0; cp < r1; ++cp) step(XLO_T, std::integral_constant<int, RES_LOOP>{}, cp);
+            }
+            for (int cp = r1; cp < c1; ++cp) step(XLO_T, PLAIN, cp);
+        }
+    };
     const int lo_end = PARTLO ? (a.lo_chunks < a.ncp ? a.lo_chunks : a.ncp) : a.ncp;
-    for (int cp = 0; cp < lo_end; ++cp) step(std::true_type{}, cp);
-    if constexpr (PARTLO)
-        for (int cp = lo_end; cp < a.ncp; ++cp) step(std::false_type{}, cp);
+    if constexpr ((EPI & EPI_RESIN) != 0) {
+        span(std::true_type{}, 0, lo_end);
+        if constexpr (PARTLO) span(std::false_type{}, lo_end, a.ncp);
+    } else {
+        for (int cp = 0; cp < lo_end; ++cp) step(std::true_type{}, PLAIN, cp);
+        if constexpr (PARTLO)
+            for (int cp = lo_end; cp < a.ncp; ++cp) step(std::false_type{}, PLAIN, cp);
+    }
     ESR_TR();
     if constexpr (!EARLY_COORDS) ec = epi_coords<R, EKIND>(a, x0, y0, wave, lane);
     conv_epilogue<NPL, MT, R, EPI, FMT, PARTLO, TMODE == 3>(a, acc, b, ec, lane);

@@ -276,7 +276,14 @@ _SIGS = {
                                 C.c_void_p]),
     'esr_sample_std_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     'esr_sample_std': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'esr_data_lrhr_plan': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    'esr_ycbcr_image': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'esr_psnr_ssim_ycbcr_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'esr_psnr_ssim_ycbcr': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    'esr_sample_std_ycbcr_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'esr_sample_std_ycbcr': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    'esr_data_lrhr_plan':(C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     'esr_data_lrhr_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(DataChannelMap), C.c_void_p, C.c_void_p, C.c_void_p]),
 }

@@ -269,6 +269,20 @@ class DecompCNNModel(BaseModel):
             out_dict['Uncomp'] = pick(self.var_Uncomp)
         return out_dict
 
+    def current_metrics(self, gt=None, crop_border=0):
+        """{'psnr', 'ssim'}: float64 [B] on the model's device, of the last test()'s output against gt as test_JPEG.py scores them — both as the
+        uint8 pictures util.tensor2img makes (esr_hip.jpeg_metrics.psnr_ssim: on the GPU nothing is copied or converted to memory).  gt: the
+        ground truth in the output's form ([B or 1, C, H, W] in 0...255); the Y model defaults to the 'Uncomp' of feed_data(need_GT=True).  The
+        colour model has to be given it: the Y plane it was fed is its own Y model's output, not the ground truth's."""
+        from esr_hip import jpeg_metrics
+        if gt is None:
+            if self.chroma_mode:
+                raise ValueError("current_metrics: the colour model needs gt (its input's Y plane is generated, keep the item's own 'Uncomp')")
+            gt = self.var_Uncomp
+        out = self.Output_Batch(within_0_1=False)
+        psnr, ssim = jpeg_metrics.psnr_ssim(out, gt.to(out.device), 'YCbCr' if out.size(1) == 3 else 'Y', crop_border=crop_border)
+        return {'psnr': psnr, 'ssim': ssim}
+
     def print_network(self):
         s, n = self.get_network_description(self.netG)
         print('Number of parameters in G: {:,d}'.format(n))

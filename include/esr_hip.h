@@ -803,6 +803,43 @@ int esr_psnr_ssim(const float* a, const float* b, int B, int C, int H, int W, fl
 int64_t esr_sample_std_partials(int C, int H, int W);
 int esr_sample_std(const float* x, int S, int B, int C, int H, int W, float* map, double* partial, double* sums, esr_stream_t stream);
 
+/* ---- scores and pictures of the JPEG decoder's output (codes/test_JPEG.py:165-327; utils/util.py:209-226 tensor2img's chroma branches) ----
+ * The decoder's images are fp32 [B][C][H][W] in 0...255: C = 1 is a Y plane (chroma mode 'Y'), C = 3 is Y, Cb, Cr ('YCbCr').  One pixel
+ * t = (Y, Cb, Cr) becomes the three 0...255 pixels p_j, j = 0 R, 1 G, 2 B, by this chain (util.tensor2img through data.util.ycbcr2rgb, :198-215),
+ * in these formats and this order:
+ *     a_c = t_c / 255f                                     fp32, IEEE division                          (img_np / 255)
+ *     x_c = a_c * 255f                                     fp32                                         (ycbcr2rgb: img *= 255.)
+ *     r_j = ((x_0 M[0][j] + x_1 M[1][j]) + x_2 M[2][j]) * 255.0 + off_j
+ *                                                          fp64, every product and sum rounded on its own (no fused multiply-add), in this order
+ *     q_j = (float)(r_j / 255.0)                           one rounding to fp32
+ *     s_j = 255f * q_j                                     fp32
+ *     p_j = rint(255f * ((clamp(s_j, lo, hi) - lo) / (hi - lo)))    fp32: esr_psnr_ssim's pixel with ESR_PIXELS_ROUND
+ *   M = {{0.00456621, 0.00456621, 0.00456621}, {0, -0.00153632, 0.00791071}, {0.00625893, -0.00318811, 0}},
+ *   off = {-222.921, 135.576, -276.836} (data.util.ycbcr2rgb's literals).  With C = 1 the chain starts at a_1 = a_2 = (float)(128.0 / 255.0), the
+ *   reference's 128 / 255 * np.ones_like(img); its three outputs differ by up to 1e-3 before rounding, so all three are computed.
+ *   (NumPy's own 3-term matmul may add in another order or fuse, one fp64 ulp away: that can move p_j only where the value before rint lies
+ *   within about 1e-5 of a half-integer.)
+ * esr_ycbcr_image — x -> out uint8 [B][H][W][3] in B, G, R order (what util.tensor2img returns and cv2.imwrite takes): p_2, p_1, p_0 of every
+ *   pixel; one read per input value, 3 bytes out.  Where W is a multiple of 4, x is 16-byte and out 4-byte aligned, a thread owns four adjacent
+ *   pixels and stores three whole dwords; otherwise one pixel, byte stores; the same bits either way.  B up to 65535.
+ * esr_psnr_ssim_ycbcr — sums[b] as esr_psnr_ssim gives them, of the 3 x H' x W' pixels p_j of a[b] against those of the image that starts
+ *   b_batch_stride * b elements into the second operand: b_batch_stride is C H W (b is [B][C][H][W]) or 0 (every image of a against the one image b).  The workgroup of
+ *   channel j reads the C planes of both operands and keeps p_j; nothing converted is written.  `partial`: 2 B esr_psnr_ssim_ycbcr_partials(C, H,
+ *   W, border) doubles.  3 B and H' / 21 up to 65535.  PSNR = 20 log10(255 / sqrt(sums[b][0] / (3 H' W'))), SSIM = sums[b][1] / (3 (H' - 10)(W' - 10)).
+ * esr_sample_std_ycbcr — x is fp32 [S][B][C][H][W]: map[b][j][y][x] = the population STD over the S samples of p_j (np.std of the rounded uint8
+ *   pixels, codes/test_JPEG.py:263; R, G, B planes), two passes in fp64 with the conversion repeated in the second, stored as fp32;
+ *   sums[b] = the fp64 sum of the un-rounded values (mean = sums[b] / (3 H W)).  S = 1 gives zeros.  `partial`: B
+ *   esr_sample_std_ycbcr_partials(C, H, W) doubles.  B up to 65535.
+ * All: ESR_E_ARG, with nothing written, for a NULL pointer, C other than 1 or 3, B, S, H or W below 1, hi <= lo, a border that leaves nothing, a
+ *   b_batch_stride other than the two above; ESR_E_UNSUPPORTED beyond the limits named. */
+int esr_ycbcr_image(const float* x, int B, int C, int H, int W, float lo, float hi, uint8_t* out, esr_stream_t stream);
+int64_t esr_psnr_ssim_ycbcr_partials(int C, int H, int W, int border);
+int esr_psnr_ssim_ycbcr(const float* a, const float* b, int B, int C, int H, int W, int64_t b_batch_stride, float lo, float hi, int border,
+                        double* partial, double* sums, esr_stream_t stream);
+int64_t esr_sample_std_ycbcr_partials(int C, int H, int W);
+int esr_sample_std_ycbcr(const float* x, int S, int B, int C, int H, int W, float lo, float hi, float* map, double* partial, double* sums,
+                         esr_stream_t stream);
+
 /* ---- LR/HR training batches from images resident on the device (codes/data/LRHR_dataset.py:48-131, codes/data/util.py:95-130) ----
  * One item of a batch: where its decoded image lies and which crop and augmentation were drawn for it.  Images are HWC uint8, 3 channels in BGR
  * order (cv2.imread's) or 1 channel.  H and W are the LOGICAL size: they may be smaller than what is stored (util.modcrop of the validation phase is

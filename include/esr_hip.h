@@ -887,6 +887,66 @@ int esr_data_lrhr_plan(int sf, int k, int pre, int32_t* tile_lo_win);
 int esr_data_lrhr_batch(const esr_data_item* items, const esr_data_item* items_dev, int B, int sf, const float* taps, int k, int pre, int ph, int pw,
                         const esr_data_channel_map* map, float* hr, float* lr, esr_stream_t stream);
 
+/* ---- Kernel estimation (KernelGAN) for E images in lock step (csrc/esr_kgan.hip; codes/KernelGAN/) ----
+ * All tensors are dense fp32 with a leading estimation index E (and, for the critic, a pass index in front of it: the real and the fake forward of
+ * one D step are the two passes of the same launches).  A launch is the only barrier; there are no atomics, every reduction has a fixed order:
+ * two runs give the same bits, and estimation e of a batch gets the bits a batch of one gets.  Every entry point checks its arguments before it
+ * touches the device: ESR_E_ARG for a NULL pointer, E outside 1..65535 or a non-positive size; ESR_E_UNSUPPORTED as said per function.
+ *
+ * The generator is linear (six bias-free convolutions), so it is applied as ONE 13 x 13 kernel k composed from its layers:
+ * esr_kgan_compose — one layer of the composition: out[e][d] = sum_c in[e][c] (*) w[e][d][c], the full 2-D convolution of the s x s planes
+ *   in [E][Cin][s][s] with the f x f filters w [E][Cout][Cin][f][f]; out [E][Cout][s+f-1][s+f-1].  The chain starts from in = the first layer's
+ *   weights [E][C][7][7] and ends at k [E][1][13][13] = codes/KernelGAN/kernelGAN.py:58-63's curr_k.  ESR_E_UNSUPPORTED: Cin or Cout > 64, s+f-1 > 13.
+ * esr_kgan_compose_bwd — its adjoint: din [E][Cin][s][s] and dw [E][Cout][Cin][f][f] from dout.
+ * esr_kgan_apply — y [E][3][oh][ow] = (x corr k)[::2, ::2] per colour plane of the crop x [E][3][H][W], oh = (H - 13) / 2 + 1.  noise given:
+ *   y_noisy = y + noise / 255.  bic_taps (device, 8 x 8) given: bic [E][oh][ow], the reference's bicubic term (stride 2, padding 3, shaved to y's
+ *   size, every plane the SUM over the three input planes), and partial [E][esr_kgan_apply_blocks(H, W)] partial sums of (y - bic)^2.
+ *   ESR_E_UNSUPPORTED: H or W odd or below 14 (a crop smaller than the shave).
+ * esr_kgan_dk — dk [E][13][13] = d/dk of sum(dy * y) with dy = dgan (optional, [E][3][oh][ow]) + lam[e][0] * 2 / N * (y - bic) (when bic is given;
+ *   N = 3 oh ow, so that is lambda_bicubic times the gradient of the mean squared distance).
+ * esr_kgan_constraints — the terms on k: losses [E][5] = (bicubic = sum(partial) / n_outputs, sum2one, boundaries with `mask` [13][13], centralized,
+ *   sparse) and dk += lam[e][1..4] times their gradients; lam [E][5] = (bicubic, sum2one, boundaries, centralized, sparse).  log given:
+ *   log[e * log_stride + slot] = the bicubic loss (the learner's record).  (|k|^0.2 has no gradient at 0: it counts as 0 there.)
+ * esr_kgan_gather — crops: out [E][3][S][S] = 2 (img + noise / 255) - 1 from resident CHW planes in [0, 1]; meta [E][3] = (offset in floats, H, W)
+ *   and top_left [E][2], both in device memory; corners are clamped into the image.  ESR_E_UNSUPPORTED: S > 1024.
+ *
+ * The critic: conv 7x7 3->C, five [conv 1x1 C->C, BatchNorm, ReLU], conv 1x1 C->1, sigmoid; all convs spectrally normalised, with bias.
+ * Its parameters are ONE flat vector per estimation, esr_kgan_d_param_count(C) floats: W0 [C][3][7][7], b0 [C]; for l = 1..5: W [C][C], b, gamma,
+ * beta [C]; W6 [C], b6 [1].  The power-iteration vectors are one vector of esr_kgan_d_uv_count(C) floats: per layer u [Cout] then v [Cin kh kw].
+ * ESR_E_UNSUPPORTED for all of them: C no multiple of 8 or outside 8..64; an input below 7 x 7 or with more than 2048 output positions.
+ * npass is 1 or 2; per-pass tensors are [npass][E][...].
+ * esr_kgan_d_spectral — one power iteration per pass and layer (pass 1 starts from pass 0's u), eps 1e-12: uv updated in place; per pass the
+ *   normalised weights wn (the parameter layout, weight slots only), the u and v used (uv_used) and sigma [npass][E][7] = u^T W v.
+ * esr_kgan_d_forward — x [npass][E][3][H][W] through the critic in training mode (batch statistics of the one image, biased variance, eps 1e-5).
+ *   act and xhat [npass][E][6][C][P], rstd [npass][E][6][C] are kept for the backward (P = (H-6)(W-6)); pred [npass][E][P] is the sigmoid map,
+ *   loss [npass][E] = mean |pred - label_pass|, dz6 [npass][E][P] = scale * d loss / d(pre-sigmoid).  gp given ([npass][E][param count]): the
+ *   last layer's parameter gradients are written there.
+ * esr_kgan_d_backward — from dz6 back to the input.  dz [npass][E][6][C][P] is work space.  gp given: the gradients of every parameter per pass,
+ *   those of the weights taken at the NORMALISED weights.  dx given: [npass][E][3][H][W], the data gradient.  One of the two is required.
+ * esr_kgan_d_finish — grad [E][param count] = sum over the passes, in pass order, of the gradient at the stored weights:
+ *   (G - <G, Wn> u v^T) / sigma with u and v constants (torch.nn.utils.spectral_norm's backward), biases and BatchNorm parameters summed. */
+int esr_kgan_compose(const float* in, const float* w, float* out, int E, int Cin, int Cout, int s, int f, esr_stream_t stream);
+int esr_kgan_compose_bwd(const float* in, const float* w, const float* dout, float* din, float* dw, int E, int Cin, int Cout, int s, int f,
+                         esr_stream_t stream);
+int esr_kgan_apply_blocks(int H, int W);
+int esr_kgan_apply(const float* x, const float* k, const float* bic_taps, const float* noise, float* y, float* y_noisy, float* bic, float* partial,
+                   int E, int H, int W, esr_stream_t stream);
+int esr_kgan_dk(const float* x, const float* y, const float* bic, const float* dgan, const float* lam, float* dk, int E, int H, int W,
+                esr_stream_t stream);
+int esr_kgan_constraints(const float* k, float* dk, const float* mask, const float* lam, const float* partial, int npartial, int n_outputs,
+                         float* losses, float* log, int log_stride, int slot, int E, esr_stream_t stream);
+int esr_kgan_gather(const float* imgs, const int64_t* meta, const int32_t* top_left, const float* noise, float* out, int E, int S,
+                    esr_stream_t stream);
+int esr_kgan_d_param_count(int C);
+int esr_kgan_d_uv_count(int C);
+int esr_kgan_d_spectral(const float* params, float* uv, float* wn, float* uv_used, float* sigma, int E, int C, int npass, esr_stream_t stream);
+int esr_kgan_d_forward(const float* x, const float* params, const float* wn, float* act, float* xhat, float* rstd, float label0, float label1,
+                       float scale, float* pred, float* loss, float* dz6, float* gp, int E, int C, int H, int W, int npass, esr_stream_t stream);
+int esr_kgan_d_backward(const float* x, const float* params, const float* wn, const float* act, const float* xhat, const float* rstd,
+                        const float* dz6, float* dz, float* gp, float* dx, int E, int C, int H, int W, int npass, esr_stream_t stream);
+int esr_kgan_d_finish(const float* gp, const float* wn, const float* uv_used, const float* sigma, float* grad, int E, int C, int npass,
+                      esr_stream_t stream);
+
 int esr_version(void);
 
 #ifdef __cplusplus

@@ -98,6 +98,30 @@ class JPEG(nn.Module):
                 self.Q_table = self._three(self.Q_table, self.process_Q_table(np.asarray(QF_or_table[1])))
                 self.padded_Q_table = self._three(self.process_Q_table(self._padded(QF_or_table[0])), self.process_Q_table(self._padded(QF_or_table[1])))
 
+    def Set_File_Q_Table(self, luminance, chrominance=None):
+        """The tables of a JPEG file in the model's domain (esr_hip.jpeg_file.JpegFile.model_data): real-valued [8, 8] arrays or tensors, taken
+        as they are — not rounded, not clamped to 1...255, not divided by 100 (Set_Q_Table(QF=False) does the last, as the reference does).
+        chroma_mode needs both; the 16x16 tables are the edge-padded ones.  self.QF: from the luminance table given, by Set_Q_Table(QF=False)'s
+        formula."""
+        def as_numpy(t):
+            t = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+            if t.shape != (8, 8) or not np.all(np.isfinite(t)) or not np.all(t > 0):
+                raise ValueError('JPEG.Set_File_Q_Table: positive [8, 8] tables, got shape %s' % (t.shape,))
+            return t.astype(np.float64)
+
+        def as_table(t):
+            return torch.from_numpy(t).view(1, t.shape[0], t.shape[1], 1, 1).type(torch.FloatTensor)
+        luminance = as_numpy(luminance)
+        tables_ratio = np.mean(LUMINANCE_QUANTIZATION_TABLE / luminance)
+        self.QF = 50 * tables_ratio if tables_ratio < 1 else 50 * np.mean((2 * LUMINANCE_QUANTIZATION_TABLE - luminance) / LUMINANCE_QUANTIZATION_TABLE)
+        self.Q_table = as_table(luminance)
+        if self.chroma_mode:
+            if chrominance is None:
+                raise ValueError('JPEG.Set_File_Q_Table: chroma_mode needs the chrominance table as well')
+            chrominance = as_numpy(chrominance)
+            self.Q_table = self._three(self.Q_table, as_table(chrominance))
+            self.padded_Q_table = self._three(as_table(self._padded(luminance)), as_table(self._padded(chrominance)))
+
     def _table_on(self, device):
         name = 'padded_Q_table' if self.chroma_mode else 'Q_table'
         if not hasattr(self, name):

@@ -49,7 +49,8 @@ training mode (HR_unpadder), the region constraint (non_local_Z_optimization on 
 six names above (the other local and periodicity ones refuse it, the whole-image ones ignore it), the '*_localSTD' histogram variants and the
 automatic histogram temperature.
 JPEG mode (jpeg_extractor given; models/DecompCNN_model.py): the model's fake_H holds DCT coefficients and its image is output_image (0...255),
-Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' in place of 'LR'.  Accepted on either model: 'l1',
+Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' (or a JPEG file's 'Q_table', and for the colour
+model its 'compressed_chroma': esr_hip.jpeg_file.JpegFile.model_data) in place of 'LR'.  Accepted on either model: 'l1',
 'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease'.  On a colour model (chroma_mode) Z_size is still the Y grid, the objectives see the RGB
 output, Z's gradient runs through both generators, and a model fed with the Y coefficients as 'Comp' gets data['uncompressed_chroma']
 ([B, 2, H, W] Cb, Cr) passed to model.test.  The colour model (the one the reference's JPEG GUI builds) also takes the editing objectives: the
@@ -585,7 +586,8 @@ class Z_optimizer():
 
     def _local_data(self):
         d = dict(self.data)
-        keys = [k for k in ('Uncomp', 'Comp', 'QF', 'uncompressed_chroma') if k in d] if self.jpeg_mode else ['LR']
+        # ('Q_table', a JPEG file's tables in place of 'QF', is one set for the whole batch: not sharded)
+        keys = [k for k in ('Uncomp', 'Comp', 'QF', 'uncompressed_chroma', 'compressed_chroma') if k in d] if self.jpeg_mode else ['LR']
         for k in keys:
             t = d[k]
             if t.size(0) == self.global_batch and self.global_batch > 1:
@@ -623,6 +625,8 @@ class Z_optimizer():
             self.model.fake_H = self.model.output_image = None
             if self.jpeg_mode and data.get('uncompressed_chroma') is not None:      # colour model fed with Y coefficients (reference :679)
                 self.model.test(prevent_grads_calc=False, uncompressed_chroma=data['uncompressed_chroma'])
+            elif self.jpeg_mode and data.get('compressed_chroma') is not None:      # colour model fed from a JPEG file (esr_hip.jpeg_file)
+                self.model.test(prevent_grads_calc=False, compressed_chroma=data['compressed_chroma'])
             else:
                 self.model.test(prevent_grads_calc=False)
             if self.jpeg_mode:       # one colour conversion per iteration; Output_Batch(within_0_1=True) is its clamp

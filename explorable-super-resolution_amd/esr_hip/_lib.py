@@ -66,6 +66,14 @@ class DataItem(C.Structure):
                 ('y0', C.c_int32), ('x0', C.c_int32), ('flags', C.c_int32), ('lr_H', C.c_int32), ('lr_W', C.c_int32), ('lr_stride', C.c_int32)]
 
 
+class JpegInfo(C.Structure):
+    """esr_jpeg_info (include/esr_hip.h)."""
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('components', C.c_int32), ('sof', C.c_int32), ('restart_interval', C.c_int32),
+                ('mcus_h', C.c_int32), ('mcus_w', C.c_int32), ('blocks_per_mcu', C.c_int32), ('reason', C.c_int32), ('reserved', C.c_int32),
+                ('h', C.c_int32 * 4), ('v', C.c_int32 * 4), ('tq', C.c_int32 * 4), ('blocks_h', C.c_int32 * 4), ('blocks_w', C.c_int32 * 4),
+                ('scan_blocks', C.c_int64)]
+
+
 class DataChannelMap(C.Structure):
     """esr_data_channel_map (include/esr_hip.h)."""
     _fields_ = [('mode', C.c_int32), ('reserved', C.c_int32), ('w', C.c_double * 3), ('b', C.c_double), ('scale', C.c_double)]
@@ -271,6 +279,10 @@ _SIGS = {
     'esr_jpeg_violation': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'esr_jpeg_pair': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'esr_jpeg16_pair': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'esr_jpeg_file_info': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(JpegInfo)]),
+    'esr_jpeg_file_decode': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(JpegInfo)]),
+    'esr_jpeg_file_unpack': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.POINTER(ActView), C.c_void_p]),
     'esr_psnr_ssim_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'esr_psnr_ssim': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),
@@ -350,12 +362,13 @@ class _LazyLib:
 
 lib = _LazyLib()
 
-ESR_OK, ESR_E_ARG, ESR_E_UNSUPPORTED, ESR_E_LAUNCH = 0, -1, -2, -3
+ESR_OK, ESR_E_ARG, ESR_E_UNSUPPORTED, ESR_E_LAUNCH, ESR_E_DATA = 0, -1, -2, -3, -4
 PIXELS_FLOAT, PIXELS_ROUND, PIXELS_RAW = 0, 1, 2     # esr_psnr_ssim `quantize`
 DATA_HFLIP, DATA_VFLIP, DATA_TRANSPOSE = 1, 2, 4      # esr_data_item `flags`
 DATA_MAP_RGB, DATA_MAP_MIX = 0, 1                     # esr_data_channel_map `mode`
 PACK_FOLD2 = 2              # esr_pack_conv_weights / esr_pack_desc `transposed` = PACK_FOLD2 + first phase: the folded pack of a phase launch
-_ERR = {-1: 'ESR_E_ARG (bad argument)', -2: 'ESR_E_UNSUPPORTED (unsupported shape)', -3: 'ESR_E_LAUNCH (HIP launch error)'}
+_ERR = {-1: 'ESR_E_ARG (bad argument)', -2: 'ESR_E_UNSUPPORTED (unsupported shape)', -3: 'ESR_E_LAUNCH (HIP launch error)',
+        -4: 'ESR_E_DATA (truncated or corrupt data)'}
 
 
 def check(rc, what):

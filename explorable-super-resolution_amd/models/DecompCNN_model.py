@@ -86,10 +86,24 @@ class DecompCNNModel(BaseModel):
         """data: 'QF' and either 'Uncomp' (an image: [B, 1, H, W], or [B, 3, H, W] YCbCr for the colour model, whose Y model then runs here —
         with gradients when detach_Y is False) or 'Comp' (coefficients; for the colour model the Y channel's [B, 64, H/8, W/8], followed by
         test(uncompressed_chroma=[B, 2, H, W])); optionally 'Z' on the Y grid [H/8, W/8].  The caller's tensors are left as they are (the
-        reference writes the generated Y channel into data['Uncomp'])."""
-        self.QF = data['QF']
-        for module in self.JPEG.values():
-            module.Set_Q_Table(self.QF)
+        reference writes the generated Y channel into data['Uncomp']).
+
+        In place of 'QF', 'Q_table' [1 or 2, 8, 8]: the real-valued luminance (and, for the colour model, chrominance) tables of a JPEG file in
+        the model's domain, with the file's coefficients as 'Comp' (esr_hip.jpeg_file.JpegFile.model_data); the colour model then takes the
+        file's chroma coefficients through test(compressed_chroma=...)."""
+        if data.get('Q_table') is not None:
+            tables = data['Q_table']                 # to the host once: every module below takes the same arrays
+            tables = tables.detach().cpu().numpy() if torch.is_tensor(tables) else np.asarray(tables)
+            if tables.ndim != 3 or tables.shape[0] < (2 if self.chroma_mode else 1):
+                raise ValueError("DecompCNNModel.feed_data: data['Q_table'] is [1, 8, 8] (luminance) or [2, 8, 8] (luminance, chrominance; needed "
+                                 'by the colour model), got %s' % (tuple(tables.shape),))
+            for module in self.JPEG.values():
+                module.Set_File_Q_Table(tables[0], tables[1] if module.chroma_mode else None)
+            self.QF = self.JPEG['extractor'].QF
+        else:
+            self.QF = data['QF']
+            for module in self.JPEG.values():
+                module.Set_Q_Table(self.QF)
         if self.latent_input is not None:
             input_size = np.array(data['Uncomp'].size()) if 'Uncomp' in data.keys() else [1, 1, 8, 8] * np.array(data['Comp'].size())
             DCT_dims = [int(v) for v in input_size[2:] // 8]
@@ -216,8 +230,27 @@ class DecompCNNModel(BaseModel):
         if detach:
             self.y_channel_input = self.y_channel_input.detach()
 
-    def test_(self, uncompressed_chroma=None, detach_Y=False, chroma_Z=None):
+    def test_(self, uncompressed_chroma=None, detach_Y=False, chroma_Z=None, compressed_chroma=None):
+        """compressed_chroma [B or 1, 128, H/16, W/16]: a JPEG file's chroma coefficients in the model's domain (JpegFile.model_data) in the
+        place of round(compress(uncompressed_chroma)) in var_Comp — they are exact, where the uncompressed_chroma route passes them through the
+        compressor's rounding; Y's 256 coefficients come from the generated Y plane as always."""
         self.netG.eval()
+        if compressed_chroma is not None:
+            if not self.chroma_mode or uncompressed_chroma is not None:
+                raise ValueError('DecompCNNModel.test(compressed_chroma=...) belongs to the colour model (chroma_mode=True), in place of uncompressed_chroma')
+            if self.var_Comp.size(1) != 64:
+                raise ValueError("DecompCNNModel.test(compressed_chroma=...) follows feed_data with the file's Y coefficients as 'Comp'")
+            B, H, W = self.var_Comp.size(0), 8 * self.var_Comp.size(2), 8 * self.var_Comp.size(3)
+            if compressed_chroma.dim() != 4 or tuple(compressed_chroma.shape[1:]) != (128, H // 16, W // 16) or compressed_chroma.size(0) not in (1, B) \
+                    or H % 16 or W % 16:
+                raise ValueError('DecompCNNModel.test: compressed_chroma %s for a Y plane of %d x %d (expected [%d or 1, 128, H/16, W/16])' % (
+                    tuple(compressed_chroma.shape), H, W, B))
+            self.test_Y(detach=detach_Y, prevent_grads_calc=False)
+            y = self.y_channel_input
+            compressed_chroma = compressed_chroma.to(device=y.device, dtype=y.dtype)
+            latent = self.GetLatent() if chroma_Z is None else chroma_Z
+            y_coef = self.JPEG['compressor'](torch.cat([y, y.new_zeros(B, 2, H, W)], 1))[:, :256]      # (Y is never rounded there)
+            self.Prepare_Input(torch.cat([y_coef, compressed_chroma.expand(B, -1, -1, -1)], 1), latent, compressed_input=True)
         if uncompressed_chroma is not None:          # colour model fed with the Y coefficients (reference :720-724)
             if not self.chroma_mode:
                 raise ValueError('DecompCNNModel.test(uncompressed_chroma=...) belongs to the colour model (chroma_mode=True)')

@@ -41,6 +41,7 @@ extern "C" {
 #define ESR_E_ARG (-1)        /* NULL / inconsistent argument */
 #define ESR_E_UNSUPPORTED (-2) /* shape outside what the kernels implement */
 #define ESR_E_LAUNCH (-3)      /* HIP reported a launch error */
+#define ESR_E_DATA (-4)        /* the bytes given are not what they claim to be (esr_jpeg_file_*: a truncated or corrupt file) */
 
 typedef void* esr_stream_t;   /* hipStream_t */
 
@@ -778,6 +779,60 @@ int esr_jpeg_pair(const float* desired, int B, int H, int W, const float* coef, 
  *   No gradient. */
 int esr_jpeg16_pair(const float* desired, int desired_C, int B, int H, int W, const float* coef, int coef_C, int coef_c0, const float* qtab,
                     float* out, esr_stream_t stream);
+
+/* ---- JPEG files into the explorable decoder's inputs (no counterpart in the reference: its GUI.py:2425-2462 is marked as not working) ----
+ * Host side: baseline entropy decoding, no device involved (csrc/esr_jpeg_parse.h).  Accepted: SOF0 / SOF1, 8-bit samples, ONE interleaved scan
+ * of 1 component or of 3 components at 4:2:0 or 4:4:4, 8- and 16-bit DQT entries, tables redefined before the scan, APPn / COM, fill bytes,
+ * 0xFF00 stuffing, DRI with RSTn.  ESR_E_UNSUPPORTED with info->reason ESR_JPEG_R_PROGRESSIVE (SOF2), _SOF_KIND (lossless, hierarchical),
+ * _ARITHMETIC, _PRECISION (12-bit), _SCANS (non-interleaved or several scans), _SAMPLING (4:2:2, 4:4:0, ...), _COMPONENTS (2 or 4),
+ * _COLORSPACE (three components that an Adobe APP14 segment with transform 0 marks as RGB: three components are read as YCbCr).
+ * ESR_E_DATA with reason _TRUNCATED, _BAD_CODE (a code in no table, a category past 11 / 10), _RUN (a run past coefficient 63), _NO_TABLE,
+ * _RST (a wrong restart number), _DIMENSION (zero width or height), _SEGMENT (a malformed segment), _NOT_JPEG (no SOI).  Bad input never
+ * crashes and never spins: every read is checked against n and every loop is bounded by n or by the block count.  Both calls are
+ * re-entrant (no state), so files may be decoded on several host threads at once.
+ *
+ * esr_jpeg_file_info   — reads up to the scan header.  mcus_h x mcus_w MCUs of blocks_per_mcu blocks (h[c] x v[c] of component c, in
+ *   component order); blocks_h / blocks_w: the component's block grid, padded to whole MCUs; scan_blocks: blocks in the file;
+ *   sof: 0 or 1; tq[c]: the component's table.  A one-component file reports h = v = 1 whatever it says (its scan is not interleaved).
+ * esr_jpeg_file_decode — scan: scan_len >= 64 scan_blocks int16, filled in scan order (MCU after MCU, blocks in the MCU's order, 64 values per
+ *   block in zigzag order, DC prediction undone); tables: 4 x 64 uint16 in natural order (row-major u, v; 0: never defined); info optional.
+ *   ESR_E_ARG: a NULL pointer, n < 0, scan_len too small.  On failure scan may be partly written and tables are not. */
+#define ESR_JPEG_R_PROGRESSIVE 1
+#define ESR_JPEG_R_SOF_KIND 2
+#define ESR_JPEG_R_ARITHMETIC 3
+#define ESR_JPEG_R_PRECISION 4
+#define ESR_JPEG_R_SCANS 5
+#define ESR_JPEG_R_SAMPLING 6
+#define ESR_JPEG_R_COMPONENTS 7
+#define ESR_JPEG_R_COLORSPACE 8
+#define ESR_JPEG_R_TRUNCATED 32
+#define ESR_JPEG_R_BAD_CODE 33
+#define ESR_JPEG_R_RUN 34
+#define ESR_JPEG_R_NO_TABLE 35
+#define ESR_JPEG_R_RST 36
+#define ESR_JPEG_R_DIMENSION 37
+#define ESR_JPEG_R_SEGMENT 38
+#define ESR_JPEG_R_NOT_JPEG 39
+typedef struct {
+    int32_t width, height, components, sof, restart_interval, mcus_h, mcus_w, blocks_per_mcu, reason, reserved;
+    int32_t h[4], v[4], tq[4], blocks_h[4], blocks_w[4];
+    int64_t scan_blocks;
+} esr_jpeg_info;
+int esr_jpeg_file_info(const uint8_t* bytes, int64_t n, esr_jpeg_info* info);
+int esr_jpeg_file_decode(const uint8_t* bytes, int64_t n, int16_t* scan, int64_t scan_len, uint16_t* tables, esr_jpeg_info* info);
+/* esr_jpeg_file_unpack — device side: the scan-order buffer of ONE file (uploaded as it is, 16-byte aligned) into the models' tensors, one
+ *   launch.  An MCU holds y_h x y_v Y blocks (1 x 1 or 2 x 2) and n_chroma (0 or 2) chroma blocks.
+ *     y_out (optional) fp32 [64][mcus_h y_v][mcus_w y_h]: channel 8u + v of block (i, j) = the Y block's coefficient at zigzag position of
+ *       (u, v), as float, + y_dc on channel 0 — JPEG.forward's coefficient layout on the 8 x 8 grid;
+ *     c_out (optional, n_chroma = 2) fp32 [128][mcus_h][mcus_w]: Cb | Cr likewise, + c_dc on channels 0 and 64 — the colour model's chroma
+ *       coefficients on its 16 x 16 grid for a 4:2:0 file;
+ *     act_out (optional): y_out's values in groups [0, 8) of an activation view of image 0 (as esr_jpeg_compress's act_out).
+ *   A workgroup stages 32 MCUs of one MCU row in LDS (16-byte reads of the scan buffer) and stores rows of consecutive blocks of one
+ *   channel (consecutive addresses).  ESR_E_ARG, with nothing written: a NULL scan, no output, a non-positive count, y_h / y_v other than 1 x 1
+ *   or 2 x 2, n_chroma other than 0 or 2, c_out without chroma blocks, scan not 16-byte aligned, an act_out of fewer than 8 groups, of another
+ *   size or format.  ESR_E_UNSUPPORTED: more than 65535 MCU rows. */
+int esr_jpeg_file_unpack(const int16_t* scan, int mcus_h, int mcus_w, int y_h, int y_v, int n_chroma, float y_dc, float c_dc, float* y_out,
+                         float* c_out, const esr_act_view* act_out, esr_stream_t stream);
 
 /* ---- scores of the SR output: PSNR, SSIM and the spread over Z samples (codes/utils/util.py:196-228, :340-391; codes/test.py:198-242) ----
  * esr_psnr_ssim — a and b are fp32 [B][C][H][W], C 1 or 3.  Every value becomes a pixel as util.tensor2img makes one, in fp32 and in this order:

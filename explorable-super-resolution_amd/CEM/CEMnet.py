@@ -73,6 +73,25 @@ class CEMnet:
         self.invalidity_margins_LR = 2 * self.ds_kernel_invalidity_half_size_LR + self.inv_hTh_invalidity_half_size
         self.invalidity_margins_HR = self.ds_factor * self.invalidity_margins_LR
 
+    @classmethod
+    def build_per_image(cls, conf_factory, kernels):
+        """[CEMnet(conf_factory(k), upscale_kernel=k) for k in kernels] — one CEM per image of a batch (CEM_PyTorch.set_per_image_kernels) — without
+        the side effect of building a CEMnet around a kernel: imresize caches the kernel in use process-wide (`imresize.kernels[str(sf)]`,
+        'Overriding previous kernel...') and every later resize, of any object, would run the last image's.  Every build starts from the cache as
+        it was found — so None means the kernel in use before the call, for every image alike — and the cache is handed back as it was found."""
+        had, before = hasattr(imresize, 'kernels'), dict(getattr(imresize, 'kernels', {}))
+        nets = []
+        try:
+            for kernel in kernels:
+                imresize.kernels = dict(before)
+                nets.append(cls(conf_factory(kernel), upscale_kernel=kernel))
+        finally:
+            imresize.kernels = before
+            if not had:
+                del imresize.kernels
+        assert len({int(n.ds_factor) for n in nets}) <= 1, 'one scale factor per batch'
+        return nets
+
     # ---------------------------------------------------------------- construction helpers
     def Return_Invalid_Margin_Size_in_LR(self, filter, max_allowed_perturbation):
         """How many LR pixels from the border a filter's response to a constant image deviates by more than the allowed
@@ -196,9 +215,10 @@ class Filter_Layer(nn.Module):
         self.pre_filter_func = pre_filter_func
         self.post_filter_func = (lambda x: x) if post_filter_func is None else post_filter_func
         self.role, self.sf, self.pre_stride = role, int(sf), int(pre_stride)
+        self.per_image_taps = None     # [B, k, k]: one tap set per image (CEM_PyTorch.set_per_image_kernels); a plain attribute, never in state_dict()
 
     def taps(self):
-        return self.Filter_OP.weight[0, 0]
+        return self.Filter_OP.weight[0, 0] if self.per_image_taps is None else self.per_image_taps
 
     def forward(self, x):
         if self.role == 'lr_filter':
@@ -236,6 +256,7 @@ class CEM_PyTorch(nn.Module):
         self.HR_unpadder = CEMnet.HR_unpadder
         self.LR_unpadder = CEMnet.LR_unpadder   # debugging tool
         self.margins_LR = int(CEMnet.invalidity_margins_LR)
+        self._own_margins_LR, self._per_image_count = self.margins_LR, None
         self.pre_pad = False   # a flag rather than a forward() argument, as in the reference (set by .train()/.eval())
         self.return_2_components = 'decomposed_output' in self.conf.__dict__ and self.conf.decomposed_output
 
@@ -245,7 +266,52 @@ class CEM_PyTorch(nn.Module):
         GPU needs no wrapper, so the module is its own `.module`."""
         return self
 
+    def _filter_layers(self):
+        return self.Conv_LR_with_Inv_hTh_OP, self.Upscale_OP, self.DownscaleOP
+
+    def set_margins_LR(self, margin):
+        """The eval-mode padding, in LR pixels: margins_LR and the padders / unpadders that go with it."""
+        mL = int(margin)
+        mH = int(self.ds_factor) * mL
+        self.margins_LR = mL
+        self.LR_padder = torch.nn.ReplicationPad2d((mL, mL, mL, mL))
+        self.HR_padder = torch.nn.ReplicationPad2d((mH, mH, mH, mH))
+        self.HR_unpadder = lambda x: x[:, :, mH:-mH, mH:-mH]
+        self.LR_unpadder = lambda x: x[:, :, mL:-mL, mL:-mL]
+
+    def set_per_image_kernels(self, nets):
+        """Image b of every later batch is projected with the kernel of nets[b] (CEMnet objects of this CEM's ds_factor — CEMnet.build_per_image),
+        in forward() and in calls to DownscaleOP / Upscale_OP / Conv_LR_with_Inv_hTh_OP; None goes back to the kernel this module was built with.
+        The three filters become [B, k, k] fp32 arrays, every image's taps zero-padded symmetrically to the batch's largest odd size (the centre
+        stays at floor(k / 2); the padded taps multiply by zero), and the eval-mode margin the batch's largest.  Forward only.
+        The arrays are plain attributes: parameters, buffers and state_dict() are untouched."""
+        if nets is None:
+            for layer in self._filter_layers():
+                layer.per_image_taps = None
+            self._per_image_count = None
+            self.set_margins_LR(self._own_margins_LR)
+            return
+        nets = list(nets)
+        assert nets and all(int(n.ds_factor) == int(self.ds_factor) for n in nets), 'per-image kernels: CEMnet objects of this ds_factor'
+        sf = int(self.ds_factor)
+        dev = self.DownscaleOP.Filter_OP.weight.device
+
+        def stack(arrays):
+            k = max(a.shape[0] for a in arrays)
+            assert all(a.shape[0] == a.shape[1] and a.shape[0] % 2 == 1 for a in arrays), 'CEM filters are odd square arrays'
+            padded = [np.pad(a, (k - a.shape[0]) // 2, mode='constant') for a in arrays]
+            return torch.from_numpy(np.ascontiguousarray(np.stack(padded))).float().to(dev)
+        self.Conv_LR_with_Inv_hTh_OP.per_image_taps = stack([n.inv_hTh for n in nets])
+        self.Upscale_OP.per_image_taps = stack([n.ds_kernel * sf ** 2 for n in nets])
+        self.DownscaleOP.per_image_taps = stack([np.rot90(n.ds_kernel, 2) for n in nets])
+        self._per_image_count = len(nets)
+        self.set_margins_LR(max(int(n.invalidity_margins_LR) for n in nets))
+
     def forward(self, x):
+        if self._per_image_count is not None:
+            B = (x if self.using_SR_model else x[0]).size(0)
+            if B != self._per_image_count:
+                raise ValueError('per-image kernels: %d kernels were set, the batch has %d images' % (self._per_image_count, B))
         return_2_components = self.return_2_components and not self.pre_pad
         sf = int(self.ds_factor)
         mL = self.margins_LR if self.pre_pad else 0

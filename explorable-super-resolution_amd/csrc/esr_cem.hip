@@ -43,14 +43,19 @@ __device__ __forceinline__ TileId xcd_tile() {
     return id;
 }
 
+// PER (every 2-D kernel below): `taps` is [B][k][k], one tap set per image shared by its C planes (the *_per_image entry points), instead of one
+// [k][k] set for every plane.  The shared instantiations are the kernels as they were: C is not read.  In the tiled kernels the plane is the
+// workgroup's (blockIdx.z), so the image's tap pointer is workgroup-uniform and the taps stay scalar loads; in the flat ones it is per thread.
+template <bool PER>
 __global__ void cem_downscale_kernel(const float* __restrict__ y, int h, int w, int sf, int pre, const float* __restrict__ taps, int k,
-                                     const float* __restrict__ lr, int lr_pad, float* __restrict__ d, long long total) {
+                                     const float* __restrict__ lr, int lr_pad, float* __restrict__ d, long long total, int C) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int j = (int)(idx % w);
     long long t = idx / w;
     const int i = (int)(t % h);
     const long long bc = t / h;
+    if (PER) taps += (bc / C) * k * k;
     const int Hh = h * sf, Wh = w * sf, p = k / 2;
     const float* src = y + bc * Hh * (long long)Wh;
     const int Y0 = sf * i + pre - p, X0 = sf * j + pre - p;
@@ -71,14 +76,16 @@ __global__ void cem_downscale_kernel(const float* __restrict__ y, int h, int w, 
     d[idx] = acc;
 }
 
+template <bool PER>
 __global__ void cem_lrfilter_kernel(const float* __restrict__ x, int h, int w, const float* __restrict__ taps, int k, float* __restrict__ out,
-                                    long long total) {
+                                    long long total, int C) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int j = (int)(idx % w);
     long long t = idx / w;
     const int i = (int)(t % h);
     const long long bc = t / h;
+    if (PER) taps += (bc / C) * k * k;
     const int p = k / 2;
     const float* src = x + bc * h * (long long)w;
     float acc = 0.f;
@@ -101,12 +108,14 @@ __global__ void cem_lrfilter_kernel(const float* __restrict__ x, int h, int w, c
 
 constexpr int LT_TY = 16, LT_TX = 64;     // lrfilter output tile: 16 rows x 64 columns, 4 outputs (x, x+16, x+32, x+48) per thread
 
+template <bool PER>
 __global__ __launch_bounds__(256) void cem_lrfilter_tiled_kernel(const float* __restrict__ x, int h, int w, const float* __restrict__ taps, int k,
-                                                               float* __restrict__ out, int pitch) {
+                                                               float* __restrict__ out, int pitch, int C) {
     extern __shared__ float tile[];          // (LT_TY + k - 1) rows x pitch; pitch % 32 == 16: two rows of 16 lanes hit disjoint banks
     const int p = k / 2;
     const int x0 = blockIdx.x * LT_TX, y0 = blockIdx.y * LT_TY;
     const long long bc = blockIdx.z;
+    if (PER) taps += (size_t)(blockIdx.z / (unsigned)C) * k * k;
     const float* src = x + bc * h * (long long)w;
     const int rows = LT_TY + k - 1, cols = LT_TX + k - 1;
     for (int e = threadIdx.x; e < rows * cols; e += 256) {
@@ -141,13 +150,15 @@ constexpr int DT = 16;                       // downscale output tile: 16 x 16 l
 
 // The input window is stored de-interleaved by column phase — plane[col % sf][row][col / sf] — so that for a given tap the 16 lanes of
 // an output row (input columns sf apart) read consecutive words; qpitch % 8 == 4 for sf = 4 (sf * qpitch % 32 == 16) spreads the rows.
+template <bool PER>
 __global__ __launch_bounds__(256) void cem_downscale_tiled_kernel(const float* __restrict__ y, int h, int w, int sf, int pre, const float* __restrict__ taps,
                                                                 int k, const float* __restrict__ lr, int lr_pad, float* __restrict__ d, int qpitch,
-                                                                int rows) {
+                                                                int rows, int C) {
     extern __shared__ float tile[];          // [sf][rows][qpitch]
     const int p = k / 2, Hh = h * sf, Wh = w * sf;
     const int j0 = blockIdx.x * DT, i0 = blockIdx.y * DT;
     const long long bc = blockIdx.z;
+    if (PER) taps += (size_t)(blockIdx.z / (unsigned)C) * k * k;
     const float* src = y + bc * Hh * (long long)Wh;
     const int Yb = sf * i0 + pre - p, Xb = sf * j0 + pre - p;        // window origin in the high-resolution frame
     const int cols = (DT - 1) * sf + k;
@@ -186,10 +197,10 @@ __global__ __launch_bounds__(256) void cem_downscale_tiled_kernel(const float* _
     }
 }
 
-template <bool TWO>
+template <bool TWO, bool PER>
 __global__ void cem_upscale_kernel(const float* __restrict__ f, const float* __restrict__ f2, int h, int w, int sf, int pre,
                                    const float* __restrict__ taps, int k, const float* __restrict__ g, int crop, int mode, float range,
-                                   float* __restrict__ out, float* __restrict__ out2, long long total) {
+                                   float* __restrict__ out, float* __restrict__ out2, long long total, int C) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int Hh = h * sf, Wh = w * sf, Ho = Hh - 2 * crop, Wo = Wh - 2 * crop, p = k / 2;
@@ -197,6 +208,7 @@ __global__ void cem_upscale_kernel(const float* __restrict__ f, const float* __r
     long long t = idx / Wo;
     const int yo = (int)(t % Ho);
     const long long bc = t / Ho;
+    if (PER) taps += (bc / C) * k * k;
     const int Y = yo + crop, X = xo + crop;
     const float* s1 = f + bc * h * (long long)w;
     const float* s2 = TWO ? f2 + bc * h * (long long)w : nullptr;
@@ -252,16 +264,17 @@ constexpr int UT_Y = 16, UT_X = 64;          // upscale output tile: 16 x 64 hig
 // Same arithmetic and edge rules as cem_upscale_kernel (polyphase: only taps that land on a sample; the replicate pad of the
 // zero-stuffed image replicates a sample column only when pre == 0 — the first — or pre == sf - 1 — the last), with the low-resolution window and the taps staged in LDS and
 // the per-tap index divisions replaced by increments.
-template <bool TWO>
+template <bool TWO, bool PER>
 __global__ __launch_bounds__(256) void cem_upscale_tiled_kernel(const float* __restrict__ f, const float* __restrict__ f2, int h, int w, int sf, int pre,
                                                               const float* __restrict__ taps, int k, const float* __restrict__ g, int crop, int mode,
-                                                              float range, float* __restrict__ out, float* __restrict__ out2, int wr, int wc) {
+                                                              float range, float* __restrict__ out, float* __restrict__ out2, int wr, int wc, int C) {
     extern __shared__ float sm[];             // taps [k*k] | window 1 [wr][wc] | window 2 [wr][wc]
     float* const st = sm;
     float* const w1 = sm + k * k;
     float* const w2 = w1 + wr * wc;
     const int Hh = h * sf, Wh = w * sf, Ho = Hh - 2 * crop, Wo = Wh - 2 * crop, p = k / 2;
     const long long bc = blockIdx.z;
+    if (PER) taps += (size_t)(blockIdx.z / (unsigned)C) * k * k;
     const int xo0 = blockIdx.x * UT_X, yo0 = blockIdx.y * UT_Y;
     // low-resolution window origin: the first sample any output of the tile can touch (floor division, may be negative)
     const int fy = yo0 + crop - p - pre, fx = xo0 + crop - p - pre;
@@ -1387,21 +1400,35 @@ static SepPlan down_shape(int sf, int k, int h, int w) {
     return p;
 }
 
-extern "C" int esr_cem_downscale(const float* y, int B, int C, int h, int w, int sf, int pre, const float* taps, int k, const float* lr,
-                                 int lr_pad, float* d, esr_stream_t stream) {
+// ---- the 2-D entry points and their *_per_image twins (taps [B][k][k]): one launcher each, `per` picks the kernels' PER instantiation
+static int downscale_2d_launch(bool per, const float* y, int B, int C, int h, int w, int sf, int pre, const float* taps, int k, const float* lr, int lr_pad,
+                               float* d, esr_stream_t stream) {
     if (int rc = cem_check_down(y && taps && d, B, C, h, w, sf, k, pre, lr, lr_pad)) return rc;
     const int rows = down_rows(sf, k), qpitch = pitch_sf_rows(sf, down_qcols(sf, k));
     const size_t lds = (size_t)sf * rows * qpitch * 4;
     const long long total = (long long)B * C * h * w;
     ESR_CLEAR_ERR();
-    if (lds <= 150 * 1024 && planes_fit_grid_z(B, C)) {
-        ESR_ALLOW_160K_LDS(cem_downscale_tiled_kernel);
-        hipLaunchKernelGGL(cem_downscale_tiled_kernel, tile_grid(h, w, DT, DT, B, C), dim3(256), lds, (hipStream_t)stream, y, h, w, sf, pre, taps, k, lr,
-                           lr_pad, d, qpitch, rows);
-    } else {
-        hipLaunchKernelGGL(cem_downscale_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, y, h, w, sf, pre, taps, k, lr, lr_pad, d, total);
-    }
+    pick<1, 0>(per, [&](auto PER) {
+        constexpr bool P = decltype(PER)::value != 0;
+        if (lds <= 150 * 1024 && planes_fit_grid_z(B, C)) {
+            ESR_ALLOW_160K_LDS(cem_downscale_tiled_kernel<P>);
+            hipLaunchKernelGGL(cem_downscale_tiled_kernel<P>, tile_grid(h, w, DT, DT, B, C), dim3(256), lds, (hipStream_t)stream, y, h, w, sf, pre, taps, k, lr,
+                               lr_pad, d, qpitch, rows, C);
+        } else {
+            hipLaunchKernelGGL(cem_downscale_kernel<P>, flat_grid(total), dim3(256), 0, (hipStream_t)stream, y, h, w, sf, pre, taps, k, lr, lr_pad, d, total, C);
+        }
+    });
     return cem_launched();
+}
+
+extern "C" int esr_cem_downscale(const float* y, int B, int C, int h, int w, int sf, int pre, const float* taps, int k, const float* lr,
+                                 int lr_pad, float* d, esr_stream_t stream) {
+    return downscale_2d_launch(false, y, B, C, h, w, sf, pre, taps, k, lr, lr_pad, d, stream);
+}
+
+extern "C" int esr_cem_downscale_per_image(const float* y, int B, int C, int h, int w, int sf, int pre, const float* taps, int k, const float* lr,
+                                           int lr_pad, float* d, esr_stream_t stream) {
+    return downscale_2d_launch(true, y, B, C, h, w, sf, pre, taps, k, lr, lr_pad, d, stream);
 }
 
 // ---- separable variants: taps[a][b] = tv[a] * th[b] (device arrays of k floats each).  Same arguments and results as the 2-D entry points up to
@@ -1451,19 +1478,31 @@ static SepPlan filt_shape(int k, int h, int w) {
     return p;
 }
 
-extern "C" int esr_cem_lrfilter(const float* x, int B, int C, int h, int w, const float* taps, int k, float* out, esr_stream_t stream) {
+static int lrfilter_2d_launch(bool per, const float* x, int B, int C, int h, int w, const float* taps, int k, float* out, esr_stream_t stream) {
     if (int rc = cem_check_filter(x && taps && out, B, C, h, w, k)) return rc;
     const int pitch = pitch_16_mod_32(LT_TX + k - 1);
     const size_t lds = (size_t)(LT_TY + k - 1) * pitch * 4;
     const long long total = (long long)B * C * h * w;
     ESR_CLEAR_ERR();
-    if (lds <= 150 * 1024 && planes_fit_grid_z(B, C)) {
-        ESR_ALLOW_160K_LDS(cem_lrfilter_tiled_kernel);
-        hipLaunchKernelGGL(cem_lrfilter_tiled_kernel, tile_grid(h, w, LT_TY, LT_TX, B, C), dim3(256), lds, (hipStream_t)stream, x, h, w, taps, k, out, pitch);
-    } else {
-        hipLaunchKernelGGL(cem_lrfilter_kernel, flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, h, w, taps, k, out, total);
-    }
+    pick<1, 0>(per, [&](auto PER) {
+        constexpr bool P = decltype(PER)::value != 0;
+        if (lds <= 150 * 1024 && planes_fit_grid_z(B, C)) {
+            ESR_ALLOW_160K_LDS(cem_lrfilter_tiled_kernel<P>);
+            hipLaunchKernelGGL(cem_lrfilter_tiled_kernel<P>, tile_grid(h, w, LT_TY, LT_TX, B, C), dim3(256), lds, (hipStream_t)stream, x, h, w, taps, k, out,
+                               pitch, C);
+        } else {
+            hipLaunchKernelGGL(cem_lrfilter_kernel<P>, flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, h, w, taps, k, out, total, C);
+        }
+    });
     return cem_launched();
+}
+
+extern "C" int esr_cem_lrfilter(const float* x, int B, int C, int h, int w, const float* taps, int k, float* out, esr_stream_t stream) {
+    return lrfilter_2d_launch(false, x, B, C, h, w, taps, k, out, stream);
+}
+
+extern "C" int esr_cem_lrfilter_per_image(const float* x, int B, int C, int h, int w, const float* taps, int k, float* out, esr_stream_t stream) {
+    return lrfilter_2d_launch(true, x, B, C, h, w, taps, k, out, stream);
 }
 
 extern "C" int esr_cem_lrfilter_sep(const float* x, int B, int C, int h, int w, const float* tv, const float* th, int k, float* out, esr_stream_t stream) {
@@ -1508,8 +1547,8 @@ static SepPlan up_shape(int sf, int k, int pre, int h, int w, int kf, int crop, 
     return p;
 }
 
-extern "C" int esr_cem_upscale(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* taps, int k,
-                               const float* g, int crop, int mode, float range, float* out, float* out2, esr_stream_t stream) {
+static int upscale_2d_launch(bool per, const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* taps, int k,
+                             const float* g, int crop, int mode, float range, float* out, float* out2, esr_stream_t stream) {
     if (int rc = cem_check_up(f && taps && out, B, C, h, w, sf, k, pre, crop, mode, g, f2, out2)) return rc;
     const int Ho = h * sf - 2 * crop, Wo = w * sf - 2 * crop;
     const int wr = up_window(UT_Y, sf, k), wc = up_window(UT_X, sf, k);
@@ -1517,15 +1556,27 @@ extern "C" int esr_cem_upscale(const float* f, const float* f2, int B, int C, in
     const long long total = (long long)B * C * Ho * Wo;
     ESR_CLEAR_ERR();
     pick<1, 0>(mode >= 2, [&](auto TWO) {
-        constexpr bool T = decltype(TWO)::value != 0;
-        if (lds <= 60 * 1024 && planes_fit_grid_z(B, C))
-            hipLaunchKernelGGL(cem_upscale_tiled_kernel<T>, tile_grid(Ho, Wo, UT_Y, UT_X, B, C), dim3(256), lds, (hipStream_t)stream, f, f2, h, w, sf, pre, taps,
-                               k, g, crop, mode, range, out, out2, wr, wc);
-        else
-            hipLaunchKernelGGL(cem_upscale_kernel<T>, flat_grid(total), dim3(256), 0, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode, range,
-                               out, out2, total);
+        pick<1, 0>(per, [&](auto PER) {
+            constexpr bool T = decltype(TWO)::value != 0, P = decltype(PER)::value != 0;
+            if (lds <= 60 * 1024 && planes_fit_grid_z(B, C))
+                hipLaunchKernelGGL((cem_upscale_tiled_kernel<T, P>), tile_grid(Ho, Wo, UT_Y, UT_X, B, C), dim3(256), lds, (hipStream_t)stream, f, f2, h, w, sf, pre,
+                                   taps, k, g, crop, mode, range, out, out2, wr, wc, C);
+            else
+                hipLaunchKernelGGL((cem_upscale_kernel<T, P>), flat_grid(total), dim3(256), 0, (hipStream_t)stream, f, f2, h, w, sf, pre, taps, k, g, crop, mode,
+                                   range, out, out2, total, C);
+        });
     });
     return cem_launched();
+}
+
+extern "C" int esr_cem_upscale(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* taps, int k,
+                               const float* g, int crop, int mode, float range, float* out, float* out2, esr_stream_t stream) {
+    return upscale_2d_launch(false, f, f2, B, C, h, w, sf, pre, taps, k, g, crop, mode, range, out, out2, stream);
+}
+
+extern "C" int esr_cem_upscale_per_image(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre, const float* taps, int k,
+                                         const float* g, int crop, int mode, float range, float* out, float* out2, esr_stream_t stream) {
+    return upscale_2d_launch(true, f, f2, B, C, h, w, sf, pre, taps, k, g, crop, mode, range, out, out2, stream);
 }
 
 // tvf / thf / kf: the LR filter folded in front of the upscale (esr_cem_filter_upscale_sep), or NULL / 0

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import EsrError, check
 from .act import require_gpu, stream_ptr
 
 
@@ -24,7 +24,8 @@ def _taps_entry(t, dev):
     7.3), its 1-D factors taps = outer(tv, th) for the separable kernels.  The taps are construction-time constants (a view of the frozen
     Filter_OP.weight): the entry is cached ON the tensor that owns the storage (the Parameter), keyed by its version counter and the target
     device, so steady-state calls do no host work and no host->device copy — and the cache dies with the module (a cache keyed by data
-    pointers would be handed stale taps when the allocator recycles a freed module's storage)."""
+    pointers would be handed stale taps when the allocator recycles a freed module's storage).
+    A 3-D array [B, k, k] is one tap set per image (the *_per_image entry points): the same cached device copy, never any factors."""
     owner = t._base if t._base is not None else t          # taps() hands out a view of the frozen Filter_OP.weight Parameter
     t = t.detach()
     key = (owner._version, tuple(t.shape), t.storage_offset(), tuple(t.stride()), str(dev))
@@ -37,15 +38,16 @@ def _taps_entry(t, dev):
             pass
     hit = cache.get(key)
     if hit is None:
-        assert t.dim() == 2 and t.shape[0] == t.shape[1] and t.shape[0] % 2 == 1, 'CEM filters are odd square 2-D arrays'
+        assert t.dim() in (2, 3) and t.shape[-2] == t.shape[-1] and t.shape[-1] % 2 == 1, 'CEM filters are odd square 2-D arrays (or [B] of them)'
         d = t.to(device=dev, dtype=torch.float32).contiguous().clone()
-        a = t.double().cpu().numpy()
-        u, sv, vt = np.linalg.svd(a)
         sep = None
-        if sv[0] > 0 and (len(sv) == 1 or sv[1] <= 1e-6 * sv[0]):
-            sgn = 1.0 if u[:, 0].sum() >= 0 else -1.0
-            tv, th = sgn * u[:, 0] * np.sqrt(sv[0]), sgn * vt[0] * np.sqrt(sv[0])
-            sep = (torch.tensor(tv, dtype=torch.float32, device=dev), torch.tensor(th, dtype=torch.float32, device=dev))
+        if t.dim() == 2:
+            a = t.double().cpu().numpy()
+            u, sv, vt = np.linalg.svd(a)
+            if sv[0] > 0 and (len(sv) == 1 or sv[1] <= 1e-6 * sv[0]):
+                sgn = 1.0 if u[:, 0].sum() >= 0 else -1.0
+                tv, th = sgn * u[:, 0] * np.sqrt(sv[0]), sgn * vt[0] * np.sqrt(sv[0])
+                sep = (torch.tensor(tv, dtype=torch.float32, device=dev), torch.tensor(th, dtype=torch.float32, device=dev))
         if len(cache) > 8:
             cache.clear()
         hit = cache[key] = (d, sep)
@@ -64,6 +66,20 @@ def _needs_grad(*ts):
     return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
 
 
+def _per_image(taps, B=None):
+    """taps [B, k, k]: one tap set per image of the batch."""
+    if taps.dim() != 3:
+        return False
+    if B is not None and taps.shape[0] != B:
+        raise ValueError('per-image kernels: %d tap sets for a batch of %d images' % (taps.shape[0], B))
+    return True
+
+
+def _forward_only(*taps):
+    if any(_per_image(t) for t in taps):
+        raise EsrError('per-image kernels: forward only (there is no per-image adjoint; run under torch.no_grad(), or one kernel per batch)')
+
+
 def downscale_raw(y, taps, sf, pre, lr=None, lr_pad=0):
     y = _prep(y, 'HR image')
     sep, taps = _sep(taps, y.device), _taps(taps, y.device)
@@ -79,8 +95,9 @@ def downscale_raw(y, taps, sf, pre, lr=None, lr_pad=0):
         rc = _lib.lib.esr_cem_downscale_sep(y.data_ptr(), B, Cc, h, w, sf, pre, sep[0].data_ptr(), sep[1].data_ptr(), taps.shape[0],
                                             lr.data_ptr() if lr is not None else None, lr_pad, out.data_ptr(), stream_ptr())
     if rc == _lib.ESR_E_UNSUPPORTED:
-        rc = _lib.lib.esr_cem_downscale(y.data_ptr(), B, Cc, h, w, sf, pre, taps.data_ptr(), taps.shape[0],
-                                        lr.data_ptr() if lr is not None else None, lr_pad, out.data_ptr(), stream_ptr())
+        entry = _lib.lib.esr_cem_downscale_per_image if _per_image(taps, B) else _lib.lib.esr_cem_downscale
+        rc = entry(y.data_ptr(), B, Cc, h, w, sf, pre, taps.data_ptr(), taps.shape[-1],
+                   lr.data_ptr() if lr is not None else None, lr_pad, out.data_ptr(), stream_ptr())
     check(rc, 'esr_cem_downscale')
     return out
 
@@ -94,7 +111,8 @@ def lr_filter_raw(x, taps):
     if sep is not None:
         rc = _lib.lib.esr_cem_lrfilter_sep(x.data_ptr(), B, Cc, h, w, sep[0].data_ptr(), sep[1].data_ptr(), taps.shape[0], out.data_ptr(), stream_ptr())
     if rc == _lib.ESR_E_UNSUPPORTED:
-        rc = _lib.lib.esr_cem_lrfilter(x.data_ptr(), B, Cc, h, w, taps.data_ptr(), taps.shape[0], out.data_ptr(), stream_ptr())
+        entry = _lib.lib.esr_cem_lrfilter_per_image if _per_image(taps, B) else _lib.lib.esr_cem_lrfilter
+        rc = entry(x.data_ptr(), B, Cc, h, w, taps.data_ptr(), taps.shape[-1], out.data_ptr(), stream_ptr())
     check(rc, 'esr_cem_lrfilter')
     return out
 
@@ -118,7 +136,8 @@ def upscale_raw(f, taps, sf, pre, f2=None, g=None, crop=0, mode=0, rng=0.0):
     if sep is not None:
         rc = _lib.lib.esr_cem_upscale_sep(*head, sep[0].data_ptr(), sep[1].data_ptr(), taps.shape[0], *tail)
     if rc == _lib.ESR_E_UNSUPPORTED:
-        rc = _lib.lib.esr_cem_upscale(*head, taps.data_ptr(), taps.shape[0], *tail)
+        entry = _lib.lib.esr_cem_upscale_per_image if _per_image(taps, B) else _lib.lib.esr_cem_upscale
+        rc = entry(*head, taps.data_ptr(), taps.shape[-1], *tail)
     check(rc, 'esr_cem_upscale')
     return (out, out2) if mode == 3 else out
 
@@ -135,12 +154,14 @@ FOLD_MAX_TILES = 512
 def filter_upscale_raw(e, taps_inv, taps_up, sf, pre, e2=None, g=None, crop=0, mode=0, rng=0.0):
     """upscale_raw(lr_filter_raw(e, taps_inv), taps_up, ..., f2=lr_filter_raw(e2, taps_inv)) — as ONE launch (esr_cem_filter_upscale_sep: every tile
     filters its own window of e on chip, bit-identical to the two launches) when both filters are separable and the windows fit, else as the two
-    (three) launches."""
+    (three) launches — per-image taps [B, k, k] always: they have no separable form."""
     e = _prep(e, 'LR image')
     sep_i, sep_u = _sep(taps_inv, e.device), _sep(taps_up, e.device)
     B, Cc, h, w = e.shape
     Ho, Wo = sf * h - 2 * crop, sf * w - 2 * crop
     fold = FUSE_FILTER_UPSCALE
+    if _per_image(taps_inv) or _per_image(taps_up):
+        fold = False
     if fold is None:
         # small launches only — and only where the separate filter launch is the TILE kernel, whose arithmetic the fold reproduces to the bit: images that
         # take the wave-streaming filter (esr_cem_sep_form) are never folded, so that a batch and any shard of it run the same arithmetic whatever their size
@@ -199,6 +220,7 @@ def adjoint_raw(dy, tabs, kind, sf, pre, in_shape, base=None, alpha=1.0):
 # ---- public, differentiable entry points -------------------------------------------------------------------------
 def downscale(y, taps, sf, pre):
     if _needs_grad(y):
+        _forward_only(taps)
         from . import autograd as AG
         return AG.CemLinear.apply(y, taps, 'downscale', sf, pre)
     return downscale_raw(y, taps, sf, pre)
@@ -206,6 +228,7 @@ def downscale(y, taps, sf, pre):
 
 def lr_filter(x, taps):
     if _needs_grad(x):
+        _forward_only(taps)
         from . import autograd as AG
         return AG.CemLinear.apply(x, taps, 'lr_filter', 1, 0)
     return lr_filter_raw(x, taps)
@@ -213,6 +236,7 @@ def lr_filter(x, taps):
 
 def upscale(x, taps, sf, pre):
     if _needs_grad(x):
+        _forward_only(taps)
         from . import autograd as AG
         return AG.CemLinear.apply(x, taps, 'upscale', sf, pre)
     return upscale_raw(x, taps, sf, pre)
@@ -220,8 +244,10 @@ def upscale(x, taps, sf, pre):
 
 def project(lr, g, taps_down, taps_inv, taps_up, sf, pre, lr_pad=0, crop=0, sigmoid_range=None, decomposed=False):
     """CEM_PyTorch.forward after the generator call (reference CEMnet.py:303-311).
-    lr: un-padded LR [B,C,h0,w0]; g: generator output on the (replicate-padded by lr_pad) LR frame."""
+    lr: un-padded LR [B,C,h0,w0]; g: generator output on the (replicate-padded by lr_pad) LR frame.
+    Any of the three tap arrays may be [B,k,k], one set per image (forward only)."""
     if _needs_grad(lr, g):
+        _forward_only(taps_down, taps_inv, taps_up)
         from . import autograd as AG
         return AG.cem_project_with_grad(lr, g, taps_down, taps_inv, taps_up, sf, pre, lr_pad, crop, sigmoid_range, decomposed)
     if sigmoid_range is None and not decomposed:

@@ -301,6 +301,33 @@ class SRRaGANModel(BaseModel):
             input_ref = data['ref'] if 'ref' in data else data['HR']
             self.var_ref = input_ref.to(self.device)
 
+    # ------------------------------------------------------------------ one CEM kernel per image of a batch
+    def set_kernels(self, kernels):
+        """Inference with a different CEM kernel for every image of the batches that follow: kernels[b] — an ndarray (an estimated kernel: built
+        with lower_magnitude_bound = 0.1, as test.kernel == 'estimated' is), None (the kernel this model was built with) or a kernel name, as
+        CEMnet(conf, upscale_kernel=...) takes them — is image b's.  None instead of the list goes back to the model's single kernel.  Only the
+        CEM's filters change (CEM_PyTorch.set_per_image_kernels): the generator, its weight packs and its engine are not touched, where
+        create_model(opt, kernel=k) per image rebuilds and repacks all of them.  feed_data() and test() are used as before; forward only."""
+        if self.is_train:
+            raise NotImplementedError('set_kernels: per-image kernels are for inference models (is_train = False)')
+        cem = self.netG.module if hasattr(self.netG, 'module') else self.netG
+        if not self.CEM_arch or not hasattr(cem, 'set_per_image_kernels'):
+            raise NotImplementedError('set_kernels: the model has no CEM (network_G.CEM_arch)')
+        if kernels is None:
+            cem.set_per_image_kernels(None)
+            return
+        base = self.CEM_net.conf
+
+        def conf_for(kernel):
+            conf = type('conf', (base,), {})
+            if isinstance(kernel, np.ndarray):
+                conf.lower_magnitude_bound = 0.1   # estimated kernels: keep the inversion of hTh stable
+            return conf
+        # None is this model's own CEMnet, as built: imresize's process-wide kernel cache may hold another model's kernel by now
+        kernels = list(kernels)
+        built = iter(CEMnet.CEMnet.build_per_image(conf_for, [k for k in kernels if k is not None]))
+        cem.set_per_image_kernels([self.CEM_net if k is None else next(built) for k in kernels])
+
     # ------------------------------------------------------------------ inference (reference :523-531)
     def test(self, prevent_grads_calc=True, **kwargs):
         self.netG.eval()

@@ -302,6 +302,19 @@ int esr_cem_upscale(const float* f, const float* f2, int B, int C, int h, int w,
                     const float* taps, int k, const float* g, int crop, int mode, float range,
                     float* out, float* out2, esr_stream_t stream);
 
+/* The three filters above with ONE TAP SET PER IMAGE: `taps` is a device fp32 [B][k][k] array, image b's C planes all use taps[b] (a batch whose
+ * images were blurred by different kernels — estimated ones are not rank one, hence the 2-D forms only).  Every other argument, the index conventions,
+ * the fused forms (lr / lr_pad; modes 0..3, crop, range, out2), the kernel forms (LDS-tiled where the window fits and B * C <= 65535, else one output
+ * per thread) and the error codes are those of esr_cem_downscale / esr_cem_lrfilter / esr_cem_upscale; with B equal tap sets the results are theirs
+ * bit for bit.  Forward only: there is no per-image adjoint. */
+int esr_cem_downscale_per_image(const float* y, int B, int C, int h, int w, int sf, int pre, const float* taps, int k,
+                                const float* lr, int lr_pad, float* d, esr_stream_t stream);
+int esr_cem_lrfilter_per_image(const float* x, int B, int C, int h, int w, const float* taps, int k, float* out,
+                               esr_stream_t stream);
+int esr_cem_upscale_per_image(const float* f, const float* f2, int B, int C, int h, int w, int sf, int pre,
+                              const float* taps, int k, const float* g, int crop, int mode, float range,
+                              float* out, float* out2, esr_stream_t stream);
+
 /* Separable variants of the three CEM filters for rank-one taps  taps[a][b] = tv[a] * th[b]  (the bicubic ds_kernel and its inv_hTh are
  * rank one; estimated / anisotropic kernels are not and use the 2-D entry points): a horizontal and a vertical 1-D pass on the tile a
  * workgroup holds on chip, 2k instead of k^2 MACs per output.  Arguments, index conventions, fused forms and results as esr_cem_downscale /

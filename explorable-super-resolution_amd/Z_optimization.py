@@ -2,60 +2,31 @@
 (Optimizable_Z :273-319, Z_optimizer.optimize :647-797): tanh-bounded Z parameter, Adam, per iteration
     Z = Z_range*tanh(P)  ->  model.feed_data({'LR', 'Z'})  ->  model.test(prevent_grads_calc=False)   (G + CEM forward WITH graph,
     weights frozen)  ->  clamp(0,1)  ->  objective  ->  loss.mean().backward()  (data-gradient kernels only)  ->  Adam step,
-keeping the iterate with the smallest loss.  The forward/backward are the HIP kernels; the objectives below are element-wise /
-reduction torch ops on the SR output.  Implemented objectives: 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1',
-'VGG' / 'max_VGG' (L1 between the VGG features of the output and of the desired image, the extractor on the library's kernels),
-'hist' (gray-level histogram), and the patch-histogram / dictionary objectives of the GUI's "Imitate histogram" and "Imitate patch histogram"
-tools: 'patchhist', 'patchhist_noDC', 'dict', 'dict_noDC', 'patchdict', 'patchdict_noDC' (SoftHistogramLoss on the pairwise KDE kernels),
-whole-image or restricted to a user-marked region (image_mask: where the objective looks; Z_mask: which latent entries may move — the
-GUI's region tools, GUI.py:1925-2057), and the GUI's local-variance, TV and periodicity tools (what its LOCAL_STD_4_OPT / RELATIVE_STD_OPT
-flags make it send, GUI.py:79-86, :1925-1937):
-  'local_max_STD' / 'local_min_STD'            -/+ mean_p S[p, b]
-  'local_STD_increase' / 'local_STD_decrease'  mean_p (S[p, b] - desired[p])^2, desired = initial x 1.05^(+-1) or initial +- data['STD_increment']
-  'local_STD_TV'                               mean_p 100 (S[p, b] - initial[p])^2 + TV_Loss(clamp(out) * mask)_b
-  '[local_STD_][nonInt_]periodicity[_1D]'      20 mean_{p,b'} (S - initial)^2 + sum_points mean M |GS+(out) - GS-(out)| (data['periodicity_points'];
-                                               'nonInt': bilinear grid_sample on the reference's coordinate lines, else integer crops)
-where S is the unbiased STD of every 7 x 7 window inside the opened image mask of the gray output (esr_hip.local.patch_std, csrc/esr_local.hip;
-whole-image Masked_STD for the periodicity names without 'local') and initial its value on the FIRST image of the model's output at
-construction.  A flat window's gradient is 0 here, NaN in the reference (torch.std's backward at 0).
-'scribble', what the GUI's Draw, brightness, local-TV brush and imprint tools send (GUI.py:1439-1440, :1993-1999; reference :401-448), with an
-image mask, data['desired'], data['scribble_mask'] (1 drawn colour, 2 / 3 brighten / darken by data['brightness_factor'], 4..50 local-TV
-regions): per image the L1 to the desired image (its brightened pixels from the initial output's HSV) on the labels 1-3 plus the 8-neighbour
-TV inside each region (esr_hip.scribble, csrc/esr_scribble.hip).  With non_local_Z_optimization on a partial image mask (the GUI's setting,
-GUI.py:63) the region constraint of :344-364, :385-390, :743-746 comes with it: the Z mask becomes min(1, E + dilate16(image_mask)) and
-1 x l1(out (1 - lm), initial (1 - lm)) holds the output outside the edited region.
-'random_l1', 'random_l1_limited', 'random_VGG', what the GUI's "produce random alternatives" tool sends (GUI.py:1833-1835; reference :365, :546-550,
-:683-701, :765-766): the samples of the batch are pushed apart from one another.  With D = clamp(out, 0, 1) ('l1') or netF(clamp(out, 0, 1)) ('VGG'):
-  near[b] = min(1, min_{a != b} |D[b] - D[a]|),   Z_loss[b] = -mean_{c,h,w} (near[b] - data['rmse_weight'] |D[b] - initial|) image_mask
-(the second term for '_limited', initial the model's output_image at construction, un-clamped; the mask when masks are given - the 'l1' names
-only), on esr_hip.pairmin / csrc/esr_pairmin.hip, which never builds the reference's [B, B, C, H, W] tensor; an exact tie between two neighbours
-goes to the lowest sample index.  '_limited' starts from randomly perturbed Z (reference :365) and replaces the first loss value by the second.
-'local_Mag_increase' / 'local_Mag_decrease' and '[local_STD_]nonInt_periodicityPlus[_1D]', what the GUI's variance and periodicity tools send
-with its special-behaviour button checked (GUI.py:1926-1937; reference :391-394, :450-455, :470-477, :717-726, :799-806), both with
-data['STD_increment']:
-  'local_Mag_*'            mean over the 49 x P entries of (patches(gray clamp(out_b)) - desired)^2: the half-overlap 7 x 7 patch set of the image
-                           mask (ReturnPatchExtractionMat, overlap 0.5) and, per patch, the initial output's patch (image 0) with its STD
-                           s = max(std, 1/255) moved to s +- increment about the patch mean (esr_hip.patchmag, csrc/esr_patchmag.hip)
-  '...periodicityPlus...'  the periodicity objective with its STD-preserving term replaced by 20 mean_{p,b'} (S - (initial + increment))^2
-(the 'nonInt' form only: the reference's integer periodicityPlus fails, its desired STD is never set).  Both take scribble's region constraint
-(non_local_Z_optimization on a partial image mask: the rebuilt Z mask and w x l1(out (1 - lm), initial (1 - lm)), esr_hip.scribble.region_constraint)
-with w = 255 / 10 x increment^2 ('Mag', :455) or 0.1 ('Plus', :390).  Accepted by exact name: every other 'Plus' / 'Mag' spelling is refused.
+keeping the iterate with the smallest loss.  The forward/backward are the HIP kernels; the objectives are element-wise / reduction torch ops
+and the library's objective kernels on the SR output.  Every accepted objective name is one entry of the table OBJECTIVES in Z_objectives.py; its family's
+class says what it computes, with the reference's lines, what it is fed and what it refuses (STD, Distance, Histogram, Periodicity,
+PatchMagnitude, Scribble, Random).  The name is read once, by resolve(), at construction.  All of them run
+whole-image or restricted to a user-marked region (image_mask: where the objective looks; Z_mask: which latent entries may move — the GUI's
+region tools, GUI.py:1925-2057), except 'l1' and the VGG names, which take no masks.
+The region constraint (non_local_Z_optimization on a partial image mask; 'scribble', the patch-magnitude and the periodicityPlus names): the
+rebuilt Z mask and w x l1(out (1 - lm), initial (1 - lm)) on esr_hip.scribble.region_constraint, w the family's.
 Not part of this build (NotImplementedError): 'random_VGG_limited' (the reference subtracts an image from a feature map), the random names with
 'local' (the GUI's LIMITED_RANDOM_WITH_STD_NOT_L1, off as shipped), the random objectives in training mode (HR_unpadder) and 'random_VGG' with
 masks; the GUI's adversarial objectives, 'scribble' without an image mask (the reference's plain-L1
-fallback, which the GUI never sends: use 'l1'), the 'Plus' / 'Mag' spellings other than the six names above, the other 'local_*' names
-without STD (the overlap-0.5 patch selection with its non-covered pixels), the local / periodicity / scribble / patch-magnitude objectives in
-training mode (HR_unpadder), the region constraint (non_local_Z_optimization on a partial image mask) for any objective but 'scribble' and the
-six names above (the other local and periodicity ones refuse it, the whole-image ones ignore it), the '*_localSTD' histogram variants and the
-automatic histogram temperature.
+fallback, which the GUI never sends: use 'l1'), the 'Plus' / 'Mag' spellings other than the six names of PLUS_OBJECTIVES and MAG_OBJECTIVES,
+the other 'local_*' names without STD (the overlap-0.5 patch selection with its non-covered pixels), the local / periodicity / scribble /
+patch-magnitude objectives in training mode (HR_unpadder), the region constraint (non_local_Z_optimization on a partial image mask) for any
+objective but 'scribble' and those six names (the other local and periodicity ones refuse it, the whole-image ones ignore it), the '*_localSTD'
+histogram variants and the automatic histogram temperature.  The refusals by name are the ordered list REFUSALS.
 JPEG mode (jpeg_extractor given; models/DecompCNN_model.py): the model's fake_H holds DCT coefficients and its image is output_image (0...255),
 Z lives on the block grid (Z_size = [H/8, W/8]) and data carries 'Uncomp' or 'Comp' and 'QF' (or a JPEG file's 'Q_table', and for the colour
-model its 'compressed_chroma': esr_hip.jpeg_file.JpegFile.model_data) in place of 'LR'.  Accepted on either model: 'l1',
+model its 'compressed_chroma': esr_hip.jpeg_file.JpegFile.model_data) in place of 'LR'.  Accepted on either model (JPEG_OBJECTIVES): 'l1',
 'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease'.  On a colour model (chroma_mode) Z_size is still the Y grid, the objectives see the RGB
 output, Z's gradient runs through both generators, and a model fed with the Y coefficients as 'Comp' gets data['uncompressed_chroma']
-([B, 2, H, W] Cb, Cr) passed to model.test.  The colour model (the one the reference's JPEG GUI builds) also takes the editing objectives: the
-local-STD, periodicity, periodicityPlus and patch-magnitude names, 'scribble', 'hist' and the patch-histogram / dictionary names, 'random_l1' and
-'random_l1_limited'.  The reference evaluates all of them on model.Output_Batch(within_0_1=True) whatever the model (:617, :680); so here: an
+([B, 2, H, W] Cb, Cr) passed to model.test.  The colour model (the one the reference's JPEG GUI builds) also takes the editing objectives
+(JPEG_EDIT_OBJECTIVES): the local-STD, periodicity, periodicityPlus and patch-magnitude names, 'scribble', 'hist' and the patch-histogram /
+dictionary names, 'random_l1' and 'random_l1_limited'.  The reference evaluates all of them on model.Output_Batch(within_0_1=True) whatever
+the model (:617, :680); so here: an
 objective's value in JPEG mode is, by definition, its SR-mode value on model.Output_Image_0_1() (the un-clamped RGB image in 0...1, csrc/
 esr_jpeg_edit.hip's esr_ycbcr_rgb on the GPU) in place of fake_H, the clamp inside the kernels as there.  The region constraint takes its
 block-grid form (:355-357): Z mask = min(1, E + D), E = 1 inside a margin of 24 // 8 blocks, D the 8 x 8 block maximum of dilate16(image_mask).
@@ -79,9 +50,10 @@ import torch
 from esr_hip import _image as esr_image
 from esr_hip import dist as esr_dist
 from esr_hip import local as esr_local
-from esr_hip import pairmin as esr_pairmin
-from esr_hip import patchmag as esr_patchmag
 from esr_hip import scribble as esr_scribble
+# the objectives: the table, the name lists derived from it (callers import them from here) and the one resolution step
+from Z_objectives import (HIST_OBJECTIVES, JPEG_EDIT_OBJECTIVES, JPEG_OBJECTIVES, LOCAL_STD_OBJECTIVES, MAG_OBJECTIVES, OBJECTIVES,  # noqa: F401
+                          PERIODICITY_OBJECTIVES, PLUS_OBJECTIVES, RANDOM_OBJECTIVES, SUPPORTED, UNSUPPORTED, hist_objective_config, refuse, resolve)
 
 
 def ArcTanH(input_tensor):
@@ -282,43 +254,10 @@ class Optimizable_Z(torch.nn.Module):
         self.Z.data = 1 * Z
 
 
-# the patch-histogram and dictionary objectives (reference :510-543; what the GUI's histogram tools send, GUI.py:1460-1461, :1931-1935)
-HIST_OBJECTIVES = ('patchhist', 'patchhist_noDC', 'dict', 'dict_noDC', 'patchdict', 'patchdict_noDC')
-
-
-def hist_objective_config(objective):
-    """SoftHistogramLoss settings of a histogram / dictionary objective (reference :536-543): 256 bins on [0, 1], patch size 6 when 'patch'
-    is in the name (else 1), temperature 5e-4 for histograms and 1e-3 for dictionaries, the patch DC removed for '_noDC'."""
-    if 'no_localSTD' in objective or 'localSTD' in objective:
-        raise NotImplementedError("Z objective '%s': the local-STD histogram variants (no_patch_STD and the STD-preserving term) are not part of "
-                                  "this build" % objective)
-    if objective not in HIST_OBJECTIVES + ('hist',):
-        raise ValueError("'%s' is not a histogram / dictionary objective" % objective)
-    return dict(bins=256, min=0, max=1, patch_size=6 if 'patch' in objective else 1, temperature=5e-4 if 'hist' in objective else 1e-3,
-                dictionary_not_histogram='dict' in objective, no_patch_DC='noDC' in objective)
-
-
-# the local-STD and periodicity objectives (reference :391-398, :459-509, :616-627, :712-733, :799-815; what the GUI's variance, TV and
-# periodicity tools send, GUI.py:1457-1459, :1481-1482, :1925-1937)
-LOCAL_STD_OBJECTIVES = ('local_max_STD', 'local_min_STD', 'local_STD_increase', 'local_STD_decrease', 'local_STD_TV')
-PERIODICITY_OBJECTIVES = tuple(pre + mid + 'periodicity' + post for pre in ('local_STD_', '') for mid in ('nonInt_', '') for post in ('', '_1D'))
-# the random-alternatives objectives (reference :365, :546-550, :683-701, :765-766; the GUI's "produce random alternatives", GUI.py:1833-1835)
-RANDOM_OBJECTIVES = ('random_l1', 'random_l1_limited', 'random_VGG')
-# what the variance and periodicity tools send with the GUI's special-behaviour button checked (GUI.py:1926-1937): the patch-magnitude
-# objectives (reference :391-394, :450-455, :717-722) and periodicityPlus (:470-477, :723-726, :799-806).  Accepted by exact name only.
-MAG_OBJECTIVES = ('local_Mag_increase', 'local_Mag_decrease')
-PLUS_OBJECTIVES = tuple(pre + 'nonInt_periodicityPlus' + post for pre in ('local_STD_', '') for post in ('', '_1D'))
-# accepted with jpeg_extractor (JPEG mode) on either model, and the editing objectives the colour model (chroma_mode) also takes there
-JPEG_OBJECTIVES = ('l1', 'TV', 'max_STD', 'min_STD', 'STD_increase', 'STD_decrease')
-JPEG_EDIT_OBJECTIVES = LOCAL_STD_OBJECTIVES + PERIODICITY_OBJECTIVES + PLUS_OBJECTIVES + MAG_OBJECTIVES + ('scribble', 'hist') + HIST_OBJECTIVES + \
-    ('random_l1', 'random_l1_limited')
-
-
 class Z_optimizer():
     MIN_LR = 1e-5
     PATCH_SIZE_4_STD = esr_image.PATCH
-    SUPPORTED = ['max_STD', 'min_STD', 'STD_increase', 'STD_decrease', 'TV', 'l1', 'hist', 'VGG', 'max_VGG'] + list(HIST_OBJECTIVES) + \
-        list(LOCAL_STD_OBJECTIVES) + list(PERIODICITY_OBJECTIVES) + ['scribble'] + list(RANDOM_OBJECTIVES) + list(MAG_OBJECTIVES) + list(PLUS_OBJECTIVES)
+    SUPPORTED = SUPPORTED
 
     def __init__(self, objective, Z_size, model, Z_range, max_iters, data=None, loggers=None, image_mask=None, Z_mask=None, initial_Z=None,
                  initial_LR=None, existing_optimizer=None, batch_size=1, HR_unpadder=None, random_Z_inits=False, auto_set_hist_temperature=False,
@@ -326,82 +265,48 @@ class Z_optimizer():
         # JPEG mode (the explorable JPEG decoder, models/DecompCNN_model.py): the model's fake_H holds DCT coefficients [B, 64, h, w] and its image
         # is output_image (0...255); Z lives on the block grid, Z_size = [H/8, W/8]; data carries 'Uncomp' or 'Comp' and 'QF' instead of 'LR'
         self.jpeg_mode = jpeg_extractor is not None
+        self.model_training = HR_unpadder is not None
         colour = bool(getattr(model, 'chroma_mode', False))
-        if self.jpeg_mode and (HR_unpadder is not None or (objective not in JPEG_OBJECTIVES and not (colour and objective in JPEG_EDIT_OBJECTIVES))):
-            raise NotImplementedError("Z objective '%s'%s in JPEG mode (jpeg_extractor given) on the %s model is not part of this build: implemented "
-                                      "there are %s%s" % (objective, '' if HR_unpadder is None else ' with HR_unpadder (training)',
-                                                          'colour' if colour else 'Y-channel', list(JPEG_OBJECTIVES),
-                                                          ' and the editing objectives %s' % (list(JPEG_EDIT_OBJECTIVES),) if colour else
-                                                          ' (the editing objectives belong to the colour model, chroma_mode=True)'))
-        if 'localSTD' in objective:
-            hist_objective_config(objective)            # raises, naming the variant
-        if objective == 'scribble' and image_mask is None:
-            raise NotImplementedError("Z objective 'scribble' without an image mask (the reference's plain unmasked L1 fallback, :404-405, which the "
-                                      "GUI never sends) is not part of this build: use 'l1'")
-        if objective == 'scribble' and HR_unpadder is not None:
-            raise NotImplementedError("Z objective 'scribble' in training mode (HR_unpadder): the reference has no initial output there (:346)")
-        if objective.startswith('random_'):
-            if 'local' in objective:
-                raise NotImplementedError("Z objective '%s': the random objectives with 'local' (the GUI's LIMITED_RANDOM_WITH_STD_NOT_L1, off as "
-                                          "shipped; their overlap-0.5 patch selection) are not part of this build" % objective)
-            if 'VGG' in objective and 'limited' in objective:
-                raise NotImplementedError("Z objective '%s': the reference subtracts the initial image from a feature map there (:697); not part of "
-                                          "this build" % objective)
-            if objective in RANDOM_OBJECTIVES and HR_unpadder is not None:
-                raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder) is not part of this build" % objective)
-        new_objective = objective in LOCAL_STD_OBJECTIVES or objective in PERIODICITY_OBJECTIVES
-        special = objective in MAG_OBJECTIVES or objective in PLUS_OBJECTIVES
-        if objective in tuple(name.replace('nonInt_', '') for name in PLUS_OBJECTIVES):
-            raise NotImplementedError("Z objective '%s': the integer periodicityPlus form fails in the reference (its desired STD is set for the 'nonInt' "
-                                      "names only, :473-477); use '%s'" % (objective, objective.replace('periodicityPlus', 'nonInt_periodicityPlus')))
-        for variant in ('Plus', 'Mag'):
-            if variant in objective and not special:
-                raise NotImplementedError("Z objective '%s': the '%s' variant (the GUI's special-behaviour button) is not part of this build" % (objective, variant))
-        if 'local' in objective and 'STD' not in objective and not special:
-            raise NotImplementedError("Z objective '%s': 'local' objectives without STD (their overlap-0.5 greedy patch selection and non-covered pixel "
-                                      "set) are not part of this build" % objective)
-        if (new_objective or special) and HR_unpadder is not None:
-            raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder): the reference has no initial STD there" % objective)
-        if special and (data is None or data.get('STD_increment') is None):
-            raise ValueError("Z objective '%s' needs data['STD_increment']" % objective)
-        if new_objective and unsupported.get('non_local_Z_optimization') and image_mask is not None and np.mean(image_mask) < 1:
+        self.family = family = resolve(objective, ('colour' if colour else 'Y-channel') if self.jpeg_mode else None, self.model_training)
+        # the GUI's non_local_Z_optimization on a partial image mask asks for the region constraint (reference :347, :352-364)
+        constrained = bool(unsupported.get('non_local_Z_optimization')) and image_mask is not None and np.mean(image_mask) < 1
+        if image_mask is None and hasattr(family, 'no_mask'):           # (scribble)
+            raise NotImplementedError("Z objective '%s'%s" % (objective, family.no_mask))
+        if self.model_training and not family.training:
+            raise NotImplementedError("Z objective '%s' in training mode (HR_unpadder)%s" %
+                                      (objective, getattr(family, 'training_refusal', ': the reference has no initial STD there')))
+        for key in family.needs_first:
+            if data is None or data.get(key) is None:
+                raise ValueError("Z objective '%s' needs data['%s']" % (objective, key))
+        if constrained and family.constraint == 'refuses':
             raise NotImplementedError("Z objective '%s' with non_local_Z_optimization on a partial image mask (the GUI's region-constraint mode: Z-mask "
                                       "rebuild and constraining L1) is not part of this build" % objective)
-        if objective in HIST_OBJECTIVES and auto_set_hist_temperature:
+        if auto_set_hist_temperature and family.fixed_temperature:
             raise NotImplementedError("Z objective '%s': auto_set_hist_temperature (the temperature search differentiates through the generator "
                                       "twice) is not part of this build" % objective)
-        if objective not in self.SUPPORTED or ((image_mask is not None or Z_mask is not None) and ('l1' in objective or 'VGG' in objective) and
-                                               objective not in ('random_l1', 'random_l1_limited')):
-            raise NotImplementedError("Z objective '%s': implemented are %s (optionally with image_mask / Z_mask, except 'l1' and the VGG ones); the GUI's other "
-                                      "editing objectives are not part of this build" % (objective, self.SUPPORTED))
+        if (image_mask is not None or Z_mask is not None) and not family.takes_masks:
+            refuse(UNSUPPORTED, objective)
         assert (image_mask is None) == (Z_mask is None), 'Should either supply both masks or niether'        # (reference :384)
-        if objective == 'scribble':
-            for key in ('desired', 'scribble_mask'):
-                if data is None or data.get(key) is None:
-                    raise ValueError("Z objective 'scribble' needs data['%s']" % key)
-            if np.isin(np.asarray(data['scribble_mask']), (2, 3)).any() and data.get('brightness_factor') is None:
-                raise ValueError("Z objective 'scribble' needs data['brightness_factor'] for its brightness labels 2 / 3")
-        self.random = objective in RANDOM_OBJECTIVES
-        if self.random and 'limited' in objective:
-            if data is None or data.get('rmse_weight') is None:
-                raise ValueError("Z objective '%s' needs data['rmse_weight']" % objective)
-            if getattr(model, 'output_image', None) is None:
-                raise ValueError("Z objective '%s' needs the model's current output_image (the image the alternatives stay close to)" % objective)
-        # the region constraint (reference :347, :352-364): the GUI's non_local_Z_optimization on a partial image mask
-        # ('scribble' and the special-behaviour names; every other objective ignores or refuses the flag, see above)
-        self.non_local_Z_optimization = (objective == 'scribble' or special) and bool(unsupported.get('non_local_Z_optimization')) and \
-            image_mask is not None and np.mean(image_mask) < 1
+        for key in family.needs:
+            if data is None or data.get(key) is None:
+                raise ValueError("Z objective '%s' needs data['%s']" % (objective, key))
+        if family.brightness_labels and np.isin(np.asarray(data['scribble_mask']), family.brightness_labels).any() and data.get('brightness_factor') is None:
+            raise ValueError("Z objective '%s' needs data['brightness_factor'] for its brightness labels %s" %
+                             (objective, ' / '.join(map(str, family.brightness_labels))))
+        if family.limited and getattr(model, 'output_image', None) is None:
+            raise ValueError("Z objective '%s' needs the model's current output_image (the image the alternatives stay close to)" % objective)
+        self.random, self.local_STD, self.STD_PRESERVING_WEIGHT = family.random, family.local, family.STD_PRESERVING_WEIGHT
+        self.non_local_Z_optimization = constrained and family.constraint == 'takes'
         if self.non_local_Z_optimization:
             Z_mask = esr_scribble.rebuilt_z_mask(image_mask, block_size=8 if self.jpeg_mode else 1)
         self.Z_mask = Z_mask
         self.objective, self.model, self.data, self.loggers = objective, model, data, loggers
         self.device = model.device
-        initial_pre_tanh_Z = None
-        if initial_Z is not None:
-            initial_pre_tanh_Z = initial_Z / Z_range
-            eps = torch.finfo(initial_pre_tanh_Z.dtype).eps
-            initial_pre_tanh_Z = ArcTanH(torch.clamp(initial_pre_tanh_Z, min=-1 + eps, max=1. - eps))
-        self.model_training = HR_unpadder is not None
+        def pre_tanh(Z):
+            Z = Z / Z_range
+            eps = torch.finfo(Z.dtype).eps
+            return ArcTanH(torch.clamp(Z, min=-1 + eps, max=1. - eps))
+        initial_pre_tanh_Z = None if initial_Z is None else pre_tanh(initial_Z)
         # this rank's shard of the Z batch (all of it when not distributed)
         self.global_batch = batch_size
         self.shard = esr_dist.shard_range(batch_size)
@@ -409,68 +314,26 @@ class Z_optimizer():
         if initial_pre_tanh_Z is not None and initial_pre_tanh_Z.size(0) == batch_size and batch_size > 1:
             initial_pre_tanh_Z = initial_pre_tanh_Z[self.shard[0]:self.shard[1]]
         if Z_mask is not None and initial_pre_tanh_Z is None:       # a masked search keeps the unmasked entries at the model's current latent
-            z_now = model.GetLatent() / Z_range
-            eps = torch.finfo(z_now.dtype).eps
-            initial_pre_tanh_Z = ArcTanH(torch.clamp(z_now, min=-1 + eps, max=1. - eps))
+            initial_pre_tanh_Z = pre_tanh(model.GetLatent())
         self.Z_model = Optimizable_Z(Z_shape=[local_bs, model.num_latent_channels] + list(Z_size), Z_range=Z_range,
                                      initial_pre_tanh_Z=initial_pre_tanh_Z, Z_mask=Z_mask, device=self.device,
-                                     random_perturbations=bool((random_Z_inits and 'random' not in objective) or
-                                                               ('random' in objective and 'limited' in objective)))      # (reference :365)
+                                     random_perturbations=bool(family.limited or (random_Z_inits and not family.random)))      # (reference :365)
         assert (initial_LR is not None) or (existing_optimizer is not None), 'Should either supply optimizer from previous iterations or initial LR for new optimizer'
         self.image_mask = None if image_mask is None else torch.from_numpy(np.asarray(image_mask, dtype=np.float32)).to(self.device)
-        self.local_STD = objective.startswith('local_') and objective not in MAG_OBJECTIVES
-        periodic = objective in PERIODICITY_OBJECTIVES or objective in PLUS_OBJECTIVES
-        if self.local_STD or periodic:
-            H, W = self._image().shape[2:] if image_mask is None else np.asarray(image_mask).shape
         if self.local_STD:
             # every 7 x 7 window inside the opened image mask (ReturnPatchExtractionMat with overlap 1, :391-398); no mask: the whole output
+            H, W = self._image().shape[2:] if image_mask is None else np.asarray(image_mask).shape
             self.patches = esr_local.PatchSet(image_mask, H, W)
-        if periodic:
-            self.periodicity_pairs = [esr_local.ShiftPair(p, H, W, interpolated='nonInt' in objective) for p in data['periodicity_points']]
         if not self.model_training and self._model_has_output():
             self.initial_output = model.Output_Batch(within_0_1=True).detach()
             # every sample's own initial STD (the reference's first_image_only flag is honoured by its 'local' objectives only,
             # Z_optimization.py:617-627): per-sample reference points, so sharding the batch over ranks needs no exchange
             self.initial_STD = self.Masked_STD(first_image_only=True).detach()
-        if 'STD' in objective and any(p in objective for p in ['increase', 'decrease']):
-            STD_CHANGE_FACTOR = 1.05
-            self.desired_STD = 1 * self.initial_STD
-            inc = data.get('STD_increment') if data is not None else None
-            if inc is None:
-                self.desired_STD = self.desired_STD * (STD_CHANGE_FACTOR if 'increase' in objective else 1 / STD_CHANGE_FACTOR)
-            else:
-                self.desired_STD = self.desired_STD + (inc if 'increase' in objective else -inc)
-        if special:
-            self._set_special(image_mask, data)
-        if 'l1' in objective and not self.random and data is not None and 'desired' in data:
-            self.desired_im = data['desired'].to(self.device)
-        if self.random and 'limited' in objective:           # reference :546-548
-            # (JPEG mode: the RGB 0...1 image the objective compares with; the reference keeps the YCbCr 0...255 output_image there)
-            self.initial_image = self._image().detach().clone() if self.jpeg_mode else 1 * model.output_image.detach()
-            self._check_initial_batch(self.initial_image, 'output_image')
-            self.rmse_weight = float(data['rmse_weight'])
-        if objective == 'scribble':
-            self._set_scribble(image_mask, data)
-        if 'VGG' in objective and not self.random:           # reference :505-507: L1 between the VGG features of the output and of the desired image
-            self.loss = torch.nn.L1Loss().to(self.device)
-            if data is not None and 'desired' in data:
-                self._set_desired_VGG(data['desired'])
-        if objective == 'hist':          # reference :536-541: 256 bins on [0, 1], temperature 5e-4
-            self.loss = SoftHistogramLoss(bins=256, min=0, max=1, desired_hist_image=[d.to(self.device) for d in data['desired']] if data is not None else None,
-                                          desired_hist_image_mask=data.get('Desired_Im_Mask') if data is not None else None, input_im_HR_mask=self.image_mask,
-                                          gray_scale=True, patch_size=1, temperature=5e-4)
-        if objective in HIST_OBJECTIVES:
-            # image_mask None: the patches cover the whole output (the reference's all-ones mask, :372-374); Desired_Im_Mask None: the whole
-            # desired image(s).  With the default temperatures and the missing-mass bin, as :536-543.
-            self.loss = SoftHistogramLoss(desired_hist_image=self._desired_list(data), desired_hist_image_mask=data.get('Desired_Im_Mask') if data else None,
-                                          input_im_HR_mask=self.image_mask, gray_scale=True, **hist_objective_config(objective))
+        family.setup(self, data, image_mask)
         self.optimizer = torch.optim.Adam(self.Z_model.parameters(), lr=initial_LR) if existing_optimizer is None else existing_optimizer
-        self.LR = initial_LR
-        self.cur_iter = 0
-        self.max_iters = max_iters
+        self.LR, self.cur_iter, self.max_iters = initial_LR, 0, max_iters
         self.random_Z_inits = 'all' if (random_Z_inits or self.model_training) else False
         self.HR_unpadder = HR_unpadder
-        self.STD_PRESERVING_WEIGHT = 100 if 'TV' in objective else 20      # reference Z_optimization.py:508-509 (TV), :471 (others)
 
     _iter_image = None
 
@@ -508,64 +371,20 @@ class Z_optimizer():
             raise ValueError("Z objective '%s': the model's %s has batch %d, the Z search %d on this rank (1 broadcasts)" %
                              (self.objective, what, initial.size(0), local_bs))
 
-    def _set_scribble(self, image_mask, data):
-        """labels, desired image and constraint of the scribble objective (reference :401-448, :385-390), built once"""
+    def _require_output(self, why):
         if not self._model_has_output():
-            raise ValueError("Z objective 'scribble' needs the model's current output (its brightened pixels and the region constraint start from it)")
-        initial = self.initial_output
-        self._check_initial_batch(initial)
-        # every rank must edit towards the same image: rank 0's brightened pixels (one broadcast, here only)
-        desired = esr_scribble.desired_image(data['desired'], data['scribble_mask'], initial[0], data.get('brightness_factor'))
-        desired = esr_dist.broadcast_tensor(torch.from_numpy(desired).to(self.device))
-        self.desired_im = desired
-        self.scribble = esr_scribble.ScribbleSpec(data['scribble_mask'], image_mask, desired, constraint=self.non_local_Z_optimization,
-                                                  initial=initial if self.non_local_Z_optimization else None)
-        self.constraining_loss_weight = 1                                   # (reference :447)
+            raise ValueError("Z objective '%s' needs the model's current output (%s from it)" % (self.objective, why))
 
-    def _set_special(self, image_mask, data):
-        """what the patch-magnitude and periodicityPlus objectives build once: the desired patches (reference :450-455) or the desired STD
-        (:476-477), and with the region constraint its reference output and weight (:385-390, :455)"""
-        if not self._model_has_output():
-            raise ValueError("Z objective '%s' needs the model's current output (its desired %s from it)" %
-                             (self.objective, 'patches start' if self.objective in MAG_OBJECTIVES else 'STD starts'))
-        inc = float(data['STD_increment'])
-        initial = self.initial_output
-        if self.objective in MAG_OBJECTIVES:
-            # image 0 of the model's output, as the sibling objectives take their initial STD (the reference's view([-1, 1]) accepts batch 1 only)
-            H, W = initial.shape[2:]
-            self.mag = esr_patchmag.MagSpec(image_mask, H, W, initial[0], inc, 1 if 'increase' in self.objective else -1)
-            # every rank must aim at the same patches: rank 0's (one broadcast, here only)
-            if esr_dist.is_distributed():
-                self.mag.replace_desired(esr_dist.broadcast_tensor(self.mag.desired.to(self.device)))
-            self.constraining_loss_weight = 255 / 10 * inc ** 2                 # (reference :455)
-        else:
-            self.desired_STD = self.initial_STD + inc                           # PLUS_MEANS_STD_INCREASE (reference :472, :476-477)
-            self.constraining_loss_weight = 0.1                                 # the default (reference :390)
+    def _set_region_constraint(self, image_mask):
+        """with the region constraint on, its reference output (reference :385-390); the family sets constraining_loss_weight"""
         if self.non_local_Z_optimization:
-            self._check_initial_batch(initial)
-            self.constraint_spec = esr_scribble.constraint_spec(image_mask, initial)
-
-    def _set_desired_VGG(self, desired):
-        self.desired_im = desired.to(self.device)
-        with torch.no_grad():
-            self.GT_HR_VGG = self.model.netF(self.desired_im).detach()
-
-    def _desired_list(self, data):
-        if data is None or data.get('desired') is None:
-            return None
-        d = data['desired']
-        return [im.to(self.device) for im in (d if isinstance(d, (list, tuple)) else [d])]
+            self._check_initial_batch(self.initial_output)
+            self.constraint_spec = esr_scribble.constraint_spec(image_mask, self.initial_output)
 
     def feed_data(self, data):
         self.data = data
         self.cur_iter = 0
-        if self.objective in HIST_OBJECTIVES and data.get('desired') is not None:
-            # a new desired image rebuilds the bins and the desired histogram (the reference's Feed_Desired_Hist_Im is broken for the KDE forms)
-            self.loss.Feed_Desired_Hist_Im(self._desired_list(data), data.get('Desired_Im_Mask'))
-        if 'l1' in self.objective and not self.random:
-            self.desired_im = data['desired'].to(self.device)
-        if 'VGG' in self.objective and not self.random:
-            self._set_desired_VGG(data['desired'])
+        self.family.feed(self, data)
 
     def _generator_parameters(self):
         """netG's and, on a colour JPEG model, the Y generator's that Z's gradient also runs through"""
@@ -621,7 +440,7 @@ class Z_optimizer():
             self.model.feed_data(data, need_GT=False, **({'detach_Y': False} if self.jpeg_mode else {}))
             # drop the previous iteration's output first: its graph holds the generator's saved-activation buffers, and a forward that finds
             # them busy allocates a second full set (2 x 90 GB at the configs[3] shape)
-            self.output_image = self._iter_image = Z_loss = loss = None
+            self.output_image = self._iter_image = self._global_loss = self._constraint = Z_loss = loss = None
             self.model.fake_H = self.model.output_image = None
             if self.jpeg_mode and data.get('uncompressed_chroma') is not None:      # colour model fed with Y coefficients (reference :679)
                 self.model.test(prevent_grads_calc=False, uncompressed_chroma=data['uncompressed_chroma'])
@@ -636,62 +455,19 @@ class Z_optimizer():
                 self.output_image = self.model.Output_Batch(within_0_1=True)
             if self.model_training:
                 self.output_image = self.HR_unpadder(self.output_image)
-            if self.random:
-                # the one objective that couples the samples: every rank sees the detached D of all ranks (one all-gather, the only data-path
-                # collective of the Z search) and gets its share of the global mean, differentiable with respect to its own rows
-                limited = 'limited' in self.objective
-                if 'VGG' in self.objective:
-                    D, clamp01 = self.model.netF(self.output_image), False
-                else:
-                    D, clamp01 = self._image(), True             # clamped inside the term, as Output_Batch(within_0_1=True)
-                D_all = None
-                if esr_dist.is_distributed():
-                    D_all = esr_dist.all_gather_tensor(D, [b - a for a, b in (esr_dist.shard_range(self.global_batch, r) for r in range(esr_dist.world_size()))])
-                Z_loss, loss = esr_pairmin.random_share(D, D_all, self.shard[0], clamp01=clamp01, mask=self.image_mask,
-                                                        init=self.initial_image if limited else None, w=self.rmse_weight if limited else 0.0)
-            elif self.objective == 'hist' or self.objective in HIST_OBJECTIVES:
-                # a dictionary gives one value per image; a histogram's KL is one mean over the local [B, bins + 1] (scaled below)
-                Z_loss = self.loss(self.output_image)
-                Z_loss = Z_loss.reshape(-1) if self.loss.dictionary_not_histogram else Z_loss.reshape(1)
-            elif 'l1' in self.objective:
-                Z_loss = (self.output_image - self.desired_im).abs().mean(dim=(1, 2, 3))
-            elif self.objective == 'scribble':
-                # per-image L1 + local TV, and the region constraint's share of l1 over the GLOBAL batch (0 when it is off)
-                image = self._image()
-                Z_loss, constraint = esr_scribble.scribble_loss(image, self.scribble, constraint_norm=self.global_batch * image[0].numel())
-            elif 'VGG' in self.objective:
-                Z_loss = self.loss(self.model.netF(self.output_image), self.GT_HR_VGG).reshape(1)
-            elif self.objective in MAG_OBJECTIVES:
-                Z_loss = esr_patchmag.patch_mag(self._image(), self.mag)
-            elif self.objective in PLUS_OBJECTIVES:
-                # the STD-preserving term gives way to one that raises the STD by the increment, a scalar over the (local) batch (reference :723-726)
-                Z_loss = esr_local.shift_l1(self._image(), self.image_mask, self.periodicity_pairs) + \
-                    (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.desired_STD) ** 2).mean()
-            elif 'periodicity' in self.objective:
-                # one STD-preserving scalar over the whole (local) batch and all patches, added to every sample (reference :799-815)
-                Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean() + \
-                    esr_local.shift_l1(self._image(), self.image_mask, self.periodicity_pairs)
-            elif 'TV' in self.objective:
-                Z_loss = (self.STD_PRESERVING_WEIGHT * (self.Masked_STD() - self.initial_STD) ** 2).mean(0) + \
-                    (TV_Loss(self._image(), self.image_mask, clamp01=True) if not self.model_training else
-                     TV_Loss(self.output_image if self.image_mask is None else self.output_image * self.image_mask))
-            else:
-                Z_loss = self.Masked_STD()
-                if any(p in self.objective for p in ['increase', 'decrease']):
-                    Z_loss = (Z_loss - self.desired_STD) ** 2
-                Z_loss = Z_loss.mean(0)
-            if 'max' in self.objective:
+            Z_loss, loss = self.family.loss(self), self._global_loss
+            if self.family.sign < 0:
                 Z_loss = -1 * Z_loss
-            if self.non_local_Z_optimization and self.objective != 'scribble':
+            if self.non_local_Z_optimization and self._constraint is None:
                 # the region constraint's share of l1 over the GLOBAL batch, on the scribble kernels
                 image = self._image()
-                constraint = esr_scribble.region_constraint(image, self.constraint_spec, norm=self.global_batch * image[0].numel())
+                self._constraint = esr_scribble.region_constraint(image, self.constraint_spec, norm=self.global_batch * image[0].numel())
             self.latest_Z_loss_values = [v.item() for v in Z_loss.reshape(-1)]
             # mean over the GLOBAL batch (reference :742): this shard contributes sum/B_global
             if loss is None:
                 loss = Z_loss.reshape(-1).sum() / self.global_batch if Z_loss.numel() > 1 else Z_loss.mean() * (self.shard[1] - self.shard[0]) / self.global_batch
             if self.non_local_Z_optimization:            # (reference :743-746)
-                loss = loss + self.constraining_loss_weight * constraint
+                loss = loss + self.constraining_loss_weight * self._constraint
             loss.backward()
             self.loss_values.append(esr_dist.all_reduce_mean_scalar(loss.item(), self.device) * esr_dist.world_size())
             self.optimizer.step()
@@ -701,7 +477,7 @@ class Z_optimizer():
             print('Minimum loss observed in %d/%d iteration, discarding subsequent iterations.' % (min_loss_iter + 1, len(self.loss_values)))
             self.Z_model.Z.data = 1 * per_iter_pre_tanh_Z[min_loss_iter]
             self.loss_values = self.loss_values[:min_loss_iter + 1]
-        if self.random and 'limited' in self.objective and len(self.loss_values) > 1:
+        if self.family.limited and len(self.loss_values) > 1:
             # the first value is close to 0 there (every sample still next to the initial image): a later loss must not look like an increase
             # against it (reference :765-766, which raises IndexError when a single value is left)
             self.loss_values[0] = self.loss_values[1]

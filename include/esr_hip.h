@@ -510,8 +510,12 @@ int esr_adam_run(const void* workspace, int n, int64_t nchunks, float lr, float 
  *   kind 1  TV_Loss          codes/Z_optimization.py:324-326                                                       sums[b] = (sum |dx|, sum |dy|, -)
  *   kind 2  structure tensor codes/models/modules/loss.py:49-62,141-151 (2x2 difference filters, (H-1) x (W-1) frame)  sums[b] = (sum ix^2, sum iy^2, sum ix iy)
  * x: fp32 [B][C][H][W]; v = clamp(x, 0, 1) when clamp01 (the reference's Output_Batch(within_0_1=True)), times mask [H][W] when given (the GUI's
- * image mask).  sums: [B][3] doubles, zeroed by the caller (the kernels add).  _grad: dx = sum_k coef[b][k] * d sums[b][k] / dx in closed form
- * (the caller folds the scalar ops after the reduction — sqrt, division by N — into coef); accumulate != 0 adds into dx. */
+ * image mask).  sums: [B][3] doubles, zeroed by the caller (the kernels add).  _grad: dx (+)= the gradient of a scalar of the three sums whose
+ * chain rule the caller has folded (sqrt, division by N) into coef[b][3], the coefficients of the closed forms of csrc/esr_zobj.hip:
+ *   kind 0  d/dx ( coef0/2 sums1 + coef1 sums0 )                    = (coef0 v + coef1) dv/dx
+ *   kind 1  d/dx ( coef0 sums0 + coef1 sums1 )
+ *   kind 2  d/dx ( coef0/2 sums0 + coef1/2 sums1 + coef2 sums2 )    (d/d ix = coef0 ix + coef2 iy, d/d iy = coef1 iy + coef2 ix)
+ * with dv/dx = mask [0 <= x <= 1] as asked; accumulate != 0 adds into dx. */
 int esr_img_stats(const float* x, int B, int C, int H, int W, const float* mask, int clamp01, int kind, double* sums, esr_stream_t stream);
 int esr_img_stats_grad(const float* x, int B, int C, int H, int W, const float* mask, int clamp01, int kind, const float* coef, float* dx, int accumulate,
                        esr_stream_t stream);

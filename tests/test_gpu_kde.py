@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle.weights import fill_formula_weights, seeded_uniform
+from oracle.zobj_contract_ref import _ref_cols, _ref_rows, _scores
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'patch_kde.npz')
@@ -45,44 +46,6 @@ def test_soft_histogram_loss_matches_the_reference(case):
 
 
 # ---------------------------------------------------------------------------------------------- float64 restatement of the formulas
-def _scores(x, b, P=1.0, eps=1e-7):
-    """[r, M] s_ij = mean_d (min(|δ|, |δ - P|, |δ + P|) + eps)^2, float64"""
-    d = x[:, None, :] - b[None]
-    w = torch.minimum(torch.minimum(d.abs(), (d - P).abs()), (d + P).abs())
-    return ((w + eps) ** 2).mean(2)
-
-
-def _ref_rows(X, bins, T, g, chunk=48):
-    """lse_i = log sum_j exp(-s_ij/T) and d (sum_i g_i lse_i) / dX, float64, chunked over rows"""
-    lse, grads = [], []
-    b = bins.double()
-    for xc, gc in zip(X.double().split(chunk), g.split(chunk)):
-        xc = xc.clone().requires_grad_(True)
-        l = torch.logsumexp(-_scores(xc, b) / T, 1)
-        (l * gc).sum().backward()
-        lse.append(l.detach())
-        grads.append(xc.grad)
-    return torch.cat(lse), torch.cat(grads)
-
-
-def _ref_cols(X, counts, bins, T, g, chunk=48):
-    """lse_bj = log sum_{i in image b} exp(-s_ij/T) and d (sum g_bj lse_bj) / dX, float64 (the gradient through a surrogate with lse fixed)"""
-    b = bins.double()
-    Xd = X.double()
-    lse, r = [], 0
-    for n in counts:
-        lse.append(torch.logsumexp(torch.cat([-_scores(xc, b) / T for xc in Xd[r:r + n].split(chunk)], 0), 0))
-        r += n
-    lse = torch.stack(lse)
-    img = torch.repeat_interleave(torch.arange(len(counts), device=X.device), torch.tensor(counts, device=X.device))
-    grads = []
-    for xc, ic in zip(Xd.split(chunk), img.split(chunk)):
-        xc = xc.clone().requires_grad_(True)
-        (g[ic] * torch.exp(-_scores(xc, b) / T - lse[ic])).sum().backward()
-        grads.append(xc.grad)
-    return lse, torch.cat(grads)
-
-
 def _region_patches(seed, side, overlap, no_dc=True, noise=0.0, base=None):
     from esr_hip import kde
     idx = torch.from_numpy(kde.patch_extraction_indexes(np.ones((side, side)), 6, overlap)).cuda()

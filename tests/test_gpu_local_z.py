@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle.weights import fill_formula_weights, seeded_uniform
+from oracle.zobj_contract_ref import shift64, std64
 
 pytestmark = pytest.mark.gpu
 
@@ -44,32 +45,6 @@ def irregular_mask(H, W, seed):
     m[:, -(W // 9):] = 0
     m[H // 4: 3 * H // 4, W // 6: 2 * W // 3] = 1
     return m
-
-
-def std64(x, ps):
-    """float64 restatement: the unbiased STD of every selected window of mean_c clamp(x, 0, 1) -> [P, B], with the zero gradient at flat windows
-    (torch.std's is NaN there)"""
-    v = torch.clamp(x, 0, 1).mean(1)
-    p = v.unfold(1, 7, 1).unfold(2, 7, 1).reshape(v.size(0), -1, 49)[:, ps.flat_idx.to(x.device)]
-    d = p - p.mean(-1, keepdim=True)
-    var = (d * d).sum(-1) / 48
-    return torch.where(var > 0, var.clamp_min(1e-300).sqrt(), torch.zeros_like(var)).t()
-
-
-def shift64(x, mask, pairs):
-    """float64 restatement of the periodicity term with grid_sample / crops -> [B]"""
-    image = torch.clamp(x, 0, 1)
-    m = mask.view(1, 1, *mask.shape)
-    loss = 0
-    for pr in pairs:
-        if pr.interpolated:
-            gp, gm = pr.grids(x.device, torch.float64)
-            gs = lambda im, g: torch.nn.functional.grid_sample(im, g.repeat([im.size(0), 1, 1, 1]), align_corners=False)  # noqa: E731
-            loss = loss + (gs(m, gp) * gs(m, gm) * (gs(image, gp) - gs(image, gm)).abs()).mean(dim=(1, 2, 3))
-        else:
-            (a0, a1, b0, b1), (c0, c1, d0, d1) = pr.crops
-            loss = loss + (m[:, :, a0:a1, b0:b1] * m[:, :, c0:c1, d0:d1] * (image[:, :, a0:a1, b0:b1] - image[:, :, c0:c1, d0:d1]).abs()).mean(dim=(1, 2, 3))
-    return loss
 
 
 def test_patch_std_matches_float64_at_512x384():

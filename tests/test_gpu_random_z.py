@@ -20,12 +20,12 @@ import pytest
 import torch
 
 from oracle.weights import fill_formula_weights, seeded_uniform
+from oracle.zobj_contract_ref import TIE, definition64
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'random_z.npz')
 DEV = 'cuda'
-TIE = 1e-6
 
 
 @pytest.fixture
@@ -35,30 +35,6 @@ def kernels_only(monkeypatch):
     def refuse(*a, **k):
         raise AssertionError('the CPU path of esr_hip.pairmin ran inside a GPU test')
     monkeypatch.setattr(pairmin, '_share_cpu', refuse)
-
-
-def definition64(x, clamp01, mask, init, w):
-    """float64: Z_loss [B] of the definition (the reference's expression, :688-699) with the graph attached to x, and the excluded positions
-    [C, H, W] of the module docstring"""
-    D = torch.clamp(x, 0, 1) if clamp01 else x
-    B = D.size(0)
-    dist = (D.unsqueeze(0) - D.unsqueeze(1)).abs() + torch.eye(B, dtype=D.dtype, device=D.device).view(B, B, 1, 1, 1)        # [a, b, ...]
-    v = dist.min(dim=0)[0]
-    if init is not None:
-        v = v - w * (D - init.double()).abs()
-    if mask is not None:
-        v = v * mask.double()
-    Z = -v.mean(dim=(1, 2, 3))
-    with torch.no_grad():
-        if B == 1:
-            return Z, torch.zeros(D.shape[1:], dtype=torch.bool, device=D.device)
-        two, idx = torch.topk(dist, 2, dim=0, largest=False)                                  # the two smallest over a, and who they are
-        tied = (two[1] - two[0]) < TIE                                                        # [b, ...]
-        raw = x.detach()
-        clamped = ((raw <= 0) | (raw >= 1)) if clamp01 else torch.zeros_like(raw, dtype=torch.bool)
-        both_clamped = torch.gather(clamped, 0, idx[0]) & torch.gather(clamped, 0, idx[1])
-        excluded = (tied & ~both_clamped).any(dim=0)
-    return Z, excluded
 
 
 def make_case(B, H, W, seed, clamp01, masked, limited, init_batch=None):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle.weights import fill_formula_weights, seeded_uniform
+from oracle.zobj_contract_ref import _ref_stats
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -66,21 +67,6 @@ def test_hist_objective_of_z_optimizer_reduces_the_divergence():
                      initial_Z=z0.clone(), initial_LR=0.1, batch_size=2)
     z = zo.optimize()
     assert all(np.isfinite(zo.loss_values)) and zo.loss_values[-1] < zo.loss_values[0] and float((z - z0).abs().max()) > 1e-3
-
-
-def _ref_stats(x, mask, clamp01, kind):
-    v = x.double()
-    if clamp01:
-        v = torch.clamp(v, 0, 1)
-    if mask is not None:
-        v = v * mask.double()
-    if kind == 0:
-        return torch.std(v, dim=(1, 2, 3))
-    if kind == 1:
-        return (v[:, :, :, :-1] - v[:, :, :, 1:]).abs().mean(dim=(1, 2, 3)) + (v[:, :, :-1, :] - v[:, :, 1:, :]).abs().mean(dim=(1, 2, 3))
-    ix = (v[..., :, 1:] - v[..., :, :-1])[..., :-1, :]
-    iy = (v[..., 1:, :] - v[..., :-1, :])[..., :, :-1]
-    return torch.stack([(ix * ix).mean(dim=(1, 2, 3)), (iy * iy).mean(dim=(1, 2, 3)), (ix * iy).mean(dim=(1, 2, 3))], 0)
 
 
 @pytest.mark.parametrize('kind', [0, 1, 2])
